@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- HiFi Gbases/s through syncasm (syncmer + syncerr) at k = 1001 on MI355X: BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config3|config2|config5] [--reads-per-gpu R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config3|config2|config5] [--reads-per-gpu R] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic HiFi reads that is already resident in HBM when the
 timed region starts: run_syncasm.c:81-131 without the file parsing --
@@ -16,7 +16,10 @@ is BASELINE.json configs[3]: the SAME 2 M reads sharded by record over the N GPU
 the graph built from everybody's candidate pairs, every rank correcting its own reads (include/oatk_hip_multi.h over RCCL); the `weak`
 sub-object repeats the step with 2 M reads on EVERY GPU (--scaling weak makes that the headline instead).
 
-Prints ONE JSON line on rank 0.  `value` is the whole step above.  Sub-objects: `scan_count` (the same batch through scan +
+Prints ONE JSON line on rank 0.  `value` is the whole step above.  A plain run sets up, warms up, times the --steps steps and prints the
+line with the headline, its phases and the roofline of the dominant kernel (priced from the timed steps themselves); --dump-outputs DIR
+also writes what the last timed step computed as DIR/<name>.npy (float64; see dump_outputs).  Everything below that takes runs of its
+own is measured only with --full.  Sub-objects (--full): `scan_count` (the same batch through scan +
 count only), `config2` (BASELINE.json configs[1]: 200 k reads, scan + count, and with the EC round), `results_back` (SURVEY 8d
 timing ii: pinned host ASCII -> device -> the reference's sr_t arrays filled on the host), `ingest` (from FASTA text, PCIe
 included), `cli` (timing iii: the drop-in syncasm CLI against the reference's CLI on the same FASTA file, when both binaries
@@ -55,6 +58,11 @@ def parse_args():
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="at N > 1: strong (default) = the workload's reads divided over the GPUs (BASELINE.json configs[3] for config3); weak = the workload's reads on every GPU")
     ap.add_argument("--no-weak", action="store_true", help="at N > 1 with strong scaling: skip the `weak` sub-object (the workload's reads on every GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every measurement beyond the headline (CPU baselines, the other workloads and EC graph, the legs after the EC round, results back, "
+                         "ingest, the CLI comparisons, weak scaling); --no-extras and --no-cpu-baseline then leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (corrected chains, syncmer table, EC statistics) as DIR/<name>.npy in float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL; the contract) or gloo (development: several ranks on ONE GPU)")
     ap.add_argument("--no-extras", action="store_true", help="headline + roofline only: no scan_count / config2 / results_back / ingest / cli legs")
@@ -78,7 +86,10 @@ def parse_args():
     ap.add_argument("--cpu-sample-reads", type=int, default=80000)
     ap.add_argument("--cpu-threads", type=int, default=8)
     ap.add_argument("--dist-timeout-s", type=int, default=600, help="a collective that does not complete within this aborts the run instead of hanging it")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:                       # a plain run measures the headline only
+        args.no_extras = args.no_cpu_baseline = True
+    return args
 
 
 def write_fasta(path, seq, off, lens, n):
@@ -402,6 +413,10 @@ def main():
             ec_summary["imported_kmers_rank0"] = sharded.n_imported
         if comm:
             ec_summary["imported_kmers_rank0"] = n_imp[0]
+    if args.dump_outputs and rank == 0:
+        if st is None:
+            raise SystemExit("--dump-outputs: the timed step ran no EC round (--no-sharded-syncerr, or --steps 0): nothing to write")
+        dump_outputs(hip, st, args.dump_outputs)
 
     extras = {}
     pending_cli_gz, hip_closed = None, False
@@ -814,6 +829,45 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE_READS = 8192            # reads whose corrected chains --dump-outputs writes in full
+DUMP_SAMPLE_SCM = 1 << 19           # syncmers of the updated table it writes (all of them when there are fewer)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(hip, st, out_dir):
+    """What a caller of the timed path receives from its last step, as float64 .npy files (every value exact: u32 fields as they are, u64 fields
+    as their two 32-bit halves where they can exceed 2^53):
+        ec_stats            the 12 statistics of read_error_correction
+        ec_n_scm            syncmers per read after correction, every read
+        sample_reads        the reads of a fixed, seeded sample (at most DUMP_SAMPLE_READS, ascending)
+        sample_chain_len    their chain lengths; sample_kmer (id << 1 | corrected), sample_mpos, sample_smer_hi / _lo: their corrected chains, concatenated
+        scm_sample          the syncmers of a fixed, seeded sample of the updated table (all of them when it is small), ascending
+        scm_cov, scm_del    their coverage and deletion flag after update_syncmer_db
+    The sample depends on the number of reads and syncmers only, so two builds that compute the same step write the same files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    hip.sync()
+    n_scm = hip.fetch("EC_N_SCM")
+    scm_off = hip.fetch("EC_SCM_OFF")
+    kmer, mpos, smer = hip.fetch("EC_KMER"), hip.fetch("EC_MPOS"), hip.fetch("EC_SMER")
+    cov, dele = hip.fetch("EC_SCM_COV"), hip.fetch("EC_SCM_DEL")
+    rng = np.random.default_rng(DUMP_SEED)
+    n_reads = len(n_scm)
+    reads = np.sort(rng.choice(n_reads, min(DUMP_SAMPLE_READS, n_reads), replace=False)) if n_reads else np.zeros(0, np.int64)
+    idx = np.concatenate([np.arange(int(scm_off[r]), int(scm_off[r]) + int(n_scm[r])) for r in reads]) if len(reads) else np.zeros(0, np.int64)
+    idx = idx.astype(np.int64)
+    scm = np.sort(rng.choice(len(cov), min(DUMP_SAMPLE_SCM, len(cov)), replace=False)) if len(cov) else np.zeros(0, np.int64)
+    assert len(kmer) == 0 or int(kmer.max()) < (1 << 53), "EC_KMER holds ids beyond float64's exact integers"
+    s = smer[idx]
+    out = {"ec_stats": st, "ec_n_scm": n_scm, "sample_reads": reads, "sample_chain_len": n_scm[reads],
+           "sample_kmer": kmer[idx], "sample_mpos": mpos[idx], "sample_smer_hi": s >> np.uint64(32), "sample_smer_lo": s & np.uint64(0xFFFFFFFF),
+           "scm_sample": scm, "scm_cov": cov[scm], "scm_del": dele[scm]}
+    total = sum(np.asarray(a).size * 8 for a in out.values())
+    assert total <= 64 << 20, "--dump-outputs would write %d bytes" % total
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a).astype(np.float64))
 
 
 def scale_model(n1, ms1, tr1, n8, ms8, tr8, bases1, ms_headline):

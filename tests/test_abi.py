@@ -75,3 +75,68 @@ def test_the_scale_model_of_bench_is_plain_arithmetic_on_its_inputs():
         assert prev is None or p["parts_ms"]["compute"] < prev
         prev = p["parts_ms"]["compute"]
         assert abs(p["speedup_over_1"] - 90.0 / p["ms_per_step"]) < 0.01
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_a_plain_bench_run_measures_the_headline_only(monkeypatch):
+    """bench.py without --full leaves every leg beyond the headline out; --full brings them back, and --no-extras / --no-cpu-baseline still narrow it"""
+    import sys
+    b = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1"])
+    a = b.parse_args()
+    assert (a.full, a.no_extras, a.no_cpu_baseline, a.steps, a.warmup, a.dump_outputs) == (False, True, True, 3, 1, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = b.parse_args()
+    assert (a.full, a.no_extras, a.no_cpu_baseline, a.dump_outputs) == (True, False, False, "d")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = b.parse_args()
+    assert (a.no_extras, a.no_cpu_baseline) == (False, True)
+
+
+def test_bench_dump_outputs_are_exact_float64_and_repeatable(tmp_path):
+    """--dump-outputs: float64 files that hold every value exactly (u64 hashes as two halves), the same sample on every run, within 64 MB"""
+    import numpy as np
+    b = _bench_module()
+    rng = np.random.default_rng(5)
+    n_reads, n_vtx = 20000, 3000
+    n = rng.integers(0, 40, n_reads).astype(np.uint32)
+    off = np.zeros(n_reads + 1, np.uint64)
+    off[1:] = np.cumsum(n)
+    tot = int(off[-1])
+    bufs = {"EC_N_SCM": n, "EC_SCM_OFF": off, "EC_KMER": (rng.integers(0, n_vtx, tot).astype(np.uint64) << np.uint64(1)) | np.uint64(1),
+            "EC_MPOS": rng.integers(0, 1 << 31, tot).astype(np.uint32), "EC_SMER": rng.integers(0, 1 << 63, tot, dtype=np.uint64) * np.uint64(2) + np.uint64(1),
+            "EC_SCM_COV": rng.integers(0, 100, n_vtx).astype(np.uint32), "EC_SCM_DEL": rng.integers(0, 2, n_vtx).astype(np.uint8)}
+
+    class FakeHip:
+        def sync(self):
+            pass
+
+        def fetch(self, name):
+            return bufs[name].copy()
+    st = np.arange(12, dtype=np.uint64)
+    b.dump_outputs(FakeHip(), st, str(tmp_path / "a"))
+    b.dump_outputs(FakeHip(), st, str(tmp_path / "b"))
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == sorted(os.listdir(str(tmp_path / "b"))) and "ec_stats.npy" in names and "ec_n_scm.npy" in names
+    total = 0
+    for f in names:
+        x, y = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert x.dtype == np.float64 and np.array_equal(x, y), f
+        total += x.nbytes
+    assert total <= 64 << 20
+    ld = lambda f: np.load(str(tmp_path / "a" / (f + ".npy")))      # noqa: E731
+    reads = ld("sample_reads").astype(np.int64)
+    assert len(reads) == b.DUMP_SAMPLE_READS and np.all(np.diff(reads) > 0)
+    idx = np.concatenate([np.arange(int(off[r]), int(off[r + 1])) for r in reads])
+    smer = (ld("sample_smer_hi").astype(np.uint64) << np.uint64(32)) | ld("sample_smer_lo").astype(np.uint64)
+    assert np.array_equal(smer, bufs["EC_SMER"][idx])
+    assert np.array_equal(ld("sample_kmer").astype(np.uint64), bufs["EC_KMER"][idx])
+    assert np.array_equal(ld("ec_n_scm"), n.astype(np.float64)) and np.array_equal(ld("ec_stats"), st.astype(np.float64))
+    assert np.array_equal(ld("scm_cov"), bufs["EC_SCM_COV"].astype(np.float64))     # a small table goes whole
