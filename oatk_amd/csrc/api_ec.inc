@@ -717,45 +717,511 @@ extern "C" int oatk_hip_ec_reserve_import(oatk_hip_ctx *ctx, uint64_t bytes)
     return OATK_OK;
 }
 
-// Every switch of the error-block solver that the environment can set, read in ONE place at the start of a call (round 6; until then some twenty getenv calls sat on
-// the launch path).  None of them changes a result: tiers, budgets, carve-ups and A/B switches for tests and measurements (tests/test_gpu_ec.py runs nine combinations
-// against the compiled reference); defaults are what ships.
+// Every switch of the error-block solver that the environment can set, read in ONE place at the start of a call.  None of them changes a result, and each is
+// here because a test or a tool drives it (tests/test_gpu_ec.py runs the solver's variants against the compiled reference); defaults are what ships.
 struct EcKnobs {
-    int heavy = -1;               // OATK_DEBUG_EC_HEAVY=0: always the tiers of round 4 (one wave per block, larger LDS carve-ups, HBM slabs); =1: always the classes with budgets and the second
-                                  // stage; unset: by the graph -- the tiers when no vertex of the live graph has two arcs out (oatk_hip_ec_correct)
-    bool fused = true;            // OATK_DEBUG_EC_FUSED=0: no step budget, no second stage (a workgroup per block with a barrier per step: round 5's first form)
-    bool cert = true;             // OATK_DEBUG_EC_CERT=0: the second stage without the table test for long arcs
+    int heavy = -1;               // OATK_DEBUG_EC_HEAVY=0: always round 4's tiers (ec_solve_tiers); =1: always the classes with budgets and the second stage
+                                  // (ec_solve_classes); unset: by the graph (oatk_hip_ec_correct).  Tests name the solver of every variant but "device"
     bool stages = false;          // OATK_DEBUG_EC_STAGES: the stages' sizes and times on stderr
-    bool serial_tiers = false;    // OATK_DEBUG_EC_SERIAL_TIERS=1, no_hybrid: OATK_DEBUG_EC_NO_HYBRID=1 (round 4's tiers only)
-    bool no_hybrid = false;
+    bool serial_tiers = false;    // OATK_DEBUG_EC_SERIAL_TIERS=1: the tiers with nothing routed (tests: besides a K too large for tier 0, the only way into that flow)
     int32_t step_budget = 1000;   // OATK_DEBUG_EC_STEP_BUDGET: wavefront steps after which a first-stage class gives a block up (tests: 1 sends everything on; 3000 until r06: 242 -> 228 ms on the surrogate)
-    int32_t arc_budget = 512;     // OATK_DEBUG_EC_ARC_BUDGET: arcs (and twice as many wavefront steps) after which the first tier gives a block up; 0: never
-    int32_t min_nw = 0;           // OATK_DEBUG_EC_FUSED_MIN_NW: the second stage's narrowest class has that many waves (0 / 1: the single-wave class too)
-    int32_t heavy_cap2 = 0;       // OATK_DEBUG_EC_HEAVY_CAP2: longest block of the second class (tests)
-    int32_t heavy_fl = 0;         // OATK_DEBUG_EC_HEAVY_FL: bytes of the LDS frame arena (tests: 64 sends every frame to HBM)
-    int32_t heavy_wgs = 0;        // OATK_DEBUG_EC_HEAVY_WGS: workgroups of a class's launch
-    int32_t capf = 0, capp = 0;   // OATK_DEBUG_EC_CAPF / _CAPP: the first tier's frame bytes / path entries
-    int32_t waves = 32;           // OATK_DEBUG_EC_WAVES: first-tier waves per CU
-    int32_t cap_t0 = 3072;        // OATK_DEBUG_EC_CAP_T0: longest block of the first tier
+    int32_t min_nw = 0;           // OATK_DEBUG_EC_FUSED_MIN_NW: the second stage's narrowest class has that many waves (0 / 1: the single-wave class too; tests: 2, 4, 8, 16)
+    int32_t heavy_cap2 = 0;       // OATK_DEBUG_EC_HEAVY_CAP2: longest block of the second class (tests: blocks the cases would not send there)
+    int32_t heavy_fl = 0;         // OATK_DEBUG_EC_HEAVY_FL: bytes of the classes' LDS frame arena (tests: 64 sends every frame to HBM)
+    int32_t waves = 32;           // OATK_DEBUG_EC_WAVES: first-tier waves per CU (tools/solverbench.py)
 };
 static EcKnobs ec_knobs_read()
 {
     EcKnobs k;
-    auto flag0 = [](const char *n) { const char *e = getenv(n); return !(e && e[0] == '0' && !e[1]); };      // on unless "0"
-    auto flag1 = [](const char *n) { const char *e = getenv(n); return e && e[0] == '1'; };
     auto num = [](const char *n, int32_t lo, int32_t dflt) { const char *e = getenv(n); return e && atoi(e) >= lo? (int32_t) atoi(e) : dflt; };
     { const char *e = getenv("OATK_DEBUG_EC_HEAVY"); k.heavy = e && (e[0] == '0' || e[0] == '1') && !e[1]? e[0] - '0' : -1; }
-    k.fused = flag0("OATK_DEBUG_EC_FUSED"), k.cert = flag0("OATK_DEBUG_EC_CERT");
     k.stages = getenv("OATK_DEBUG_EC_STAGES") != nullptr;
-    k.serial_tiers = flag1("OATK_DEBUG_EC_SERIAL_TIERS"), k.no_hybrid = flag1("OATK_DEBUG_EC_NO_HYBRID");
+    { const char *e = getenv("OATK_DEBUG_EC_SERIAL_TIERS"); k.serial_tiers = e && e[0] == '1'; }
     k.step_budget = num("OATK_DEBUG_EC_STEP_BUDGET", 1, 1000);
-    { const char *e = getenv("OATK_DEBUG_EC_ARC_BUDGET"); k.arc_budget = e? atoi(e) : 512; }
     k.min_nw = num("OATK_DEBUG_EC_FUSED_MIN_NW", 2, 0);
-    k.heavy_cap2 = num("OATK_DEBUG_EC_HEAVY_CAP2", 1, 0), k.heavy_fl = num("OATK_DEBUG_EC_HEAVY_FL", 64, 0) & ~7, k.heavy_wgs = num("OATK_DEBUG_EC_HEAVY_WGS", 1, 0);
-    k.capf = num("OATK_DEBUG_EC_CAPF", 256, 0) & ~7, k.capp = num("OATK_DEBUG_EC_CAPP", 8, 0), k.waves = num("OATK_DEBUG_EC_WAVES", 1, 32);
-    k.cap_t0 = num("OATK_DEBUG_EC_CAP_T0", 64, 3072);
+    k.heavy_cap2 = num("OATK_DEBUG_EC_HEAVY_CAP2", 1, 0), k.heavy_fl = num("OATK_DEBUG_EC_HEAVY_FL", 64, 0) & ~7;
+    k.waves = num("OATK_DEBUG_EC_WAVES", 1, 32);
     return k;
 }
+
+namespace oatk {
+
+// ---- the solver's pieces: oatk_hip_ec_correct runs one of two strategies, ec_solve_classes or ec_solve_tiers, and both are made of these ----
+static const int32_t EC_CAP_T0 = 3072;         // longest block of the first tier (test hook: oatk_hip_debug_ec_tiers)
+static const int32_t EC_CAP_T1 = 16384;        // longest block of round 4's last LDS tier (the same hook)
+static const int32_t EC_ARC_BUDGET = 512;      // arcs (and twice as many wavefront steps) after which the classes' first tier gives a block up
+
+// a carve-up of ec_wave.hpp: its limits, the LDS of one wave, and (hybrid) the HBM slab of one wave
+struct EcTier { int32_t cap_t, cap_c, cap_w, cap_path, cap_f; uint64_t bytes, slab; bool usable, hybrid; int wpb; };
+
+static int32_t ec_cap_c(int32_t cap_t, int K) { return cap_t + cap_t / 8 + 2 * K + 64; }       // the consensus of a block of cap_t bases
+
+// the longest block whose band fits bwmax diagonals (bw = ceil(l * max_edist)), at most 60 000 bases
+static int32_t ec_band_cap(int32_t bwmax, double max_edist)
+{
+    int64_t ct = max_edist > 0? (int64_t) floor((double) bwmax / max_edist) : 0x3FFFFFFF;
+    while (ct > 0 && (int32_t) ceil((double) ct * max_edist) > bwmax) --ct;
+    return (int32_t) (ct > 60000? 60000 : ct);
+}
+
+// workgroups of `bytes` of LDS each that one CU holds: 160 KiB of LDS, at most 16 workgroups, at least one
+static uint64_t ec_wg_per_cu(uint64_t bytes)
+{
+    const uint64_t n = 160 * 1024 / (bytes + 256);
+    return n > 16? 16 : (n? n : 1);
+}
+
+// an LDS tier of ec_wave.hpp (MODE 0: every array in LDS).  Hybrid (MODE 2): only what the alignment reads in LDS; the paths and DFS frames lie in an HBM slab
+// per wave -- a path may be as long as the consensus has bases, and 1 MB holds a few thousand levels that all branch.
+static EcTier ec_lds_tier(int32_t cap_t, int32_t cap_path, int32_t cap_f, bool hybrid, double max_edist, int K)
+{
+    EcTier t;
+    const int32_t bw = (int32_t) (cap_t * max_edist) + 1;
+    t.cap_t = cap_t, t.cap_w = 2 * (bw > EC_MIN_ERR_BASE? bw : EC_MIN_ERR_BASE) + 12, t.cap_c = ec_cap_c(cap_t, K);
+    t.hybrid = hybrid;
+    if (hybrid) {
+        t.cap_path = t.cap_c, t.cap_f = 1 << 20;
+        t.bytes = (uint64_t) ecw_lds_words_hybrid(t.cap_t, t.cap_c, t.cap_w) * 4;
+        t.slab = ecw_slab_bytes_hybrid(t.cap_path, t.cap_f);
+    } else {
+        t.cap_path = cap_path, t.cap_f = cap_f;
+        t.bytes = (uint64_t) ecw_scratch_words(t.cap_t, t.cap_c, t.cap_w, t.cap_path, t.cap_f, false) * 4;
+        t.slab = 0;
+    }
+    t.usable = t.bytes <= 64 * 1024;                        // (a very large K goes straight to the slabs)
+    t.wpb = ECW_WPB * t.bytes <= 64 * 1024? ECW_WPB : 1;    // waves per workgroup, each with its own carve-up
+    return t;
+}
+
+// waves of an LDS tier's launch: what the CUs hold, at most per_cu_max a CU (the hardware places at most 16 workgroups on a CU, so the waves come in workgroups
+// of t.wpb that share nothing)
+static uint64_t ec_tier_waves(const EcTier &t, int32_t per_cu_max, int n_cu)
+{
+    uint64_t per_cu = ec_wg_per_cu((uint64_t) t.wpb * t.bytes) * (uint64_t) t.wpb;
+    if (per_cu > (uint64_t) per_cu_max) per_cu = (uint64_t) per_cu_max / (uint64_t) t.wpb * (uint64_t) t.wpb;
+    return (uint64_t) n_cu * (per_cu? per_cu : (uint64_t) t.wpb);
+}
+
+// words of one wave's optimum consensus in an LDS tier (it lives in HBM: ec_wave_kernel)
+static uint64_t ec_os_words(int32_t cap_c) { return ((uint64_t) ecw_words(cap_c) + 15) & ~15ULL; }
+
+static void ec_set_caps(EcwArgs &a, const EcTier &t) { a.cap_t = t.cap_t, a.cap_c = t.cap_c, a.cap_w = t.cap_w, a.cap_path = t.cap_path, a.cap_f = t.cap_f; }
+
+// one launcher per kernel family: `lds` bytes of LDS per wave (ec_wave_kernel) or per workgroup (the others)
+template <int MODE, int WPB> static void ec_wave_launch(uint64_t waves, uint64_t lds, hipStream_t st, const EcwArgs &a)
+{
+    hipLaunchKernelGGL((ec_wave_kernel<MODE, WPB>), dim3((unsigned) ((waves + WPB - 1) / WPB)), dim3(64 * WPB), (unsigned) (WPB * lds), st, a);
+}
+static void ec_launch_lds_tier(const EcTier &t, uint64_t waves, hipStream_t st, const EcwArgs &a)
+{
+    if (t.wpb > 1) {
+        if (t.hybrid) ec_wave_launch<2, ECW_WPB>(waves, t.bytes, st, a);
+        else ec_wave_launch<0, ECW_WPB>(waves, t.bytes, st, a);
+    } else {
+        if (t.hybrid) ec_wave_launch<2, 1>(waves, t.bytes, st, a);
+        else ec_wave_launch<0, 1>(waves, t.bytes, st, a);
+    }
+}
+template <int NW, int R> static void ec_heavy_launch(uint64_t wgs, uint64_t lds, hipStream_t st, const EcwArgs &a)
+{
+    hipLaunchKernelGGL((ec_heavy_kernel<NW, R>), dim3((unsigned) wgs), dim3(64 * NW), (unsigned) lds, st, a);
+}
+template <int NW> static void ec_fused_launch(uint64_t wgs, uint64_t lds, hipStream_t st, const EcwArgs &a)
+{
+    hipLaunchKernelGGL((ec_fused_kernel<NW>), dim3((unsigned) wgs), dim3(64 * NW), (unsigned) lds, st, a);
+}
+
+// the next of the call's HBM slab buffers: launches that may run side by side each take one of their own
+static int ec_slab_buf(oatk_hip_ctx *ctx, EcState *e, int &k, uint64_t bytes, hipStream_t st, const char *who, const char *what, void **p)
+{
+    if (k >= 16) { ctx->err = std::string("EC solver: more launches of ") + who + " than slab buffers (internal)"; return OATK_E_STATE; }
+    DevBuf &b = e->hyb_slabs[k++];
+    if (!b.ensure(bytes, st)) { ctx->err = std::string("hipMalloc failed for ") + who + "'s " + what; return OATK_E_NOMEM; }
+    *p = b.p;
+    return OATK_OK;
+}
+
+// the solver's side streams (made once per handle), and the fork event recorded on the handle's stream
+static int ec_fork_side_streams(oatk_hip_ctx *ctx, EcState *e)
+{
+    if (!e->aux[0]) {
+        // (Streams share the runtime's hardware queues -- four per priority level by default, handed out by use count -- and two launches on one queue run one AFTER
+        //  the other: with the reads' uploader, the handle's own stream and a host program's streams about, the second stage's four classes were seen running
+        //  8 waves, then 4 waves (rocprofv3 kernel trace, round 6).  The solver's side streams are the only ones of their priority level, so they get queues of their own.)
+        int pr_least = 0, pr_greatest = 0;
+        CK(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
+        for (int i = 0; i < 5; ++i) { CK(hipStreamCreateWithPriority(&e->aux[i], hipStreamNonBlocking, i < 4? pr_greatest : pr_least)); CK(hipEventCreateWithFlags(&e->aux_ev[i], hipEventDisableTiming)); }
+        CK(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
+    }
+    CK(hipEventRecord(e->fork_ev, ctx->stream));
+    return OATK_OK;
+}
+
+// every work item onto the list of the first tier or class whose longest block holds it; the lists' counts back to the host
+static int ec_route(oatk_hip_ctx *ctx, EcState *e, uint64_t n_work, const EcRoute &rt, unsigned long long *routed, size_t bytes)
+{
+    hipLaunchKernelGGL(ec_route_kernel, dim3((unsigned) ((n_work + 256 * ECW_ROUTE_ITEMS - 1) / (256 * ECW_ROUTE_ITEMS))), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), n_work, rt);
+    CK(hipMemcpyAsync(routed, rt.cnt[0], bytes, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    return OATK_OK;
+}
+
+// a list of blocks, longest first: a block's length is what the host can tell of its search, and the longest search of a batch (0.6 s on the config-1 surrogate)
+// must not start when the others are done.  A radix sort on ~length, its keys and values in todo2 (the caller has made room for 3 (n + 1) words).
+static int ec_sort_longest_first(oatk_hip_ctx *ctx, EcState *e, uint32_t *list, uint64_t n)
+{
+    uint32_t *k_in = e->todo2.as<uint32_t>(), *k_out = k_in + (n + 1), *v_out = k_out + (n + 1);
+    hipLaunchKernelGGL(ec_route_keys_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), list, n, k_in);
+    size_t tb = 0;
+    CK(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, list, v_out, n, 0, 32, ctx->stream));
+    ENSURE(tmp, tb);
+    CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, k_in, k_out, list, v_out, n, 0, 32, ctx->stream));
+    CK(hipMemcpyAsync(list, v_out, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    return OATK_OK;
+}
+
+// The slab tier: deeper than the carve-ups' frames, or longer than their blocks.  One wave per block, every array in an HBM slab sized for the longest read of
+// the batch (ec_wave_kernel MODE 1); what outgrows even that is only counted (cursor[63]) and the call fails.  todo == nullptr: every work item.
+static int ec_launch_slab_tier(oatk_hip_ctx *ctx, EcState *e, const EcwArgs &base, uint32_t &max_hl, const uint32_t *todo, uint64_t n_todo,
+                               unsigned long long *queue, hipStream_t st)
+{
+    if (max_hl == 0) {
+        std::vector<uint32_t> hl(ctx->n_reads);
+        CK(hipMemcpy(hl.data(), ctx->hoco_l.p, ctx->n_reads * 4, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < ctx->n_reads; ++i) if (hl[i] > max_hl) max_hl = hl[i];
+    }
+    EcwArgs a = base;
+    a.cap_t = (int32_t) max_hl + 64, a.cap_c = ec_cap_c(a.cap_t, ctx->K);
+    a.cap_w = 2 * ((int32_t) (max_hl * base.max_edist) + 16) + 16, a.cap_path = ec_cap_c((int32_t) max_hl, ctx->K), a.cap_f = 1 << 22;
+    a.todo = todo, a.n_todo = n_todo, a.next = queue, a.skip_l = 0x7FFFFFFF, a.batch = 1;
+    a.todo_out = e->todo2.as<uint32_t>(), a.todo_cnt = base.pool_cursor + 63;
+    a.slab_bytes = ((uint64_t) ecw_scratch_words(a.cap_t, a.cap_c, a.cap_w, a.cap_path, a.cap_f) * 4 + 63) & ~63ULL;
+    uint64_t waves = todo? n_todo : base.n_work;
+    if (waves > 1024) waves = 1024;
+    if (!waves) return OATK_OK;
+    EENSURE(big_slabs, waves * a.slab_bytes);
+    a.slabs = e->big_slabs.as<uint8_t>();
+    ec_wave_launch<1, 1>(waves, 0, st, a);
+    return OATK_OK;
+}
+
+// The second stage: the blocks that went past the first stage's step budget or outgrew a class (`todo`, nh of them), several steps per barrier, longest first.
+// A wave owns 56 slots of the wavefront (ec_fused.hpp), a block needs 2 bw + 3: classes of 16, 8, 4 and 2 waves -- the fewer waves meet, the cheaper the meeting, the
+// fewer copies of the search's scalar bookkeeping run (every wave of a block executes all of it: 276 scalar + 150 vector instructions per arc and wave on the
+// config-1 surrogate, profiles/r06b_config1s_pmc_ec.csv -- the second stage is bound by instruction issue while every CU is full) and the more blocks a CU holds.
+// The narrowest bands (2 bw + 3 <= 64: blocks of up to 1500 bases) take ONE wave each, the wavefront a diagonal per lane in registers, no barrier anywhere
+// (ec_heavy.hpp with NW = 1, the first stage's engine without its budget): such a block's search is arcs, not steps -- 0.9 steps per arc on four diagonals on the
+// config-1 surrogate, a long arc that dies costs its thirty steps at most -- and two waves that meet at four barriers per arc took 3 us per arc where the first
+// tier's single wave took 1.75.  (Wider bands on one wave, two diagonals per lane, were tried: 78 s of wave time against 104, but their long dying arcs are not
+// asked by table there and the longest block took 451 ms against 209.)  In a list sorted longest first the classes are consecutive stretches.  All launches run
+// side by side; what outgrows one (frames, paths) goes onto `todo_out` (cursor[1], `left` of them) for the slab tier.
+static int ec_second_stage(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, const EcwArgs &base, uint32_t *todo, uint64_t nh, uint32_t *todo_out,
+                           int &qslot, int &hyb_k, unsigned long long &left)
+{
+    unsigned long long *cur = base.pool_cursor;
+    struct timespec ts0, ts1;
+    if (kn.stages) clock_gettime(CLOCK_MONOTONIC, &ts0);
+    if (nh > 1 && nh <= (4u << 20)) {
+        if (3 * (nh + 1) > base.n_work + 1) EENSURE(todo2, 3 * (nh + 1) * 4);
+        int rc = ec_sort_longest_first(ctx, e, todo, nh); if (rc) return rc;
+    }
+    const int NCLS = 5;
+    const int NWS[NCLS] = {16, 8, 4, 2, 1};
+    EcwArgs fa[NCLS];
+    uint64_t lds[NCLS];
+    for (int i = 0; i < NCLS; ++i) {
+        const int NW = NWS[i];
+        EcwArgs &a = fa[i];
+        a = base;
+        a.cap_t = ec_band_cap(((NW == 1? 64 : NW * ECF_OWN) - 3) / 2, base.max_edist);
+        a.cap_c = ec_cap_c(a.cap_t, ctx->K), a.cap_w = 0, a.cap_path = a.cap_c;
+        a.cap_f = kn.heavy_fl? kn.heavy_fl : (NW == 16? 32768 : (NW == 8? 24576 : (NW == 4? 16384 : (NW == 2? 12288 : 8192))));
+        a.os_words = 1 << 20;
+        lds[i] = (uint64_t) (NW == 1? ech_lds_words(a.cap_t, a.cap_c, a.cap_f, 1) : ecf_lds_words(a.cap_t, a.cap_c, a.cap_f, NW)) * 4;
+    }
+    int narrowest = NCLS - 1;                                          // OATK_DEBUG_EC_FUSED_MIN_NW=2: no single-wave class (A/B, tests); =8: the two classes of round 5
+    if (kn.min_nw >= 2) narrowest = kn.min_nw >= 16? 0 : (kn.min_nw >= 8? 1 : (kn.min_nw >= 4? 2 : 3));
+    while (narrowest > 0 && lds[narrowest] > 64 * 1024) --narrowest;
+    // longer[i] = blocks too long for class i + 1 (the head of the sorted list): class i takes todo[longer[i - 1] .. longer[i])
+    unsigned long long longer[NCLS] = {0, 0, 0, 0, 0};
+    CK(hipMemsetAsync(cur + 1, 0, 40, ctx->stream));                  // [1] what is left over, [2 .. 5] the counts
+    for (int i = 0; i < narrowest; ++i)
+        hipLaunchKernelGGL(ec_route_longer_kernel, dim3((unsigned) ((nh + 255) / 256)), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), todo, nh, lds[i + 1] <= 64 * 1024? fa[i + 1].cap_t : -1, cur + 2 + i);
+    CK(hipMemcpyAsync(longer, cur + 2, 32, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    if (nh > (4u << 20)) longer[0] = nh;                               // (unsorted: sixteen waves for all)
+    longer[narrowest] = nh;
+    for (int i = 1; i <= narrowest; ++i) if (longer[i] < longer[i - 1]) longer[i] = longer[i - 1];
+    auto launch = [&](int i, const uint32_t *list, uint64_t n, hipStream_t st) -> int {
+        const int NW = NWS[i];
+        if (lds[i] > 64 * 1024) { ctx->err = "EC solver: the second stage's carve-up does not fit LDS (K too large)"; return OATK_E_STATE; }
+        if (qslot >= 60) { ctx->err = "EC solver: more launches than work-queue counters (internal)"; return OATK_E_STATE; }
+        EcwArgs a = fa[i];
+        a.todo = list, a.n_todo = n, a.next = cur + qslot++, a.skip_l = 0x7FFFFFFF, a.batch = 1, a.arc_budget = 0;
+        a.todo_out = todo_out, a.todo_cnt = cur + 1;
+        a.slab_bytes = ech_slab_bytes(a.cap_c, a.cap_path, (int32_t) a.os_words);
+        uint64_t per_cu = ec_wg_per_cu(lds[i]);                        // one wave per block (ec_heavy.hpp)
+        if (NW > 1) {                                                  // a workgroup per block: 2048 threads a CU
+            const uint64_t by_lds = 160 * 1024 / (lds[i] + 512);
+            per_cu = 2048 / (64 * (uint64_t) NW);
+            if (per_cu > by_lds) per_cu = by_lds;
+            if (per_cu > 16) per_cu = 16;
+            if (!per_cu) per_cu = 1;
+        }
+        uint64_t wgs = (uint64_t) ctx->n_cu * per_cu;
+        if (wgs > n) wgs = n;
+        void *p = nullptr;
+        { int rc = ec_slab_buf(ctx, e, hyb_k, wgs * a.slab_bytes + 64, st, "the workgroup solver", "slabs", &p); if (rc) return rc; }
+        a.slabs = (uint8_t *) p;
+        if (NW == 1) {
+            ec_heavy_launch<1, 1>(wgs, lds[i], st, a);
+            if (kn.stages) fprintf(stderr, "[ec stages] one wave: %llu blocks on %llu waves (%llu B of LDS, slabs %.1f MB)\n", (unsigned long long) n, (unsigned long long) wgs, (unsigned long long) lds[i], wgs * a.slab_bytes / 1e6);
+            return OATK_OK;
+        }
+        { int rc = ec_slab_buf(ctx, e, hyb_k, wgs * ecf_tab_words(a.cap_t) * 4 + 64, st, "the workgroup solver", "tables", &p); if (rc) return rc; }
+        a.os_slabs = (uint32_t *) p;                                   // a region of tables per workgroup
+        if (NW == 2) ec_fused_launch<2>(wgs, lds[i], st, a);
+        else if (NW == 4) ec_fused_launch<4>(wgs, lds[i], st, a);
+        else if (NW == 8) ec_fused_launch<8>(wgs, lds[i], st, a);
+        else ec_fused_launch<16>(wgs, lds[i], st, a);
+        if (kn.stages) fprintf(stderr, "[ec stages] %d waves: %llu blocks on %llu workgroups (%llu B of LDS, slabs %.1f MB)\n", NW, (unsigned long long) n, (unsigned long long) wgs, (unsigned long long) lds[i], wgs * a.slab_bytes / 1e6);
+        return OATK_OK;
+    };
+    CK(hipEventRecord(e->fork_ev, ctx->stream));
+    int used_aux = 0;
+    bool used_low = false;
+    for (int i = 0; i <= narrowest; ++i) {                             // the longest blocks first, each class on a side stream of its own ([4]: the single waves)
+        const uint64_t b0 = i? longer[i - 1] : 0, b1 = longer[i];
+        if (b1 <= b0) continue;
+        const int s = NWS[i] == 1? 4 : used_aux;
+        CK(hipStreamWaitEvent(e->aux[s], e->fork_ev, 0));
+        { int rc = launch(i, todo + b0, b1 - b0, e->aux[s]); if (rc) return rc; }
+        CK(hipEventRecord(e->aux_ev[s], e->aux[s]));
+        if (s == 4) used_low = true; else ++used_aux;
+    }
+    if (used_low) CK(hipStreamWaitEvent(ctx->stream, e->aux_ev[4], 0));
+    for (int i = 0; i < used_aux; ++i) CK(hipStreamWaitEvent(ctx->stream, e->aux_ev[i], 0));
+    CK(hipMemcpyAsync(&left, cur + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    if (kn.stages) { clock_gettime(CLOCK_MONOTONIC, &ts1); fprintf(stderr, "[ec stages] second stage %.1f ms; %llu left for the slabs\n", ((double) (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double) (ts1.tv_nsec - ts0.tv_nsec)) * 1e3, left); }
+    return OATK_OK;
+}
+
+// Round 5's classes with step budgets, then the second stage (the live graph branches: the config-1 surrogate).  Classes by block length: the first tier of
+// ec_wave.hpp (a wave per block, everything in LDS) for the millions of small blocks; three carve-ups of ec_heavy.hpp -- classes 1 and 2 ONE wave per block with
+// the wavefront in 4 / 8 registers per lane (2 bw + 3 <= 64 R: no barrier at all, fifteen blocks a CU), class 3 ECH_NW waves and 6 (2 bw + 3 <= 256 R).  The
+// classes run with a BUDGET of wavefront steps: nearly every block is done within a few dozen (config 3: 258 k blocks past the first tier).  A block that goes
+// past it is a search inside a repeat -- a million steps on hundreds of diagonals -- and starts again in the second stage; what outgrows that, in the slab tier.
+// (A solver that shares a block's search TREE among eight waves was built in round 5, is exact and 2 - 8 x slower on repeats: tools/experiments/ec_tree.hpp.)
+// n_big: the blocks the first tier did not finish.
+static int ec_solve_classes(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, const EcwArgs &base, uint32_t &max_hl, uint64_t &n_big)
+{
+    const uint64_t n_work = base.n_work;
+    unsigned long long *cur = base.pool_cursor;    // [0] pool, [1 .. 4] entries of list[c], [5 ...] one work queue per launch, [63] blocks that outgrew the slabs
+    struct EcClass { int32_t cap_t, cap_c, cap_fl, cap_fh; int R; uint64_t lds, slab; bool usable, routes; } H[4];
+    const int hr[4] = {0, 4, 8, 6};
+    for (int c = 1; c <= 3; ++c) {
+        EcClass &h = H[c];
+        h.R = hr[c];
+        int32_t ct = ec_band_cap(((c < 3? 64 : 256) * h.R - 3) / 2, base.max_edist);
+        if (c == 1 && ctx->ec_cap_t1 > 0 && ctx->ec_cap_t1 < ct) ct = ctx->ec_cap_t1;      // (test hooks: push blocks into the larger classes)
+        if (c == 2 && kn.heavy_cap2 > H[1].cap_t && kn.heavy_cap2 < ct) ct = kn.heavy_cap2;
+        h.cap_t = ct, h.cap_c = ec_cap_c(ct, ctx->K);              // (the paths have cap_c entries: every arc appends at least one base)
+        h.cap_fl = kn.heavy_fl? kn.heavy_fl : (c < 3? 4096 : 32768);
+        h.cap_fh = c < 3? 128 << 10 : 1 << 20;                     // (thousands of single waves: a megabyte of HBM frames each would be gigabytes; what outgrows 128 KB is a heavy search and goes on anyway)
+        h.lds = (uint64_t) ech_lds_words(h.cap_t, h.cap_c, h.cap_fl, h.R) * 4;
+        h.slab = ech_slab_bytes(h.cap_c, h.cap_c, h.cap_fh);
+        h.usable = h.lds <= 64 * 1024;
+        h.routes = h.usable && (c == 1 || h.cap_t > H[c - 1].cap_t);      // (a class that takes no longer blocks than the one before it only takes that one's left-overs)
+    }
+    EcTier T0 = ec_lds_tier(ctx->ec_cap_t0 > 0? ctx->ec_cap_t0 : EC_CAP_T0, 32, 2048, false, base.max_edist, ctx->K);
+    T0.usable = T0.usable && H[1].usable && T0.cap_t <= H[1].cap_t;
+    const uint64_t t0_waves = T0.usable? ec_tier_waves(T0, kn.waves, ctx->n_cu) : 0;
+    EENSURE(os_slabs, (t0_waves + ECW_WPB) * ec_os_words(T0.cap_c) * 4 + 64);
+    // lists 1 .. 3: the classes' blocks (routed there by length, or left over by the first tier); list 4: what the classes gave up on
+    EENSURE(todo, 4 * (n_work + 1) * 4); EENSURE(todo2, (n_work + 1) * 4);
+    uint32_t *list[5] = {nullptr, e->todo.as<uint32_t>(), e->todo.as<uint32_t>() + (n_work + 1), e->todo.as<uint32_t>() + 2 * (n_work + 1), e->todo.as<uint32_t>() + 3 * (n_work + 1)};
+    int qslot = 5, hyb_k = 0;
+    auto launch_class = [&](int c, const uint32_t *todo, uint64_t n_todo, hipStream_t st) -> int {
+        if (!n_todo) return OATK_OK;
+        if (qslot >= 60) { ctx->err = "EC solver: more launches than work-queue counters (internal)"; return OATK_E_STATE; }
+        const EcClass &h = H[c];
+        EcwArgs a = base;
+        a.cap_t = h.cap_t, a.cap_c = h.cap_c, a.cap_w = kn.step_budget, a.cap_path = h.cap_c, a.cap_f = h.cap_fl, a.os_words = (uint64_t) h.cap_fh;
+        a.todo = todo, a.n_todo = n_todo, a.next = cur + qslot++, a.skip_l = 0x7FFFFFFF, a.batch = 1;
+        a.todo_out = list[4], a.todo_cnt = cur + 4;
+        uint64_t wgs = (uint64_t) ctx->n_cu * (c < 3? ec_wg_per_cu(h.lds) : 8);
+        if (wgs > n_todo) wgs = n_todo;
+        while (wgs > (uint64_t) ctx->n_cu && wgs * h.slab > (3ULL << 30)) wgs -= (uint64_t) ctx->n_cu;          // (no launch holds more than three gigabytes of slabs: several handles share a device)
+        void *p = nullptr;
+        { int rc = ec_slab_buf(ctx, e, hyb_k, wgs * h.slab + 64, st, "the workgroup solver", "slabs", &p); if (rc) return rc; }
+        a.slabs = (uint8_t *) p, a.slab_bytes = h.slab;
+        if (c == 1) ec_heavy_launch<1, 4>(wgs, h.lds, st, a);
+        else if (c == 2) ec_heavy_launch<1, 8>(wgs, h.lds, st, a);
+        else ec_heavy_launch<ECH_NW, 6>(wgs, h.lds, st, a);
+        return OATK_OK;
+    };
+    // 1. route by length, the classes of long blocks on streams of their own (longest first: they are the longest chains of dependent steps), the first tier beside them
+    EcRoute rt;
+    for (int c = 0; c < 4; ++c) rt.list[c] = list[c], rt.cnt[c] = cur + c;
+    rt.cap[0] = T0.usable? T0.cap_t : 0, rt.cap[1] = H[1].routes? H[1].cap_t : 0, rt.cap[2] = H[2].routes? H[2].cap_t : 0, rt.cap[3] = 0x7FFFFFFF;
+    unsigned long long routed[5] = {0, 0, 0, 0, 0}, cnts[5] = {0, 0, 0, 0, 0};
+    if (n_work) { int rc = ec_route(ctx, e, n_work, rt, routed, sizeof(routed)); if (rc) return rc; }
+    { int rc = ec_fork_side_streams(ctx, e); if (rc) return rc; }
+    {   // (room to sort a class's list)
+        unsigned long long mx = routed[1] > routed[2]? routed[1] : routed[2];
+        mx = routed[3] > mx? routed[3] : mx;
+        if (mx <= (4u << 20) && 3 * (mx + 1) > n_work + 1) EENSURE(todo2, 3 * (mx + 1) * 4);
+    }
+    int used_aux = 0;
+    for (int c = 3; c >= 1; --c) {
+        if (!routed[c]) continue;
+        if (!H[c].usable) { ctx->err = "EC solver: a class of the workgroup solver does not fit LDS (K too large)"; return OATK_E_STATE; }
+        if (routed[c] > 1 && routed[c] <= (64u << 10)) {               // (the lists are small: thousands of blocks)
+            int rc = ec_sort_longest_first(ctx, e, list[c], routed[c]); if (rc) return rc;
+            CK(hipEventRecord(e->fork_ev, ctx->stream));
+        }
+        hipStream_t st = e->aux[used_aux];
+        CK(hipStreamWaitEvent(st, e->fork_ev, 0));
+        { int rc = launch_class(c, list[c], routed[c], st); if (rc) return rc; }
+        CK(hipEventRecord(e->aux_ev[used_aux], st));
+        ++used_aux;
+    }
+    if (T0.usable && n_work) {
+        EcwArgs a = base;
+        ec_set_caps(a, T0);
+        a.todo = nullptr, a.n_todo = 0, a.next = cur + qslot++, a.skip_l = T0.cap_t, a.batch = ECW_BATCH;
+        // (a small block inside a repeat tries tens of thousands of arcs on a handful of diagonals -- 70 ms of ONE wave on the config-1 surrogate with everything else waiting
+        //  for this launch: past the arc budget it is left to the classes and, past their step budget, to the second stage)
+        a.arc_budget = EC_ARC_BUDGET;
+        a.todo_out = list[1], a.todo_cnt = cur + 1;        // what outgrows the first tier's frames or paths is short: the first class takes it
+        a.os_words = ec_os_words(T0.cap_c), a.os_slabs = e->os_slabs.as<uint32_t>();
+        uint64_t waves = t0_waves;
+        const uint64_t groups = (n_work + (uint64_t) a.batch - 1) / (uint64_t) a.batch;
+        if (waves > groups) waves = groups;
+        ec_launch_lds_tier(T0, waves, ctx->stream, a);
+    }
+    // 2. the first tier's left-overs (deep searches: the longest chains of the batch) as soon as it is done; then everything launched so far; then the second stage
+    CK(hipMemcpyAsync(cnts, cur, sizeof(cnts), hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    if (cnts[1] > routed[1]) { int rc = launch_class(1, list[1] + routed[1], cnts[1] - routed[1], ctx->stream); if (rc) return rc; }
+    n_big = cnts[1] + routed[2] + routed[3];
+    for (int i = 0; i < used_aux; ++i) CK(hipStreamWaitEvent(ctx->stream, e->aux_ev[i], 0));
+    CK(hipMemcpyAsync(cnts, cur, sizeof(cnts), hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    if (kn.stages) fprintf(stderr, "[ec stages] first stage done: %llu blocks go on (classes got %llu + %llu + %llu)\n", cnts[4], cnts[1], routed[2], routed[3]);
+    if (!cnts[4]) return OATK_OK;
+    unsigned long long left = 0;
+    { int rc = ec_second_stage(ctx, e, kn, base, list[4], cnts[4], list[1], qslot, hyb_k, left); if (rc) return rc; }
+    if (!left) return OATK_OK;
+    return ec_launch_slab_tier(ctx, e, base, max_hl, list[1], left, cur + qslot++, ctx->stream);
+}
+
+// Round 4's tiers (the live graph does not branch: config 2 and config 3).  One wave per block in every tier: small LDS carve-ups for every block, larger ones
+// (fewer waves per CU) for the blocks that did not fit, the last of them hybrid, HBM slabs for the rest.  n_big: the blocks the first tier did not finish.
+static int ec_solve_tiers(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, const EcwArgs &base, uint32_t &max_hl, uint64_t &n_big)
+{
+    const int LAST = 3;                  // tiers 0 .. LAST - 1 carve LDS (more per wave, fewer waves per CU), tier LAST uses HBM slabs
+    const uint64_t n_work = base.n_work;
+    unsigned long long *cur = base.pool_cursor;    // [0] pool, [1 .. 3] entries of list[t], [4 ...] one work queue per launch, [63] blocks that outgrew the slabs
+    const int32_t t_lo = ctx->ec_cap_t0 > 0? ctx->ec_cap_t0 : EC_CAP_T0, t_hi = ctx->ec_cap_t1 > 0? ctx->ec_cap_t1 : EC_CAP_T1;
+    EcTier T[LAST + 1];
+    T[0] = ec_lds_tier(t_lo, 32, 2048, false, base.max_edist, ctx->K);
+    T[1] = ec_lds_tier(2 * t_lo < t_hi? 2 * t_lo : t_hi, 64, 4096, false, base.max_edist, ctx->K);
+    T[2] = ec_lds_tier(t_hi, 0, 0, true, base.max_edist, ctx->K);
+    T[LAST] = EcTier{}, T[LAST].usable = true;                 // the slab tier, sized when (if) a block gets there: it takes the longest read of the batch
+    // the LDS tiers' optimum consensus: one slab per wave and launch (a tier is launched at most twice, and tiers run side by side), sized before anything runs
+    uint64_t os_total = 0, os_next = 0;
+    for (int t = 0; t < LAST; ++t) if (T[t].usable) os_total += 3 * (ec_tier_waves(T[t], kn.waves, ctx->n_cu) + ECW_WPB) * ec_os_words(T[t].cap_c);
+    EENSURE(os_slabs, os_total * 4 + 64);
+    // lists: list[t] collects the blocks tier t must run -- routed there by length before anything runs, or left over by a smaller tier
+    EENSURE(todo, 3 * (n_work + 1) * 4); EENSURE(todo2, (n_work + 1) * 4);
+    uint32_t *list[4] = {nullptr, e->todo.as<uint32_t>(), e->todo.as<uint32_t>() + (n_work + 1), e->todo.as<uint32_t>() + 2 * (n_work + 1)};
+    int qslot = 4, hyb_k = 0;
+    auto next_usable = [&](int t) { int u = t + 1; while (u < LAST && !T[u].usable) ++u; return u; };
+    auto launch = [&](int tier, const uint32_t *todo, uint64_t n_todo, hipStream_t st, bool routed, uint64_t max_waves = 0) -> int {
+        if (qslot >= 60) { ctx->err = "EC solver: more rounds of left-overs than queue counters (internal)"; return OATK_E_STATE; }
+        unsigned long long *queue = cur + qslot++;
+        if (tier == LAST) return ec_launch_slab_tier(ctx, e, base, max_hl, todo, n_todo, queue, st);
+        const EcTier &t = T[tier];
+        EcwArgs a = base;
+        ec_set_caps(a, t);
+        a.todo = todo, a.n_todo = n_todo, a.next = queue;
+        a.skip_l = routed && tier == 0? t.cap_t : 0x7FFFFFFF;
+        a.batch = tier == 0? ECW_BATCH : 1;                        // (241 long blocks in batches of sixteen were sixteen waves' work: r04e)
+        // a block outgrows an LDS tier by the depth of its search or by its frames (its length was checked before): the hybrid tier, without such limits, takes it
+        const int nx = tier < LAST - 1 && T[LAST - 1].usable? LAST - 1 : next_usable(tier);
+        a.todo_out = list[nx], a.todo_cnt = cur + nx;
+        uint64_t waves = ec_tier_waves(t, kn.waves, ctx->n_cu);
+        a.os_words = ec_os_words(t.cap_c);
+        if ((os_next + waves * a.os_words) * 4 > e->os_slabs.cap) { ctx->err = "EC solver: more launches than optimum-consensus slabs (internal)"; return OATK_E_STATE; }
+        a.os_slabs = e->os_slabs.as<uint32_t>() + os_next;
+        os_next += waves * a.os_words;
+        const uint64_t n_items = todo? n_todo : n_work;
+        const uint64_t groups = (n_items + (uint64_t) a.batch - 1) / (uint64_t) a.batch;
+        if (waves > groups) waves = groups;
+        if (max_waves && waves > max_waves) waves = max_waves;
+        if (!waves) return OATK_OK;
+        if (t.hybrid) {
+            void *p = nullptr;
+            int rc = ec_slab_buf(ctx, e, hyb_k, (waves + ECW_WPB) * t.slab + 64, st, "the hybrid tier", "slabs", &p); if (rc) return rc;
+            a.slabs = (uint8_t *) p, a.slab_bytes = t.slab;
+        }
+        ec_launch_lds_tier(t, waves, st, a);
+        return OATK_OK;
+    };
+    // 1. route by length (one pass over the work items), then the LDS tiers side by side.  A long block is a long chain of dependent steps and
+    //    its tier's carve-up lets few waves onto a CU, so run after the first tier the larger tiers are a tail of mostly idle CUs (0.8 ms for
+    //    86 blocks at config 2; 4 waves per CU for 4 ms at config 3).  Run BESIDE it they must not crowd it out either: a larger tier starts
+    //    first with a small share of every CU's LDS (a wave per CU, a wave per two CUs), the first tier fills the rest, and when that is
+    //    done a second launch of each larger tier, as wide as it likes, helps empty the same queue.
+    EcRoute rt;
+    for (int t = 0; t <= LAST; ++t) rt.cap[t] = T[t].usable? T[t].cap_t : 0, rt.list[t] = list[t], rt.cnt[t] = cur + t;
+    rt.cap[LAST] = 0x7FFFFFFF;
+    // (measured: at config 2, 0.8 M blocks, side by side saves 0.9 of 3.7 ms.  At config 3, 7.9 M blocks, it used to cost more than the tails it hides
+    //  -- 24.3 against 23.5 ms in r02 -- and was kept for small batches only; since r03 the first tier is known to run no faster with more than
+    //  sixteen of its waves on a CU (DESIGN.md 8.3), the slots the larger tiers take cost it nothing, and side by side is 15.5 against 18.6 ms)
+    const bool side_by_side = T[0].usable && !kn.serial_tiers && n_work;
+    unsigned long long routed[4] = {0, 0, 0, 0}, done[4] = {0, 0, 0, 0}, cnts[4] = {0, 0, 0, 0};
+    int used_aux = 0;
+    if (side_by_side) {
+        { int rc = ec_route(ctx, e, n_work, rt, routed, sizeof(routed)); if (rc) return rc; }
+        { int rc = ec_fork_side_streams(ctx, e); if (rc) return rc; }
+        for (int tier = LAST - 1; tier >= 1; --tier) {               // longest first.  A wave takes ONE long block at a time, so every routed block may have its own
+            if (!T[tier].usable || !routed[tier]) continue;          // wave from the start (r04: 308 long blocks of the config-1 surrogate on 128 waves were 2.5 s)
+            hipStream_t st = e->aux[used_aux];
+            CK(hipStreamWaitEvent(st, e->fork_ev, 0));
+            { int rc = launch(tier, list[tier], routed[tier], st, true, tier == 1? 2 * (uint64_t) ctx->n_cu : 0); if (rc) return rc; }
+            CK(hipEventRecord(e->aux_ev[used_aux], st));
+            ++used_aux;
+            done[tier] = routed[tier];
+        }
+    }
+    // nothing routed: the first usable tier takes everything
+    const int first_tier = side_by_side || T[0].usable? 0 : next_usable(0);
+    { int rc = launch(first_tier, nullptr, 0, ctx->stream, side_by_side); if (rc) return rc; }
+    // 2. what a tier left over (frames or paths outgrew its carve-up; or, with nothing routed, everything too long) goes round again.  The first round starts as
+    //    soon as the FIRST tier is done -- its left-overs are the deep searches, the longest chains of dependent steps of the batch, and they should not wait
+    //    for the long blocks on the side streams --, later rounds when everything launched so far is done, until a round leaves nothing over.
+    bool waited_aux = used_aux == 0;
+    for (int round = 0; ; ++round) {
+        CK(hipMemcpyAsync(cnts, cur, sizeof(cnts), hipMemcpyDeviceToHost, ctx->stream));
+        CK(hipStreamSynchronize(ctx->stream));
+        if (round == 0) n_big = cnts[1] + cnts[2] + routed[3];   // blocks the first tier did not finish: routed past it, or left over by it
+        bool any = false;
+        for (int tier = first_tier + 1; tier <= LAST; ++tier) {
+            if (!T[tier].usable || cnts[tier] <= done[tier]) continue;
+            { int rc = launch(tier, list[tier] + done[tier], cnts[tier] - done[tier], ctx->stream, false); if (rc) return rc; }
+            done[tier] = cnts[tier];
+            any = true;
+        }
+        if (!any && waited_aux) break;
+        if (!waited_aux) { for (int i = 0; i < used_aux; ++i) CK(hipStreamWaitEvent(ctx->stream, e->aux_ev[i], 0)); waited_aux = true; }
+    }
+    return OATK_OK;
+}
+
+}  // namespace oatk
 
 // the rest of read_error_correction (syncerr.c:819): blocks, search, corrected chains, refreshed table
 extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
@@ -807,570 +1273,29 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     t_end(ctx, OATK_T_EC_MARK);
     t_begin(ctx, OATK_T_EC_SOLVE);
 
-    // ---- solve: one wave per block (ec_wave.hpp).  Tiers: small LDS carve-up for every block, a large one for the blocks that
-    //      did not fit, HBM slabs for the rest. ----
+    // ---- solve ----
+    // Which solver (r06).  A search is a walk when no vertex of the live graph has two arcs out: one candidate per level, as many levels as the block is long -- nothing
+    // to bound.  Round 4's tiers do such a batch 1.2 - 2.5 ms faster at config 3 (14.7 against 15.9 - 17.3 ms; tools/solverbench.py, DESIGN.md 7): there every search
+    // is one, the light graph of a random genome at 30 x has 15 350 arcs and not one vertex with two (tools/graph_branching.py).  With a single branching vertex the
+    // classes with budgets and the second stage run: the config-1 surrogate has 304, and its searches are what they were built for (0.23 s against 3.2).
+    const bool heavy = kn.heavy < 0? graph_branches : kn.heavy != 0;
     uint64_t pool_cap = 2 * nocc + (uint64_t) 16384 * ECW_POOL_CHUNK + 4096;
     EENSURE(cursor, 512); EENSURE(stats, 16 * 8);
     uint64_t n_big = 0;
-    uint32_t max_hl_cache = 0;
+    uint32_t max_hl = 0;                 // the longest read of the batch, once the slab tier has needed it
     for (;;) {
         EENSURE(path_pool, pool_cap * 8);
         CK(hipMemsetAsync(e->cursor.p, 0, 512, ctx->stream));
-        unsigned long long *cur = (unsigned long long *) e->cursor.p;       // [0] pool, then the lists' and queues' counters (below)
-        EcwArgs sa;
-        sa.lv = lv, sa.rd = rd, sa.work = e->work.as<EcWork>(), sa.n_work = n_work, sa.todo = nullptr, sa.n_todo = 0, sa.max_edist = max_edist;
-        sa.out = e->out.as<EcBlockOut>(), sa.path_pool = e->path_pool.as<uint64_t>(), sa.pool_cap = pool_cap;
-        sa.pool_cursor = cur, sa.slabs = nullptr, sa.slab_bytes = 0, sa.arc_budget = 0;
-#ifdef ECW_PROF
-        static unsigned long long *d_prof = nullptr;
-        if (!d_prof) CK(hipMalloc(&d_prof, 32 * 8));
-#endif
-        // ---- round 5: everything that is not small goes to a WORKGROUP per block (ec_heavy.hpp); OATK_DEBUG_EC_HEAVY=0: the tiers of round 4 (A/B, tests) ----
-        // Which solver (r06).  A search is a walk when no vertex of the live graph has two arcs out: one candidate per level, as many levels as the block is long -- nothing
-        // to bound.  Round 4's tiers do such a batch 1.2 - 2.5 ms faster at config 3 (14.7 against 15.9 - 17.3 ms; tools/solverbench.py, DESIGN.md 7): there every search
-        // is one, the light graph of a random genome at 30 x has 15 350 arcs and not one vertex with two (tools/graph_branching.py).  With a single branching vertex the
-        // classes with budgets and the second stage run: the config-1 surrogate has 304, and its searches are what they were built for (0.23 s against 3.2).
-        const bool heavy = kn.heavy < 0? graph_branches : kn.heavy != 0;
+        EcwArgs base = {};               // what every launch shares; each sets the rest of its own
+        base.lv = lv, base.rd = rd, base.work = e->work.as<EcWork>(), base.n_work = n_work, base.max_edist = max_edist;
+        base.out = e->out.as<EcBlockOut>(), base.path_pool = e->path_pool.as<uint64_t>(), base.pool_cap = pool_cap;
+        base.pool_cursor = (unsigned long long *) e->cursor.p;       // [0] pool, then the lists' and work queues' counters; [63] blocks that outgrew the slabs
         if (kn.stages) fprintf(stderr, "[ec stages] the live graph %s: %s\n", graph_branches? "branches" : "does not branch", heavy? "classes with budgets, second stage" : "round 4's tiers");
-        if (heavy) {
-            // classes by block length: the first tier of ec_wave.hpp (a wave per block, everything in LDS) for the millions of small blocks; three carve-ups of
-            // the workgroup solver (R = 1, 2, 6 diagonals per lane: 2 bw + 3 <= 256 R); HBM slabs (one wave, ec_wave_kernel<1>) for whatever is left
-            const int32_t t_lo = ctx->ec_cap_t0 > 0? ctx->ec_cap_t0 : kn.cap_t0;
-            struct HTier { int32_t cap_t, cap_c, cap_path, cap_fl, cap_fh, R; uint64_t lds, slab; bool usable, routes; } H[4];
-            // Two stages.  The classes run with a BUDGET of wavefront steps: nearly every block is done within a few dozen (config 3: 258 k blocks past the first tier).  A
-            // block that goes past the budget is a search inside a repeat -- a million steps on hundreds of diagonals -- and starts again in the second stage, below.
-            // OATK_DEBUG_EC_FUSED=0: no budget, no second stage (r05b: A/B, tests); OATK_DEBUG_EC_STEP_BUDGET: the budget (tests: 1 sends everything on).
-            // (A solver that shares a block's search TREE among eight waves was built in round 5, is exact and 2 - 8 x slower on repeats: tools/experiments/ec_tree.hpp.)
-            const bool use_fused = kn.fused;
-            const int32_t step_budget = use_fused? kn.step_budget : 0;
-            // (first stage, classes 1 and 2: ONE wave per block with the wavefront in 4 / 8 registers per lane -- ec_heavy.hpp with NW = 1: no barrier at all, fifteen blocks
-            //  a CU; what needs four waves on a wavefront is a search past the budget, and that goes to the second stage.  OATK_DEBUG_EC_FUSED=0: four waves, r05b)
-            const bool one_wave = use_fused;
-            const int hr[4] = {0, one_wave? 4 : 1, one_wave? 8 : 2, 6};
-            for (int c = 1; c <= 3; ++c) {
-                HTier &h = H[c];
-                h.R = hr[c];
-                // the longest block whose band fits the class's registers: bw = max(6, ceil(l * max_edist)), 2 bw + 3 <= 256 R (64 R for a single wave)
-                const bool single = one_wave && c < 3;
-                const int32_t bwmax = ((single? 64 : 256) * h.R - 3) / 2;
-                int64_t ct = max_edist > 0? (int64_t) floor((double) bwmax / max_edist) : 0x3FFFFFFF;
-                while (ct > 0 && (int32_t) ceil((double) ct * max_edist) > bwmax) --ct;
-                if (ct > 60000) ct = 60000;
-                if (c == 1 && ctx->ec_cap_t1 > 0 && ctx->ec_cap_t1 < ct) ct = ctx->ec_cap_t1;      // (test hooks: push blocks into the larger classes)
-                if (c == 2 && kn.heavy_cap2 > H[1].cap_t && kn.heavy_cap2 < ct) ct = kn.heavy_cap2;
-                h.cap_t = (int32_t) ct;
-                h.cap_c = h.cap_t + h.cap_t / 8 + 2 * ctx->K + 64;
-                h.cap_path = h.cap_c;                                  // every arc appends at least one base
-                h.cap_fl = single? 4096 : (c == 1? 16384 : (c == 2? 24576 : 32768)), h.cap_fh = single? 128 << 10 : 1 << 20;        // (thousands of single waves: a megabyte of HBM frames each would be gigabytes; what outgrows 128 KB is a heavy search and goes on anyway)
-                if (kn.heavy_fl) h.cap_fl = kn.heavy_fl;
-                h.lds = (uint64_t) ech_lds_words(h.cap_t, h.cap_c, h.cap_fl, h.R) * 4;
-                h.slab = ech_slab_bytes(h.cap_c, h.cap_path, h.cap_fh);
-                h.usable = h.lds <= 64 * 1024;
-                h.routes = h.usable && (c == 1 || h.cap_t > H[c - 1].cap_t);      // (a class that takes no longer blocks than the one before it only takes that one's left-overs)
-            }
-            // tier 0 and the slab tier as in round 4
-            struct Tier0 { int32_t cap_t, cap_c, cap_w, cap_path, cap_f; uint64_t bytes; bool usable; int wpb; } T0, TB;
-            T0.cap_t = t_lo, T0.cap_path = 32, T0.cap_f = 2048;
-            if (kn.capf) T0.cap_f = kn.capf;
-            if (kn.capp) T0.cap_path = kn.capp;
-            T0.cap_w = 2 * ((int32_t) (T0.cap_t * max_edist) + 1 > EC_MIN_ERR_BASE? (int32_t) (T0.cap_t * max_edist) + 1 : EC_MIN_ERR_BASE) + 12;
-            T0.cap_c = T0.cap_t + T0.cap_t / 8 + 2 * ctx->K + 64;
-            T0.bytes = (uint64_t) ecw_scratch_words(T0.cap_t, T0.cap_c, T0.cap_w, T0.cap_path, T0.cap_f, false) * 4;
-            T0.usable = T0.bytes <= 64 * 1024 && H[1].usable && T0.cap_t <= H[1].cap_t;
-            T0.wpb = ECW_WPB * T0.bytes <= 64 * 1024? ECW_WPB : 1;
-            TB.cap_t = 0;
-            uint64_t t0_waves = 0;
-            if (T0.usable) {
-                uint64_t wg_cu = 160 * 1024 / ((uint64_t) T0.wpb * T0.bytes + 256);
-                if (wg_cu > 16) wg_cu = 16;
-                uint64_t per_cu = wg_cu * (uint64_t) T0.wpb;
-                const uint64_t cap = (uint64_t) kn.waves;
-                if (per_cu > cap) per_cu = cap / (uint64_t) T0.wpb * (uint64_t) T0.wpb;
-                t0_waves = (uint64_t) ctx->n_cu * (per_cu? per_cu : (uint64_t) T0.wpb);
-            }
-            const uint64_t os_words0 = ((uint64_t) ecw_words(T0.cap_c) + 15) & ~15ULL;
-            EENSURE(os_slabs, (t0_waves + ECW_WPB) * os_words0 * 4 + 64);
-            // lists 1 .. 3: the classes' blocks (routed there by length, or left over by the first tier); list 4: what the workgroup solver gave up on
-            EENSURE(todo, 4 * (n_work + 1) * 4); EENSURE(todo2, (n_work + 1) * 4);
-            uint32_t *list[5] = {nullptr, e->todo.as<uint32_t>(), e->todo.as<uint32_t>() + (n_work + 1), e->todo.as<uint32_t>() + 2 * (n_work + 1), e->todo.as<uint32_t>() + 3 * (n_work + 1)};
-            // counters: [0] pool, [1 .. 4] entries of list[c], [5 ...] one work queue per launch, [63] blocks that outgrew the slabs
-            int qslot = 5, hyb_k = 0;
-            auto launch_heavy = [&](int c, const uint32_t *todo, uint64_t n_todo, hipStream_t st) -> int {
-                if (!n_todo) return OATK_OK;
-                const HTier &h = H[c];
-                EcwArgs ha = sa;
-                ha.cap_t = h.cap_t, ha.cap_c = h.cap_c, ha.cap_w = step_budget, ha.cap_path = h.cap_path, ha.cap_f = h.cap_fl, ha.os_words = (uint64_t) h.cap_fh;
-                ha.todo = todo, ha.n_todo = n_todo, ha.next = cur + qslot++, ha.skip_l = 0x7FFFFFFF, ha.batch = 1;
-                ha.todo_out = list[4], ha.todo_cnt = cur + 4;
-                uint64_t wgs = (uint64_t) ctx->n_cu * 8;
-                if (one_wave && c < 3) { uint64_t per_cu = 160 * 1024 / (h.lds + 256); if (per_cu > 16) per_cu = 16; if (per_cu < 1) per_cu = 1; wgs = (uint64_t) ctx->n_cu * per_cu; }
-                if (kn.heavy_wgs) wgs = (uint64_t) kn.heavy_wgs;
-                if (wgs > n_todo) wgs = n_todo;
-                while (wgs > (uint64_t) ctx->n_cu && wgs * h.slab > (3ULL << 30)) wgs -= (uint64_t) ctx->n_cu;          // (no launch holds more than three gigabytes of slabs: several handles share a device)
-                if (hyb_k >= 16 || qslot >= 60) { ctx->err = "EC solver: more launches of the workgroup solver than slab buffers (internal)"; return OATK_E_STATE; }
-                DevBuf &hb = e->hyb_slabs[hyb_k++];
-                if (!hb.ensure(wgs * h.slab + 64, st)) { ctx->err = "hipMalloc failed for the workgroup solver's slabs"; return OATK_E_NOMEM; }
-                ha.slabs = (uint8_t *) hb.p, ha.slab_bytes = h.slab;
-                if (one_wave && c == 1) hipLaunchKernelGGL((ec_heavy_kernel<1, 4>), dim3((unsigned) wgs), dim3(64), (unsigned) h.lds, st, ha);
-                else if (one_wave && c == 2) hipLaunchKernelGGL((ec_heavy_kernel<1, 8>), dim3((unsigned) wgs), dim3(64), (unsigned) h.lds, st, ha);
-                else if (h.R == 1) hipLaunchKernelGGL((ec_heavy_kernel<ECH_NW, 1>), dim3((unsigned) wgs), dim3(64 * ECH_NW), (unsigned) h.lds, st, ha);
-                else if (h.R == 2) hipLaunchKernelGGL((ec_heavy_kernel<ECH_NW, 2>), dim3((unsigned) wgs), dim3(64 * ECH_NW), (unsigned) h.lds, st, ha);
-                else hipLaunchKernelGGL((ec_heavy_kernel<ECH_NW, 6>), dim3((unsigned) wgs), dim3(64 * ECH_NW), (unsigned) h.lds, st, ha);
-                return OATK_OK;
-            };
-            // 1. route by length, the classes of long blocks on streams of their own (longest first: they are the longest chains of dependent steps), the first tier beside them
-            EcRoute rt;
-            for (int c = 0; c < 4; ++c) rt.list[c] = list[c], rt.cnt[c] = cur + c;
-            rt.cap[0] = T0.usable? T0.cap_t : 0;
-            rt.cap[1] = H[1].routes? H[1].cap_t : 0, rt.cap[2] = H[2].routes? H[2].cap_t : 0, rt.cap[3] = 0x7FFFFFFF;
-            unsigned long long routed[5] = {0, 0, 0, 0, 0}, cnts[5] = {0, 0, 0, 0, 0};
-            if (n_work) {
-                hipLaunchKernelGGL(ec_route_kernel, dim3((unsigned) ((n_work + 256 * ECW_ROUTE_ITEMS - 1) / (256 * ECW_ROUTE_ITEMS))), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), n_work, rt);
-                CK(hipMemcpyAsync(routed, cur, sizeof(routed), hipMemcpyDeviceToHost, ctx->stream));
-                CK(hipStreamSynchronize(ctx->stream));
-            }
-            if (!e->aux[0]) {
-                // (Streams share the runtime's hardware queues -- four per priority level by default, handed out by use count -- and two launches on one queue run one AFTER
-                //  the other: with the reads' uploader, the handle's own stream and a host program's streams about, the second stage's four classes were seen running
-                //  8 waves, then 4 waves (rocprofv3 kernel trace, round 6).  The solver's side streams are the only ones of their priority level, so they get queues of their own.)
-                int pr_least = 0, pr_greatest = 0;
-                CK(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
-                for (int i = 0; i < 5; ++i) { CK(hipStreamCreateWithPriority(&e->aux[i], hipStreamNonBlocking, i < 4? pr_greatest : pr_least)); CK(hipEventCreateWithFlags(&e->aux_ev[i], hipEventDisableTiming)); }
-                CK(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
-            }
-            CK(hipEventRecord(e->fork_ev, ctx->stream));
-            int used_aux = 0;
-            {   // (room to sort a class's list, see below)
-                unsigned long long mx = routed[1] > routed[2]? routed[1] : routed[2];
-                mx = routed[3] > mx? routed[3] : mx;
-                if (mx <= (4u << 20) && 3 * (mx + 1) > n_work + 1) EENSURE(todo2, 3 * (mx + 1) * 4);
-            }
-            for (int c = 3; c >= 1; --c) {
-                if (!routed[c]) continue;
-                if (!H[c].usable) { ctx->err = "EC solver: a class of the workgroup solver does not fit LDS (K too large)"; return OATK_E_STATE; }
-                if (routed[c] > 1 && routed[c] <= (64u << 10)) {
-                    // longest first: a block's length is what the host can tell of its search, and the longest search of the batch (0.6 s on the config-1 surrogate) must not
-                    // start when the others are done.  The lists are small (thousands of blocks): a radix sort on ~length.
-                    uint32_t *k_in = e->todo2.as<uint32_t>(), *k_out = k_in + (routed[c] + 1), *v_out = k_out + (routed[c] + 1);
-                    hipLaunchKernelGGL(ec_route_keys_kernel, dim3((unsigned) ((routed[c] + 255) / 256)), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), list[c], routed[c], k_in);
-                    size_t tb = 0;
-                    CK(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, list[c], v_out, routed[c], 0, 32, ctx->stream));
-                    ENSURE(tmp, tb);
-                    CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, k_in, k_out, list[c], v_out, routed[c], 0, 32, ctx->stream));
-                    CK(hipMemcpyAsync(list[c], v_out, routed[c] * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                    CK(hipEventRecord(e->fork_ev, ctx->stream));
-                }
-                hipStream_t st = e->aux[used_aux];
-                CK(hipStreamWaitEvent(st, e->fork_ev, 0));
-                { int rc = launch_heavy(c, list[c], routed[c], st); if (rc) return rc; }
-                CK(hipEventRecord(e->aux_ev[used_aux], st));
-                ++used_aux;
-            }
-            if (T0.usable && n_work) {
-                sa.cap_t = T0.cap_t, sa.cap_c = T0.cap_c, sa.cap_w = T0.cap_w, sa.cap_path = T0.cap_path, sa.cap_f = T0.cap_f;
-                sa.todo = nullptr, sa.n_todo = 0, sa.next = cur + qslot++, sa.skip_l = T0.cap_t, sa.batch = ECW_BATCH;
-                // (a small block inside a repeat tries tens of thousands of arcs on a handful of diagonals -- 70 ms of ONE wave on the config-1 surrogate with everything else waiting
-                //  for this launch: past 2048 arcs it is left to the classes and, past their step budget, to the second stage)
-                if (use_fused) sa.arc_budget = kn.arc_budget;
-                sa.todo_out = list[1], sa.todo_cnt = cur + 1;        // what outgrows the first tier's frames or paths is short: the first class takes it
-                sa.os_words = os_words0, sa.os_slabs = e->os_slabs.as<uint32_t>();
-                uint64_t waves = t0_waves;
-                const uint64_t groups = (n_work + (uint64_t) sa.batch - 1) / (uint64_t) sa.batch;
-                if (waves > groups) waves = groups;
-                if (T0.wpb > 1) hipLaunchKernelGGL((ec_wave_kernel<0, ECW_WPB>), dim3((unsigned) ((waves + ECW_WPB - 1) / ECW_WPB)), dim3(64 * ECW_WPB), (unsigned) (ECW_WPB * T0.bytes), ctx->stream, sa);
-                else hipLaunchKernelGGL((ec_wave_kernel<0, 1>), dim3((unsigned) waves), dim3(64), (unsigned) T0.bytes, ctx->stream, sa);
-            }
-            // 2. the first tier's left-overs (deep searches: the longest chains of the batch) as soon as it is done; then everything launched so far; then the slabs
-            CK(hipMemcpyAsync(cnts, cur, sizeof(cnts), hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-            if (cnts[1] > routed[1]) { int rc = launch_heavy(1, list[1] + routed[1], cnts[1] - routed[1], ctx->stream); if (rc) return rc; }
-            n_big = cnts[1] + routed[2] + routed[3];
-            for (int i = 0; i < used_aux; ++i) CK(hipStreamWaitEvent(ctx->stream, e->aux_ev[i], 0));
-            CK(hipMemcpyAsync(cnts, cur, sizeof(cnts), hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-            if (cnts[2] > routed[2]) {                                 // the tree solver's left-overs
-                int rc = launch_heavy(2, list[2] + routed[2], cnts[2] - routed[2], ctx->stream); if (rc) return rc;
-                CK(hipMemcpyAsync(cnts, cur, sizeof(cnts), hipMemcpyDeviceToHost, ctx->stream));
-                CK(hipStreamSynchronize(ctx->stream));
-            }
-            uint32_t *slab_list = list[4];
-            unsigned long long slab_n = cnts[4];
-            const bool dbg_stages = kn.stages;
-            struct timespec ts0, ts1;
-            if (dbg_stages) { clock_gettime(CLOCK_MONOTONIC, &ts0); fprintf(stderr, "[ec stages] first stage done: %llu blocks go on (classes got %llu + %llu + %llu)\n", cnts[4], cnts[1], routed[2], routed[3]); }
-            if (use_fused && cnts[4]) {
-                // ---- second stage: what went past the step budget (or outgrew a class), several steps per barrier, longest first ----
-                const uint64_t nh = cnts[4];
-                if (nh > 1 && nh <= (4u << 20)) {
-                    if (3 * (nh + 1) > n_work + 1) EENSURE(todo2, 3 * (nh + 1) * 4);
-                    uint32_t *k_in = e->todo2.as<uint32_t>(), *k_out = k_in + (nh + 1), *v_out = k_out + (nh + 1);
-                    hipLaunchKernelGGL(ec_route_keys_kernel, dim3((unsigned) ((nh + 255) / 256)), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), list[4], nh, k_in);
-                    size_t tb = 0;
-                    CK(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, list[4], v_out, nh, 0, 32, ctx->stream));
-                    ENSURE(tmp, tb);
-                    CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, k_in, k_out, list[4], v_out, nh, 0, 32, ctx->stream));
-                    CK(hipMemcpyAsync(list[4], v_out, nh * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                }
-                // A wave owns 56 slots of the wavefront (ec_fused.hpp), a block needs 2 bw + 3: classes of 16, 8, 4 and 2 waves -- the fewer waves meet, the cheaper the meeting, the
-                // fewer copies of the search's scalar bookkeeping run (every wave of a block executes all of it: 276 scalar + 150 vector instructions per arc and wave on the
-                // config-1 surrogate, profiles/r06b_config1s_pmc_ec.csv -- the second stage is bound by instruction issue while every CU is full) and the more blocks a CU holds.
-                // In a list sorted longest first the classes are consecutive stretches.  All launches run side by side; what outgrows one (frames, paths) goes to the slabs.
-                auto fused_caps = [&](int NW, EcwArgs &fa) -> uint64_t {
-                    const int32_t bwmax = (NW * ECF_OWN - 3) / 2;
-                    int64_t ct = max_edist > 0? (int64_t) floor((double) bwmax / max_edist) : 0x3FFFFFFF;
-                    while (ct > 0 && (int32_t) ceil((double) ct * max_edist) > bwmax) --ct;
-                    if (ct > 60000) ct = 60000;
-                    fa = sa;
-                    fa.cap_t = (int32_t) ct, fa.cap_c = fa.cap_t + fa.cap_t / 8 + 2 * ctx->K + 64, fa.cap_w = 0, fa.cap_path = fa.cap_c;
-                    fa.cap_f = NW >= 16? 32768 : (NW == 8? 24576 : (NW == 4? 16384 : 12288));
-                    if (kn.heavy_fl) fa.cap_f = kn.heavy_fl;
-                    fa.os_words = 1 << 20;
-                    return (uint64_t) ecf_lds_words(fa.cap_t, fa.cap_c, fa.cap_f, NW) * 4;
-                };
-                // The narrowest bands (2 bw + 3 <= 64: blocks of up to 1500 bases) take ONE wave each, the wavefront a diagonal per lane in registers, no barrier anywhere
-                // (ec_heavy.hpp with NW = 1, the first stage's engine without its budget): such a block's search is arcs, not steps -- 0.9 steps per arc on four diagonals on the
-                // config-1 surrogate, a long arc that dies costs its thirty steps at most -- and two waves that meet at four barriers per arc took 3 us per arc where the first
-                // tier's single wave took 1.75.  (Wider bands on one wave, two diagonals per lane, were tried: 78 s of wave time against 104, but their long dying arcs are not
-                // asked by table there and the longest block took 451 ms against 209.)  OATK_DEBUG_EC_FUSED_MIN_NW=2: no such class (A/B, tests); =8: the two classes of round 5.
-                const int NCLS = 5;
-                int NWS[NCLS] = {16, 8, 4, 2, 1};
-                EcwArgs fa[NCLS];
-                uint64_t lds[NCLS];
-                int narrowest = NCLS - 1;
-                if (kn.min_nw >= 2) narrowest = kn.min_nw >= 16? 0 : (kn.min_nw >= 8? 1 : (kn.min_nw >= 4? 2 : 3));
-                auto single_caps = [&](EcwArgs &fa) -> uint64_t {
-                    const int R = 1;
-                    const int32_t bwmax = (64 * R - 3) / 2;
-                    int64_t ct = max_edist > 0? (int64_t) floor((double) bwmax / max_edist) : 0x3FFFFFFF;
-                    while (ct > 0 && (int32_t) ceil((double) ct * max_edist) > bwmax) --ct;
-                    if (ct > 60000) ct = 60000;
-                    fa = sa;
-                    fa.cap_t = (int32_t) ct, fa.cap_c = fa.cap_t + fa.cap_t / 8 + 2 * ctx->K + 64, fa.cap_w = 0, fa.cap_path = fa.cap_c, fa.cap_f = 8192;
-                    if (kn.heavy_fl) fa.cap_f = kn.heavy_fl;
-                    fa.os_words = 1 << 20;
-                    return (uint64_t) ech_lds_words(fa.cap_t, fa.cap_c, fa.cap_f, R) * 4;
-                };
-                for (int i = 0; i < NCLS; ++i) lds[i] = NWS[i] == 1? single_caps(fa[i]) : fused_caps(NWS[i], fa[i]);
-                while (narrowest > 0 && lds[narrowest] > 64 * 1024) --narrowest;
-                // longer[i] = blocks too long for class i + 1 (the head of the sorted list): class i takes list[4][longer[i - 1] .. longer[i])
-                unsigned long long longer[NCLS] = {0, 0, 0, 0, 0};
-                CK(hipMemsetAsync(cur + 1, 0, 40, ctx->stream));                  // [1] what is left over, [2 .. 5] the counts
-                for (int i = 0; i < narrowest; ++i)
-                    hipLaunchKernelGGL(ec_route_longer_kernel, dim3((unsigned) ((nh + 255) / 256)), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), list[4], nh, lds[i + 1] <= 64 * 1024? fa[i + 1].cap_t : -1, cur + 2 + i);
-                CK(hipMemcpyAsync(longer, cur + 2, 32, hipMemcpyDeviceToHost, ctx->stream));
-                CK(hipStreamSynchronize(ctx->stream));
-                if (nh > (4u << 20)) longer[0] = nh;                               // (unsorted: sixteen waves for all)
-                longer[narrowest] = nh;
-                for (int i = 1; i <= narrowest; ++i) if (longer[i] < longer[i - 1]) longer[i] = longer[i - 1];
-                const bool use_cert = kn.cert;      // (the table test for long arcs, ec_fused.hpp CERT: on since round 6; =0: without)
-                auto launch_fused = [&](int NW, EcwArgs &fa, uint64_t lds, const uint32_t *todo, uint64_t n_todo, hipStream_t st) -> int {
-                    if (!n_todo) return OATK_OK;
-                    if (lds > 64 * 1024) { ctx->err = "EC solver: the second stage's carve-up does not fit LDS (K too large)"; return OATK_E_STATE; }
-                    fa.todo = todo, fa.n_todo = n_todo, fa.next = cur + qslot++, fa.skip_l = 0x7FFFFFFF, fa.batch = 1, fa.arc_budget = 0;
-                    fa.todo_out = list[1], fa.todo_cnt = cur + 1;
-                    if (NW == 1) {                                             // one wave per block, no budget (ec_heavy.hpp)
-                        uint64_t per_cu = 160 * 1024 / (lds + 256);
-                        if (per_cu > 16) per_cu = 16;
-                        uint64_t wgs = (uint64_t) ctx->n_cu * (per_cu? per_cu : 1);
-                        if (wgs > n_todo) wgs = n_todo;
-                        if (hyb_k >= 16 || qslot >= 60) { ctx->err = "EC solver: more launches of the workgroup solver than slab buffers (internal)"; return OATK_E_STATE; }
-                        DevBuf &hb = e->hyb_slabs[hyb_k++];
-                        fa.slab_bytes = ech_slab_bytes(fa.cap_c, fa.cap_path, (int32_t) fa.os_words);
-                        if (!hb.ensure(wgs * fa.slab_bytes + 64, st)) { ctx->err = "hipMalloc failed for the workgroup solver's slabs"; return OATK_E_NOMEM; }
-                        fa.slabs = (uint8_t *) hb.p;
-                        hipLaunchKernelGGL((ec_heavy_kernel<1, 1>), dim3((unsigned) wgs), dim3(64), (unsigned) lds, st, fa);
-                        if (dbg_stages) fprintf(stderr, "[ec stages] one wave: %llu blocks on %llu waves (%llu B of LDS, slabs %.1f MB)\n", (unsigned long long) n_todo, (unsigned long long) wgs, (unsigned long long) lds, wgs * fa.slab_bytes / 1e6);
-                        return OATK_OK;
-                    }
-                    uint64_t per_cu = 2048 / (64 * (uint64_t) NW), by_lds = 160 * 1024 / (lds + 512);
-                    if (per_cu > by_lds) per_cu = by_lds;
-                    if (per_cu > 16) per_cu = 16;
-                    uint64_t wgs = (uint64_t) ctx->n_cu * (per_cu? per_cu : 1);
-                    if (wgs > n_todo) wgs = n_todo;
-                    if (hyb_k >= 16 || qslot >= 60) { ctx->err = "EC solver: more launches of the workgroup solver than slab buffers (internal)"; return OATK_E_STATE; }
-                    DevBuf &hb = e->hyb_slabs[hyb_k++];
-                    fa.slab_bytes = ech_slab_bytes(fa.cap_c, fa.cap_path, (int32_t) fa.os_words);
-                    if (!hb.ensure(wgs * fa.slab_bytes + 64, st)) { ctx->err = "hipMalloc failed for the workgroup solver's slabs"; return OATK_E_NOMEM; }
-                    fa.slabs = (uint8_t *) hb.p;
-                    if (use_cert) {                                            // a region of tables per workgroup
-                        if (hyb_k >= 16) { ctx->err = "EC solver: more launches of the workgroup solver than slab buffers (internal)"; return OATK_E_STATE; }
-                        DevBuf &tb = e->hyb_slabs[hyb_k++];
-                        if (!tb.ensure(wgs * ecf_tab_words(fa.cap_t) * 4 + 64, st)) { ctx->err = "hipMalloc failed for the workgroup solver's tables"; return OATK_E_NOMEM; }
-                        fa.os_slabs = (uint32_t *) tb.p;
-                        if (NW == 2) hipLaunchKernelGGL((ec_fused_kernel<2, true>), dim3((unsigned) wgs), dim3(128), (unsigned) lds, st, fa);
-                        else if (NW == 4) hipLaunchKernelGGL((ec_fused_kernel<4, true>), dim3((unsigned) wgs), dim3(256), (unsigned) lds, st, fa);
-                        else if (NW == 8) hipLaunchKernelGGL((ec_fused_kernel<8, true>), dim3((unsigned) wgs), dim3(512), (unsigned) lds, st, fa);
-                        else hipLaunchKernelGGL((ec_fused_kernel<16, true>), dim3((unsigned) wgs), dim3(1024), (unsigned) lds, st, fa);
-                    } else
-                    if (NW == 2) hipLaunchKernelGGL((ec_fused_kernel<2>), dim3((unsigned) wgs), dim3(128), (unsigned) lds, st, fa);
-                    else if (NW == 4) hipLaunchKernelGGL((ec_fused_kernel<4>), dim3((unsigned) wgs), dim3(256), (unsigned) lds, st, fa);
-                    else if (NW == 8) hipLaunchKernelGGL((ec_fused_kernel<8>), dim3((unsigned) wgs), dim3(512), (unsigned) lds, st, fa);
-                    else hipLaunchKernelGGL((ec_fused_kernel<16>), dim3((unsigned) wgs), dim3(1024), (unsigned) lds, st, fa);
-                    if (dbg_stages) fprintf(stderr, "[ec stages] %d waves: %llu blocks on %llu workgroups (%llu B of LDS, slabs %.1f MB)\n", NW, (unsigned long long) n_todo, (unsigned long long) wgs, (unsigned long long) lds, wgs * fa.slab_bytes / 1e6);
-                    return OATK_OK;
-                };
-                CK(hipEventRecord(e->fork_ev, ctx->stream));
-                int aux_used2 = 0;
-                bool used_low = false;
-                for (int i = 0; i <= narrowest; ++i) {                             // the longest blocks first, each class on a side stream of its own
-                    const uint64_t b0 = i? longer[i - 1] : 0, b1 = longer[i];
-                    if (b1 <= b0) continue;
-                    hipStream_t st = e->aux[NWS[i] == 1? 4 : aux_used2];
-                    const int ev_i = NWS[i] == 1? 4 : aux_used2;
-                    CK(hipStreamWaitEvent(st, e->fork_ev, 0));
-                    { int rc = launch_fused(NWS[i], fa[i], lds[i], list[4] + b0, b1 - b0, st); if (rc) return rc; }
-                    CK(hipEventRecord(e->aux_ev[ev_i], st));
-                    if (ev_i == 4) used_low = true; else ++aux_used2;
-                }
-                if (used_low) CK(hipStreamWaitEvent(ctx->stream, e->aux_ev[4], 0));
-                for (int i = 0; i < aux_used2; ++i) CK(hipStreamWaitEvent(ctx->stream, e->aux_ev[i], 0));
-                unsigned long long left = 0;
-                CK(hipMemcpyAsync(&left, cur + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
-                CK(hipStreamSynchronize(ctx->stream));
-                if (dbg_stages) { clock_gettime(CLOCK_MONOTONIC, &ts1); fprintf(stderr, "[ec stages] second stage %.1f ms; %llu left for the slabs\n", ((double) (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double) (ts1.tv_nsec - ts0.tv_nsec)) * 1e3, left); }
-                const uint32_t *in_list = list[1];
-                unsigned long long in_n = left;
-                slab_list = const_cast<uint32_t *>(in_list), slab_n = in_n;
-            }
-            if (slab_n) {                                              // deeper than a megabyte of frames, or longer than the largest class: one wave per block, every array in an HBM slab
-                if (max_hl_cache == 0) {
-                    std::vector<uint32_t> hl(nr);
-                    CK(hipMemcpy(hl.data(), ctx->hoco_l.p, nr * 4, hipMemcpyDeviceToHost));
-                    for (uint64_t i = 0; i < nr; ++i) if (hl[i] > max_hl_cache) max_hl_cache = hl[i];
-                }
-                TB.cap_t = (int32_t) max_hl_cache + 64;
-                const int32_t bwmax = (int32_t) (max_hl_cache * max_edist) + 16;
-                TB.cap_w = 2 * bwmax + 16, TB.cap_path = (int32_t) max_hl_cache + (int32_t) max_hl_cache / 8 + 2 * ctx->K + 64, TB.cap_f = 1 << 22;
-                TB.cap_c = TB.cap_t + TB.cap_t / 8 + 2 * ctx->K + 64;
-                TB.bytes = (uint64_t) ecw_scratch_words(TB.cap_t, TB.cap_c, TB.cap_w, TB.cap_path, TB.cap_f) * 4;
-                sa.cap_t = TB.cap_t, sa.cap_c = TB.cap_c, sa.cap_w = TB.cap_w, sa.cap_path = TB.cap_path, sa.cap_f = TB.cap_f;
-                sa.todo = slab_list, sa.n_todo = slab_n, sa.next = cur + qslot++, sa.skip_l = 0x7FFFFFFF, sa.batch = 1;
-                sa.todo_out = e->todo2.as<uint32_t>(), sa.todo_cnt = cur + 63;
-                uint64_t waves = 1024;
-                if (waves > slab_n) waves = slab_n;
-                sa.slab_bytes = (TB.bytes + 63) & ~63ULL;
-                EENSURE(big_slabs, waves * sa.slab_bytes);
-                sa.slabs = e->big_slabs.as<uint8_t>();
-                hipLaunchKernelGGL((ec_wave_kernel<1, 1>), dim3((unsigned) waves), dim3(64), 0, ctx->stream, sa);
-            }
-            {   // a block that outgrows the slabs
-                unsigned long long fin = 0;
-                CK(hipMemcpyAsync(&fin, cur + 63, 8, hipMemcpyDeviceToHost, ctx->stream));
-                CK(hipStreamSynchronize(ctx->stream));
-                if (fin) { ctx->err = "error correction: a block outgrew the large scratch slab (DFS deeper than 4 MiB of frames)"; return OATK_E_NOMEM; }
-            }
-            unsigned long long used = 0;
-            CK(hipMemcpyAsync(&used, e->cursor.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-            if (used <= pool_cap) break;
-            pool_cap = used + used / 4 + 4096;          // the pool overflowed: grow it and solve again
-            continue;
-        }
-        const int LAST = 3;                  // tiers 0 .. LAST - 1 carve LDS (more per wave, fewer waves per CU), tier LAST uses HBM slabs
-        const int32_t t_lo = ctx->ec_cap_t0 > 0? ctx->ec_cap_t0 : 3072, t_hi = ctx->ec_cap_t1 > 0? ctx->ec_cap_t1 : 16384;
-        // the carve-up of every tier
-        struct Tier { int32_t cap_t, cap_c, cap_w, cap_path, cap_f; uint64_t bytes; bool usable; int wpb; bool hybrid; uint64_t slab; } T[4];
-        const bool no_hybrid = kn.no_hybrid;                       // (A/B: the last LDS tier as it was until round 3)
-        for (int tier = 0; tier < LAST; ++tier) {
-            Tier &t = T[tier];
-            t.cap_t = tier == 0? t_lo : (tier == LAST - 1? t_hi : (2 * t_lo < t_hi? 2 * t_lo : t_hi));
-            t.cap_path = tier == 0? 32 : (tier == LAST - 1? 256 : 64), t.cap_f = tier == 0? 2048 : (tier == LAST - 1? 12288 : 4096);
-            if (tier == 0) { if (kn.capf) t.cap_f = kn.capf; if (kn.capp) t.cap_path = kn.capp; }
-            t.cap_w = 2 * ((int32_t) (t.cap_t * max_edist) + 1 > EC_MIN_ERR_BASE? (int32_t) (t.cap_t * max_edist) + 1 : EC_MIN_ERR_BASE) + 12;
-            t.cap_c = t.cap_t + t.cap_t / 8 + 2 * ctx->K + 64;
-            t.bytes = (uint64_t) ecw_scratch_words(t.cap_t, t.cap_c, t.cap_w, t.cap_path, t.cap_f, false) * 4;
-            t.hybrid = false, t.slab = 0;
-            if (tier == LAST - 1 && !no_hybrid) {
-                // the last LDS tier keeps only what the alignment reads in LDS; its paths and DFS frames lie in an HBM slab per wave (ec_wave_kernel MODE 2):
-                // a path may be as long as the consensus has bases, and 1 MB holds a few thousand levels that all branch
-                t.hybrid = true;
-                t.cap_path = t.cap_c, t.cap_f = 1 << 20;
-                t.bytes = (uint64_t) ecw_lds_words_hybrid(t.cap_t, t.cap_c, t.cap_w) * 4;
-                t.slab = ecw_slab_bytes_hybrid(t.cap_path, t.cap_f);
-            }
-            t.usable = t.bytes <= 64 * 1024;                        // (a very large K goes straight to the slabs)
-            t.wpb = ECW_WPB * t.bytes <= 64 * 1024? ECW_WPB : 1;    // waves per workgroup, each with its own carve-up
-        }
-        // the LDS tiers' optimum consensus: one slab per wave and launch (a tier is launched at most twice, and tiers run side by side), sized before anything runs
-        // (waves per CU: the hardware places at most 16 workgroups on a CU, so the waves come in workgroups of ECW_WPB that share nothing)
-        auto lds_waves = [&](const Tier &t) -> uint64_t {
-            uint64_t wg_cu = 160 * 1024 / ((uint64_t) t.wpb * t.bytes + 256);
-            if (wg_cu > 16) wg_cu = 16;
-            uint64_t per_cu = wg_cu * (uint64_t) t.wpb;
-            const uint64_t cap = (uint64_t) kn.waves;
-            if (per_cu > cap) per_cu = cap / (uint64_t) t.wpb * (uint64_t) t.wpb;
-            return (uint64_t) ctx->n_cu * (per_cu? per_cu : (uint64_t) t.wpb);
-        };
-        uint64_t os_total = 0, os_next = 0;
-        for (int tier = 0; tier < LAST; ++tier) if (T[tier].usable) os_total += 3 * (lds_waves(T[tier]) + ECW_WPB) * (((uint64_t) ecw_words(T[tier].cap_c) + 15) & ~15ULL);
-        EENSURE(os_slabs, os_total * 4 + 64);
-        int hyb_k = 0;                                             // launches of the hybrid tier so far in this call
-        T[LAST].usable = true, T[LAST].cap_t = 0;                  // sized when (if) a block gets there: it takes the longest read of the batch
-        auto size_last_tier = [&]() -> int {
-            Tier &t = T[LAST];
-            if (t.cap_t) return OATK_OK;
-            if (max_hl_cache == 0) {
-                std::vector<uint32_t> hl(nr);
-                CK(hipMemcpy(hl.data(), ctx->hoco_l.p, nr * 4, hipMemcpyDeviceToHost));
-                for (uint64_t i = 0; i < nr; ++i) if (hl[i] > max_hl_cache) max_hl_cache = hl[i];
-            }
-            t.cap_t = (int32_t) max_hl_cache + 64;
-            const int32_t bwmax = (int32_t) (max_hl_cache * max_edist) + 16;
-            t.cap_w = 2 * bwmax + 16, t.cap_path = (int32_t) max_hl_cache + (int32_t) max_hl_cache / 8 + 2 * ctx->K + 64, t.cap_f = 1 << 22;
-            t.cap_c = t.cap_t + t.cap_t / 8 + 2 * ctx->K + 64;
-            t.bytes = (uint64_t) ecw_scratch_words(t.cap_t, t.cap_c, t.cap_w, t.cap_path, t.cap_f) * 4;
-            return OATK_OK;
-        };
-        // lists: list[t] collects the blocks tier t must run -- routed there by length before anything runs, or left over by a smaller tier
-        EENSURE(todo, 3 * (n_work + 1) * 4); EENSURE(todo2, (n_work + 1) * 4);
-        uint32_t *list[4] = {nullptr, e->todo.as<uint32_t>(), e->todo.as<uint32_t>() + (n_work + 1), e->todo.as<uint32_t>() + 2 * (n_work + 1)};
-        // counters: [0] pool, [1 .. 3] entries of list[t], [4 .. 7] work queue of tier t's first launch, [8 .. 11] of its second
-        auto next_usable = [&](int t) { int u = t + 1; while (u < LAST && !T[u].usable) ++u; return u; };
-        auto launch = [&](int tier, const uint32_t *todo, uint64_t n_todo, hipStream_t st, unsigned long long *queue, bool routed, uint64_t max_waves = 0) -> int {
-            if (tier == LAST) { int rc = size_last_tier(); if (rc) return rc; }
-            const Tier &t = T[tier];
-            sa.cap_t = t.cap_t, sa.cap_c = t.cap_c, sa.cap_w = t.cap_w, sa.cap_path = t.cap_path, sa.cap_f = t.cap_f;
-            sa.todo = todo, sa.n_todo = n_todo, sa.next = queue;
-            sa.skip_l = routed && tier == 0? t.cap_t : 0x7FFFFFFF;
-            // a block outgrows an LDS tier by the depth of its search or by its frames (its length was checked before): the tier without such limits takes it
-            int nx = next_usable(tier);
-            if (tier < LAST - 1 && T[LAST - 1].usable && T[LAST - 1].hybrid) nx = LAST - 1;
-            sa.todo_out = nx <= LAST? list[nx] : list[LAST], sa.todo_cnt = cur + (nx <= LAST? nx : LAST);
-            if (tier == LAST) sa.todo_out = e->todo2.as<uint32_t>(), sa.todo_cnt = cur + 63;        // (what outgrows the slabs is only counted: the call fails)
-            const uint64_t n_items = todo? n_todo : n_work;
-            uint64_t waves;
-            if (tier < LAST) {
-                waves = lds_waves(t);
-                sa.os_words = ((uint64_t) ecw_words(t.cap_c) + 15) & ~15ULL;
-                if ((os_next + waves * sa.os_words) * 4 > e->os_slabs.cap) { ctx->err = "EC solver: more launches than optimum-consensus slabs (internal)"; return OATK_E_STATE; }
-                sa.os_slabs = e->os_slabs.as<uint32_t>() + os_next;
-                os_next += waves * sa.os_words;
-            } else {
-                waves = 1024;
-                sa.slab_bytes = (t.bytes + 63) & ~63ULL;
-            }
-            sa.batch = tier == 0? ECW_BATCH : 1;                   // (241 long blocks in batches of sixteen were sixteen waves' work: r04e)
-            const uint64_t groups = (n_items + (uint64_t) sa.batch - 1) / (uint64_t) sa.batch;
-            if (waves > groups) waves = groups;
-            if (max_waves && waves > max_waves) waves = max_waves;
-            if (!waves) return OATK_OK;
-            if (tier == LAST) { EENSURE(big_slabs, waves * sa.slab_bytes); sa.slabs = e->big_slabs.as<uint8_t>(); }
-            if (tier < LAST && t.hybrid) {
-                sa.slab_bytes = t.slab;
-                if (hyb_k >= 16) { ctx->err = "EC solver: more launches of the hybrid tier than slab buffers (internal)"; return OATK_E_STATE; }
-                DevBuf &hb = e->hyb_slabs[hyb_k++];
-                if (!hb.ensure((waves + ECW_WPB) * t.slab + 64, st)) { ctx->err = "hipMalloc failed for the hybrid tier's slabs"; return OATK_E_NOMEM; }
-                sa.slabs = (uint8_t *) hb.p;
-            }
-#ifdef ECW_PROF
-            CK(hipMemsetAsync(d_prof, 0, 32 * 8, st));
-            sa.prof = d_prof;
-#endif
-            if (tier < LAST && t.hybrid && t.wpb > 1) hipLaunchKernelGGL((ec_wave_kernel<2, ECW_WPB>), dim3((unsigned) ((waves + ECW_WPB - 1) / ECW_WPB)), dim3(64 * ECW_WPB), (unsigned) (ECW_WPB * t.bytes), st, sa);
-            else if (tier < LAST && t.hybrid) hipLaunchKernelGGL((ec_wave_kernel<2, 1>), dim3((unsigned) waves), dim3(64), (unsigned) t.bytes, st, sa);
-            else if (tier < LAST && t.wpb > 1) hipLaunchKernelGGL((ec_wave_kernel<0, ECW_WPB>), dim3((unsigned) ((waves + ECW_WPB - 1) / ECW_WPB)), dim3(64 * ECW_WPB), (unsigned) (ECW_WPB * t.bytes), st, sa);
-            else if (tier < LAST) hipLaunchKernelGGL((ec_wave_kernel<0, 1>), dim3((unsigned) waves), dim3(64), (unsigned) t.bytes, st, sa);
-            else hipLaunchKernelGGL((ec_wave_kernel<1, 1>), dim3((unsigned) waves), dim3(64), 0, st, sa);
-#ifdef ECW_CENSUS
-            {
-                unsigned long long cz[2];
-                CK(hipStreamSynchronize(st));
-                CK(hipMemcpyFromSymbol(cz, HIP_SYMBOL(ecw_census), sizeof(cz)));
-                fprintf(stderr, "[ecw census] tier %d: %llu waves launched so far, %llu found work (cumulative); this launch %llu waves, %llu B of LDS each\n", tier, cz[0], cz[1], (unsigned long long) waves, (unsigned long long) t.bytes);
-            }
-#endif
-#ifdef ECW_PROF
-            {
-                unsigned long long hp[32];
-                CK(hipMemcpyAsync(hp, d_prof, sizeof(hp), hipMemcpyDeviceToHost, st));
-                CK(hipStreamSynchronize(st));
-                const char *nm[16] = {"target", "pops", "-", "restore+arc", "append", "wf steps", "result+push", "queue+out", "#arcs", "#extra steps", "#blocks", "#big:tl/bw", "#big:frames", "#big:path", "#big:c_len", "#lazy levels"};
-                unsigned long long tot = 0;
-                for (int i = 0; i < 8; ++i) tot += hp[i];
-                fprintf(stderr, "[ecw prof] tier %d: waves %llu scratch %llu B, %llu blocks\n", tier, (unsigned long long) waves, (unsigned long long) t.bytes, (unsigned long long) n_items);
-                for (int i = 0; i < 16; ++i) fprintf(stderr, "[ecw prof] %-14s %14llu  %5.1f%%  per block %.1f\n", nm[i], hp[i], i < 8? 100.0 * hp[i] / tot : 0.0, (double) hp[i] / (double) (hp[10]? hp[10] : 1));
-                unsigned long long dyn[16];
-                CK(hipMemcpyFromSymbol(dyn, HIP_SYMBOL(ecw_dyn), sizeof(dyn)));
-                fprintf(stderr, "[ecw prof] dynamic (cumulative over launches): step calls %llu, base turns %llu, extension turns %llu, ends reached %llu, next wavefronts %llu, append turns %llu; calls by n: 1:%llu 2:%llu 3-4:%llu 5-8:%llu 9-16:%llu more:%llu\n",
-                        dyn[0], dyn[1], dyn[2], dyn[3], dyn[4], dyn[5], dyn[6], dyn[7], dyn[8], dyn[9], dyn[10], dyn[11]);
-                fprintf(stderr, "[ecw prof] waves launched %llu, waves that found work %llu, batches %llu (cumulative)\n", dyn[13], dyn[12], dyn[14]);
-                fprintf(stderr, "[ecw prof] log2(tl) histogram:");
-                for (int i = 16; i < 32; ++i) fprintf(stderr, " %d:%llu", i - 16, hp[i]);
-                fprintf(stderr, "\n");
-            }
-#endif
-            return OATK_OK;
-        };
-        // 1. route by length (one pass over the work items), then the LDS tiers side by side.  A long block is a long chain of dependent steps and
-        //    its tier's carve-up lets few waves onto a CU, so run after the first tier the larger tiers are a tail of mostly idle CUs (0.8 ms for
-        //    86 blocks at config 2; 4 waves per CU for 4 ms at config 3).  Run BESIDE it they must not crowd it out either: a larger tier starts
-        //    first with a small share of every CU's LDS (a wave per CU, a wave per two CUs), the first tier fills the rest, and when that is
-        //    done a second launch of each larger tier, as wide as it likes, helps empty the same queue.
-        EcRoute rt;
-        for (int t = 0; t <= LAST; ++t) rt.cap[t] = T[t].usable? T[t].cap_t : 0, rt.list[t] = list[t], rt.cnt[t] = cur + t;
-        rt.cap[LAST] = 0x7FFFFFFF;
-        // (measured: at config 2, 0.8 M blocks, side by side saves 0.9 of 3.7 ms.  At config 3, 7.9 M blocks, it used to cost more than the tails it hides
-        //  -- 24.3 against 23.5 ms in r02 -- and was kept for small batches only; since r03 the first tier is known to run no faster with more than
-        //  sixteen of its waves on a CU (DESIGN.md 8.3), the slots the larger tiers take cost it nothing, and side by side is 15.5 against 18.6 ms)
-        const bool side_by_side = T[0].usable && !kn.serial_tiers;
-        unsigned long long routed[4] = {0, 0, 0, 0}, done[4] = {0, 0, 0, 0}, cnts[4] = {0, 0, 0, 0};
-        int qslot = 4, used_aux = 0;                                   // work-queue counters cur[4 ...], one per launch
-        if (side_by_side && n_work) {
-            hipLaunchKernelGGL(ec_route_kernel, dim3((unsigned) ((n_work + 256 * ECW_ROUTE_ITEMS - 1) / (256 * ECW_ROUTE_ITEMS))), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), n_work, rt);
-            CK(hipMemcpyAsync(routed, cur, sizeof(routed), hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-            if (!e->aux[0]) {
-                // (Streams share the runtime's hardware queues -- four per priority level by default, handed out by use count -- and two launches on one queue run one AFTER
-                //  the other: with the reads' uploader, the handle's own stream and a host program's streams about, the second stage's four classes were seen running
-                //  8 waves, then 4 waves (rocprofv3 kernel trace, round 6).  The solver's side streams are the only ones of their priority level, so they get queues of their own.)
-                int pr_least = 0, pr_greatest = 0;
-                CK(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
-                for (int i = 0; i < 5; ++i) { CK(hipStreamCreateWithPriority(&e->aux[i], hipStreamNonBlocking, i < 4? pr_greatest : pr_least)); CK(hipEventCreateWithFlags(&e->aux_ev[i], hipEventDisableTiming)); }
-                CK(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
-            }
-            CK(hipEventRecord(e->fork_ev, ctx->stream));
-            uint64_t aux1 = 2 * (uint64_t) ctx->n_cu;
-            { const char *ev = getenv("OATK_DEBUG_EC_AUX1"); if (ev && atoi(ev) > 0) aux1 = (uint64_t) atoi(ev); }
-            for (int tier = LAST - 1; tier >= 1; --tier) {               // longest first.  A wave takes ONE long block at a time, so every routed block may have its own
-                if (!T[tier].usable || !routed[tier]) continue;          // wave from the start (r04: 308 long blocks of the config-1 surrogate on 128 waves were 2.5 s)
-                hipStream_t st = e->aux[used_aux];
-                CK(hipStreamWaitEvent(st, e->fork_ev, 0));
-                { int rc = launch(tier, list[tier], routed[tier], st, cur + qslot++, true, tier == 1? aux1 : 0); if (rc) return rc; }
-                CK(hipEventRecord(e->aux_ev[used_aux], st));
-                ++used_aux;
-                done[tier] = routed[tier];
-            }
-            { int rc = launch(0, nullptr, 0, ctx->stream, cur + qslot++, true); if (rc) return rc; }
-        } else {
-            int rc = launch(T[0].usable? 0 : next_usable(0), nullptr, 0, ctx->stream, cur + qslot++, false); if (rc) return rc;      // nothing routed: the first usable tier takes everything
-        }
-        // 2. what a tier left over (frames or paths outgrew its carve-up; or, with nothing routed, everything too long) goes round again.  The first round starts as
-        //    soon as the FIRST tier is done -- its left-overs are the deep searches, the longest chains of dependent steps of the batch, and they should not wait
-        //    for the long blocks on the side streams --, later rounds when everything launched so far is done, until a round leaves nothing over.
-        const int first_tier = side_by_side && n_work? 0 : (T[0].usable? 0 : next_usable(0));
-        bool waited_aux = used_aux == 0;
-        for (int round = 0; ; ++round) {
-            CK(hipMemcpyAsync(cnts, cur, sizeof(cnts), hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-            if (round == 0) n_big = cnts[1] + cnts[2] + routed[3];   // blocks the first tier did not finish: routed past it, or left over by it
-            bool any = false;
-            for (int tier = first_tier + 1; tier <= LAST; ++tier) {
-                if (!T[tier].usable || cnts[tier] <= done[tier]) continue;
-                if (qslot >= 60) { ctx->err = "EC solver: more rounds of left-overs than queue counters (internal)"; return OATK_E_STATE; }
-                { int rc = launch(tier, list[tier] + done[tier], cnts[tier] - done[tier], ctx->stream, cur + qslot++, false); if (rc) return rc; }
-                done[tier] = cnts[tier];
-                any = true;
-            }
-            if (!any && waited_aux) break;
-            if (!waited_aux) { for (int i = 0; i < used_aux; ++i) CK(hipStreamWaitEvent(ctx->stream, e->aux_ev[i], 0)); waited_aux = true; }
-        }
-        {   // a block that outgrows the slabs
-            unsigned long long fin = 0;
-            CK(hipMemcpyAsync(&fin, cur + 63, 8, hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-            if (fin) { ctx->err = "error correction: a block outgrew the large scratch slab (DFS deeper than 4 MiB of frames)"; return OATK_E_NOMEM; }
-        }
-        unsigned long long used = 0;
+        { int rc = heavy? ec_solve_classes(ctx, e, kn, base, max_hl, n_big) : ec_solve_tiers(ctx, e, kn, base, max_hl, n_big); if (rc) return rc; }
+        unsigned long long fin = 0, used = 0;
+        CK(hipMemcpyAsync(&fin, base.pool_cursor + 63, 8, hipMemcpyDeviceToHost, ctx->stream));
+        CK(hipStreamSynchronize(ctx->stream));
+        if (fin) { ctx->err = "error correction: a block outgrew the large scratch slab (DFS deeper than 4 MiB of frames)"; return OATK_E_NOMEM; }
         CK(hipMemcpyAsync(&used, e->cursor.p, 8, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
         if (used <= pool_cap) break;
@@ -1386,12 +1311,10 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     aa.rd = rd, aa.scm_del = (const uint8_t *) e->scm_del.p, aa.scm_s = g.scm_s, aa.blk_off = e->blk_off.as<uint64_t>();
     aa.out = e->out.as<EcBlockOut>(), aa.path_pool = e->path_pool.as<uint64_t>(), aa.new_n = e->new_n.as<uint32_t>(), aa.new_off = nullptr;
     aa.new_k_mer = nullptr, aa.new_s_mer = nullptr, aa.new_m_pos = nullptr, aa.old_s_mer = ctx->pos_smer.as<uint64_t>();
-    aa.stats = (unsigned long long *) e->stats.p, aa.pass = 0;
-    aa.key_id = nullptr, aa.val_occ = nullptr, aa.sid0 = ctx->sid0;
+    aa.stats = (unsigned long long *) e->stats.p, aa.pass = 1;
     if (n_work) hipLaunchKernelGGL(ec_block_stats_kernel, dim3((unsigned) (n_work / 256 + 1 < 512? n_work / 256 + 1 : 512)), dim3(256), 0, ctx->stream, e->work.as<EcWork>(),
                                    e->out.as<EcBlockOut>(), n_work, (unsigned long long *) e->stats.p);
-    if (getenv("OATK_DEBUG_EC_COUNT_WALK")) hipLaunchKernelGGL(ec_assemble_wave_kernel<0>, rblocks, dim3(256), 0, ctx->stream, aa);      // (the counting walk, as until r04: A/B and tests)
-    else hipLaunchKernelGGL(ec_new_n_kernel, blocks(nr), dim3(256), 0, ctx->stream, nr, e->copy_n.as<uint32_t>(), e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->out.as<EcBlockOut>(), e->new_n.as<uint32_t>());
+    hipLaunchKernelGGL(ec_new_n_kernel, blocks(nr), dim3(256), 0, ctx->stream, nr, e->copy_n.as<uint32_t>(), e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->out.as<EcBlockOut>(), e->new_n.as<uint32_t>());
     uint64_t tot = 0;
     { int rc = ec_exclusive_scan_u32(ctx, e, e->new_n, e->new_n64, e->new_off, nr, &tot); if (rc) return rc; }
     e->new_tot = tot;
@@ -1399,7 +1322,6 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     EENSURE(key_id, (tot + 1) * 4); EENSURE(key_sorted, (tot + 1) * 4); EENSURE(val_occ, (tot + 1) * 8); EENSURE(occ, (tot + 1) * 8);
     aa.new_off = e->new_off.as<uint64_t>(), aa.new_k_mer = e->new_k.as<uint64_t>(), aa.new_m_pos = e->new_m.as<uint32_t>(), aa.new_s_mer = e->new_s.as<uint64_t>();
     aa.key_id = e->key_id.as<uint32_t>(), aa.val_occ = e->val_occ.as<uint64_t>(), aa.sid0 = ctx->sid0;
-    aa.pass = 1;
     hipLaunchKernelGGL(ec_assemble_wave_kernel<1>, rblocks, dim3(256), 0, ctx->stream, aa);
 
     // ---- update_syncmer_db ----

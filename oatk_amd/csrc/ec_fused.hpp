@@ -25,8 +25,8 @@ namespace oatk {
 #define ECF_OWN (64 - 2 * ECF_S)  // slots a wave owns
 #define ECF_NW 16                 // waves per block: 16 x 56 = 896 slots, 2 bw + 3 <= 896
 #define ECF_TIER 32u
-#define ECF_NT 64                 // (CERT) pairs of tables a workgroup keeps per block: one per arc with a long string (14 - 17 in the heavy blocks of 40 k surrogate reads; at 200 k reads 24 were too few for half the long arcs that die: profiles/r06g)
-// (CERT) a workgroup's table region in HBM, 32-bit words: [0] pairs in use, [1 .. ECF_NT] their arcs, then (from word 128 on) ECF_NT x 2 x (cap_t + 1) numbers
+#define ECF_NT 64                 // (table test) pairs of tables a workgroup keeps per block: one per arc with a long string (14 - 17 in the heavy blocks of 40 k surrogate reads; at 200 k reads 24 were too few for half the long arcs that die: profiles/r06g)
+// (table test) a workgroup's table region in HBM, 32-bit words: [0] pairs in use, [1 .. ECF_NT] their arcs, then (from word 128 on) ECF_NT x 2 x (cap_t + 1) numbers
 __host__ __device__ inline uint64_t ecf_tab_words(int32_t cap_t) { return 128 + (uint64_t) ECF_NT * 2 * (uint64_t) (cap_t + 1); }
 
 // LDS carve-up (32-bit words): [endt: 2 x NW][bnd: 2 x NW x 2 S][red: 2 x NW x 2][any: 2 x NW][bc: 8] ts cs frames
@@ -38,8 +38,8 @@ __host__ __device__ inline uint32_t ecf_lds_words(int32_t cap_t, int32_t cap_c, 
 
 #ifdef ECF_PROF2
 // development builds (-DECF_PROF2): cycles of thread 0 by phase of the per-arc loop, summed over blocks, one row per class of workgroups (tools/r06_prof_arcs.sh)
-//   0 arcs  1 from a frame  2 without alignment  3 known dead (CERT)  4 tables built  5 aligned  6 arcs of >= 32 bases  7 ... with a lagging wavefront
-//   8 top (barrier + restore + arc)  9 append + barrier  10 CERT test  11 alignment  12 outcome + frame push  13 table building  14 blocks  15 wavefront steps
+//   0 arcs  1 from a frame  2 without alignment  3 known dead (table test)  4 tables built  5 aligned  6 arcs of >= 32 bases  7 ... with a lagging wavefront
+//   8 top (barrier + restore + arc)  9 append + barrier  10 table test  11 alignment  12 outcome + frame push  13 table building  14 blocks  15 wavefront steps
 __device__ unsigned long long ecf_prof2[5][28];      // 16 .. 19 aligned arcs by (string >= 32 bases) x 2 + (dies by score), 20 .. 23 their wavefront steps
 #define ECF_P2_T(i) do { const uint64_t now_ = __builtin_readcyclecounter(); p2[i] += now_ - p2_last; p2_last = now_; } while (0)
 #define ECF_P2_C(i, v) (p2[i] += (uint64_t) (v))
@@ -55,7 +55,7 @@ struct EcfShared {
     uint32_t *os;
     uint64_t *c_path, *o_path;
     int32_t cap_t, cap_c, cap_path, cap_fl, cap_fh;
-    int32_t *tab;                 // (CERT) this workgroup's table region, ecf_tab_words(cap_t) words
+    int32_t *tab;                 // (table test) this workgroup's table region, ecf_tab_words(cap_t) words
 };
 
 // what one lane has to do in one step (levdist.c:156-205, extension mode, no traceback): its diagonal run down (kn, and whether that reached an end of a string), and the
@@ -319,10 +319,10 @@ __global__ __launch_bounds__(64 * NW) void ecf_wf_ed_kernel(const uint32_t *tw, 
 
 // Solve one block with the whole workgroup (ech_solve_block of ec_heavy.hpp with the wavefront one slot per lane and ecf_align for wf_ed_core).  Returns false when the
 // block outgrows the carve-up (it is then re-run by the next class or the slab tier of ec_wave.hpp).
-// CERT (experimental, OATK_DEBUG_EC_CERT=1; written after round 5's last GPU run and never executed): an arc that appends a long string is first asked whether it can be
-// alive at all -- min over the band of (what the parent's wavefront knows of its last row + the string's tables) beyond bw: dead by score, no step taken (DESIGN.md 8.3,
-// tests/trace/ec_trace.c ECT_ROWS: 92.8 % of such arcs' steps on the config-1 surrogate, no living arc).  Without CERT the code is what it was.
-template <int NW, bool CERT = false>
+// The table test (round 6, always on): an arc that appends a long string is first asked whether it can be alive at all -- min over the band of (what the
+// parent's wavefront knows of its last row + the string's tables) beyond bw: dead by score, no step taken (tests/trace/ec_trace.c ECT_ROWS:
+// 92.8 % of such arcs' steps on the config-1 surrogate, no living arc).  The tables live in a region of HBM per workgroup (a.os_slabs, ecf_tab_words).
+template <int NW>
 __device__ bool ecf_solve_block(const EcLive &lv, const EcReads &rd, const EcWork &wk, const EcfShared &sh, double max_edist,
                                 uint32_t &status_out, uint32_t &np_out, uint32_t &tried_out, uint32_t &n_path_out, uint32_t &wf_steps_out, uint32_t &wf_diag_out)
 {
@@ -376,11 +376,11 @@ __device__ bool ecf_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
     bool vpend = false;
     uint32_t v_arc = 0;
     int32_t v_depth = 0;
-    int32_t aligned_len = 0;                          // (CERT) the consensus length the wavefront stands for: behind c_len where alignments were skipped
+    int32_t aligned_len = 0;                          // (table test) the consensus length the wavefront stands for: behind c_len where alignments were skipped
 #ifdef ECF_PROF2
     uint64_t p2[28] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, p2_last = __builtin_readcyclecounter();
 #endif
-    if (CERT) { if (t == 0 && sh.tab) sh.tab[0] = 0; }
+    if (t == 0 && sh.tab) sh.tab[0] = 0;
 
     // workgroup-wide "any lane": rare paths only (ties between optimum paths)
     auto wg_any = [&](bool p) -> bool {
@@ -505,7 +505,7 @@ __device__ bool ecf_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
             continue;
         }
         bool known_dead = false;
-        if constexpr (CERT) {
+        {   // the table test
             const int32_t l0 = c_len - ext;
             if (ext >= 32) { ECF_P2_C(6, 1); if (aligned_len != l0) ECF_P2_C(7, 1); else if (ext > 1024) ECF_P2_C(24, 1); else if (!(l0 >= 1 && l0 - 1 + bw + 2 < tl - 1)) ECF_P2_C(25, 1); }
             // a long string, the wavefront standing for exactly the consensus before it, and no row before the new ones within reach of the target's last column
@@ -567,7 +567,7 @@ __device__ bool ecf_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
         }
         // wf_ed_core (levdist.c:265-310)
         ECF_P2_T(10);
-        if (CERT && known_dead) { score = bw + 1, t_end = -1, q_end = -1; ECF_P2_C(3, 1); }          // (what the steps would have left: levdist.c:303, syncerr.c:195 "zero if not aligned")
+        if (known_dead) { score = bw + 1, t_end = -1, q_end = -1; ECF_P2_C(3, 1); }          // (what the steps would have left: levdist.c:303, syncerr.c:195 "zero if not aligned")
         else {
 #ifdef ECF_PROF2
             const uint32_t st0_ = wf_steps;
@@ -645,7 +645,7 @@ __device__ bool ecf_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
 }
 
 // One workgroup per block, blocks taken one at a time from the list.  EcwArgs as for ec_heavy_kernel.
-template <int NW, bool CERT = false>
+template <int NW>
 __global__ __launch_bounds__(64 * NW) void ec_fused_kernel(EcwArgs a)
 {
     extern __shared__ uint32_t ecf_lds[];
@@ -661,7 +661,7 @@ __global__ __launch_bounds__(64 * NW) void ec_fused_kernel(EcwArgs a)
     sh.c_path = (uint64_t *) slab, sh.o_path = sh.c_path + a.cap_path;
     sh.os = (uint32_t *) (sh.o_path + a.cap_path);
     sh.fh = (uint8_t *) (sh.os + ecw_words(a.cap_c));
-    sh.tab = CERT && a.os_slabs? (int32_t *) a.os_slabs + (uint64_t) blockIdx.x * ecf_tab_words(a.cap_t) : nullptr;      // (the fused launches do not use os_slabs otherwise)
+    sh.tab = a.os_slabs? (int32_t *) a.os_slabs + (uint64_t) blockIdx.x * ecf_tab_words(a.cap_t) : nullptr;      // (the fused launches do not use os_slabs otherwise)
     const uint64_t total = a.todo? a.n_todo : a.n_work;
     uint64_t pool_at = 0, pool_end = 0;
     for (;;) {
@@ -691,7 +691,7 @@ __global__ __launch_bounds__(64 * NW) void ec_fused_kernel(EcwArgs a)
             o.short_block = 1;                         // syncerr.c:502-504
         } else {
             uint32_t st = 0, np = 0;
-            if (ECW_RARE(!(ecf_solve_block<NW, CERT>(a.lv, a.rd, wk, sh, a.max_edist, st, np, o.tried, o.n_path, o.wf_steps, o.wf_diag)))) {
+            if (ECW_RARE(!(ecf_solve_block<NW>(a.lv, a.rd, wk, sh, a.max_edist, st, np, o.tried, o.n_path, o.wf_steps, o.wf_diag)))) {
                 o.flags = 1;
                 if (t == 0) a.todo_out[atomicAdd(a.todo_cnt, 1ULL)] = (uint32_t) wi;
             } else {

@@ -108,19 +108,6 @@ __global__ void ecw_import_kmer_kernel(uint64_t n, const uint32_t *ids, const ui
     vtx_mpos[ids[i]] = rev[i] & 1u;                            // position 0 on its own string
 }
 
-#ifdef ECW_PROF
-__device__ unsigned long long ecw_dyn[16];          // dynamic counts of the loops of ecw_step (development builds only)
-#define ECW_D(i) do { if ((threadIdx.x & 63) == 0) atomicAdd(&ecw_dyn[i], 1ULL); } while (0)
-#define ECW_T(i) do { const unsigned long long _t = __builtin_readcyclecounter(); s.prof[i] += _t - s.t_last; s.t_last = _t; } while (0)
-#define ECW_C(i, v) do { s.prof[i] += (v); } while (0)
-#else
-#define ECW_T(i) do {} while (0)
-#define ECW_C(i, v) do {} while (0)
-#define ECW_D(i) do {} while (0)
-#endif
-#ifdef ECW_CENSUS                                    // development builds: how many of the launched waves were resident early enough to find work
-__device__ unsigned long long ecw_census[2];
-#endif
 // block placement: the usual path of the search falls through (a taken branch is what costs here)
 #define ECW_LIKELY(x) __builtin_expect(!!(x), 1)
 #define ECW_RARE(x) __builtin_expect(!!(x), 0)
@@ -132,9 +119,6 @@ struct EcwScratch {
     uint8_t *frames;              // DFS frame arena
     int32_t cap_t, cap_c, cap_w, cap_path, cap_f;
     int32_t arc_budget;           // arcs after which a block is given up here (0: never): a search inside a repeat tries tens of thousands (round 6)
-#ifdef ECW_PROF
-    mutable unsigned long long prof[32], t_last;
-#endif
 };
 
 struct EcwFrame {                 // state at the entry of one DFS level (syncerr.c:158-171), followed by k[n]
@@ -155,8 +139,6 @@ __device__ int ecw_step(const uint32_t *ts, int32_t tl, const uint32_t *qs, int3
     const int32_t n = wv.n, d0 = wv.d0;
     int32_t *k = wv.k;
     t_end = q_end = -1;
-    ECW_D(0);
-    if (n == 1) ECW_D(6); else if (n <= 2) ECW_D(7); else if (n <= 4) ECW_D(8); else if (n <= 8) ECW_D(9); else if (n <= 16) ECW_D(10); else ECW_D(11);
     int lg = 0;                                        // lanes per diagonal = 1 << lg
     if (n <= 32) lg = n <= 1? 6 : __builtin_clz((uint32_t) (n - 1)) - 26;      // 64 / next_pow2(n)
     const int G = 1 << lg, c = lane & (G - 1), gbase = lane & ~(G - 1);
@@ -178,9 +160,7 @@ __device__ int ecw_step(const uint32_t *ts, int32_t tl, const uint32_t *qs, int3
                 act[u] = a0[u];
                 lim[u] = (ql - dd[u] < tl? ql - dd[u] : tl) - 1;
             }
-            ECW_D(1);
             while (__ballot(act[0] | act[1] | act[2] | act[3])) {
-                ECW_D(2);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int32_t r = lim[u] - kk[u];
@@ -202,7 +182,6 @@ __device__ int ecw_step(const uint32_t *ts, int32_t tl, const uint32_t *qs, int3
                     if (a0[u] && lane < fl) k[j] = kk[u];
                     t_end = (int32_t) ecw_lane((uint32_t) kk[u], fl);
                     q_end = t_end + d0 + base + 64 * u + fl;
-                    ECW_D(3);
                     ecw_sync();
                     return 1;
                 }
@@ -212,7 +191,6 @@ __device__ int ecw_step(const uint32_t *ts, int32_t tl, const uint32_t *qs, int3
     } else
     for (int32_t base = 0; base < n; base += 64) {
         const int32_t j = base + (lane >> lg);
-        ECW_D(1);
         const bool valid = j < n;
         int32_t kk = valid? k[j] : 0;
         const int32_t dd = valid? d0 + j : 0;          // (0: lanes without a diagonal read, harmlessly, inside the strings)
@@ -224,7 +202,6 @@ __device__ int ecw_step(const uint32_t *ts, int32_t tl, const uint32_t *qs, int3
         if (__ballot(act)) {
             const int32_t o = c << 4;
             for (;;) {
-                ECW_D(2);
                 const int32_t r = lim - kk - o;                 // bases left from this lane's window on
                 const int32_t oo = r > 0? o : 0;                // (a window behind the end is not read: the strings may lie in HBM, at the end of a buffer)
                 const uint32_t x = ecw_win16(ts, kk + 1 + oo) ^ ecw_win16(qs, kk + dd + 1 + oo);
@@ -248,7 +225,6 @@ __device__ int ecw_step(const uint32_t *ts, int32_t tl, const uint32_t *qs, int3
             if (act0 && c == 0 && j < jf) k[j] = kk;
             t_end = (int32_t) ecw_lane((uint32_t) kk, fl);
             q_end = t_end + d0 + jf;
-            ECW_D(3);
             ecw_sync();
             return 1;
         }
@@ -257,7 +233,6 @@ __device__ int ecw_step(const uint32_t *ts, int32_t tl, const uint32_t *qs, int3
     ecw_sync();
     // next wavefront: diagonals d0 - 1 .. d0 + n (levdist.c:183-205)
     int32_t *__restrict__ nk = wv.spare;
-    ECW_D(4);
 #pragma unroll 4
     for (int32_t ib = 0; ib < n + 2; ib += 64) {      // (a uniform trip count -- one turn up to 62 diagonals -- and no branches inside: reads with clamped indices, selects)
         const int32_t i = ib + lane, jj = i - 1;
@@ -400,8 +375,7 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
     const int32_t tl = wk.l;
     int32_t bw = (int32_t) ceil((double) tl * max_edist);
     if (bw < EC_MIN_ERR_BASE) bw = EC_MIN_ERR_BASE;
-    ECW_C(16 + (31 - __builtin_clz((uint32_t) tl | 1u)), 1);                  // 16..: histogram of log2(tl)
-    if (ECW_RARE(tl > s.cap_t || 2 * bw + 8 > s.cap_w)) { ECW_C(11, 1); return false; }
+    if (ECW_RARE(tl > s.cap_t || 2 * bw + 8 > s.cap_w)) return false;
     // the first arc out of the source is fetched while the target is gathered
     EcwArcRegs pre;
     pre.a = make_uint4(0, 0, 0, 0), pre.b = make_uint2(0, 0);
@@ -436,7 +410,6 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
         else for (int32_t wb = 0; (wb << 4) < tl; wb += 256) gather_target(std::integral_constant<int, 4>(), rev, wb);   // four windows per lane with their loads in flight together
     };
     if (wk.r) gather_all(std::true_type()); else gather_all(std::false_type());
-    ECW_T(0);                                          // 0: target gather
     int32_t status = EC_FAILURE, n_path = 0, edist = INT32_MAX, s_edist = INT32_MAX;
     int32_t c_len = 0, o_len = 0, np = 0;
     uint32_t tried = 0, wf_steps = 0;
@@ -470,7 +443,7 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
         return true;
     };
     if (ECW_LIKELY(wk.ln == 1)) vpend = true, v_arc = wk.lp, v_depth = 0;
-    else if (!push_frame(wk.lp, wk.ln, 0)) { ECW_C(12, 1); return false; }
+    else if (!push_frame(wk.lp, wk.ln, 0)) return false;
 
     while (nfr > 0 || vpend) {
         ecw_sync();
@@ -487,7 +460,6 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
                 fsz = top;
                 top = ecw_uni(f->prev_off);
                 --nfr;
-                ECW_T(1);                              // 1: pops
                 continue;
             }
             if (lane == 0) f->arc_i = a + 1;
@@ -498,7 +470,6 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
             const int32_t *sv = (const int32_t *) (f + 1);
             for (int32_t j = lane; j < wv.n; j += 64) s.ka[j] = sv[j];
         }
-        ECW_C(8, 1);                                   // 8: arcs tried
         ++tried;
         if (ECW_RARE(s.arc_budget > 0 && (tried > (uint32_t) s.arc_budget || wf_steps > 2u * (uint32_t) s.arc_budget))) return false;      // a search inside a repeat (arcs, or twice as many wavefront steps): it starts again where it is given a workgroup
         if (ECW_RARE(pre_idx != a)) pre = ecw_arc_load(lv.arc, a);
@@ -506,13 +477,12 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
         const int32_t ls = (int32_t) ecw_uniu(pre.a.y), ext = K - ls;
         const uint32_t w_hs16 = ecw_uniu(pre.a.z), w_mpos = ecw_uniu(pre.a.w), w_lp = ecw_uniu(pre.b.x), w_ln = ecw_uniu(pre.b.y);
         const int32_t t_end0 = t_end;
-        if (ECW_RARE(depth + 2 > s.cap_path || c_len + ext > s.cap_c)) { ECW_C(depth + 2 > s.cap_path? 13 : 14, 1); return false; }
+        if (ECW_RARE(depth + 2 > s.cap_path || c_len + ext > s.cap_c)) return false;
         if (lane == 0) s.c_path[depth + 1] = w;
         int32_t cn = depth + 2;                       // entries in c_path
         // the arc most likely to be tried next: the first one out of w (in flight during the gather and the alignment)
         pre_idx = 0xFFFFFFFFu;
         if (ECW_LIKELY(w_ln)) pre = ecw_arc_load(lv.arc, w_lp), pre_idx = w_lp;
-        ECW_T(3);                                      // 3: restore + arc fetch
         {   // append the part of w's k-mer that lies beyond the overlap (syncerr.c:186-190).  With F the vertex's forward
             // string, base t of the extension is F[ls + t] for a forward w and comp(F[K - ls - 1 - t]) for a reverse one; F itself is
             // the first occurrence's k-mer, reverse-complemented when that occurrence is reverse: two cases remain.
@@ -523,7 +493,6 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
             for (int32_t wb = w0; wb <= w1; wb += 64) {             // (uniform trip count: one turn for an extension of up to 1000 bases)
                 const int32_t wi = wb + lane;
                 if (wi > w1) continue;
-                ECW_D(5);
                 const int32_t t0 = (wi << 4) - c_len;
                 uint32_t x = asc? ecw_gather16(vs, (int64_t) pos + ls + t0, false) : ecw_gather16(vs, (int64_t) pos + K - 1 - ls - t0, true);
                 if (t0 < 0) {
@@ -535,7 +504,6 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
             c_len += ext;
         }
         ecw_sync();
-        ECW_T(4);                                      // 4: consensus append
         // A vertex on an unbranched stretch that cannot be the end of the path needs no alignment of its own.  wf_ed_core RESUMES: run on the
         // consensus up to w and then on the consensus up to w's successor, it leaves the wavefront (and score, ends) that a single run on the longer
         // consensus leaves -- extending a diagonal in two goes or in one is the same run of matches, and a step that ends early stores nothing
@@ -546,7 +514,6 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
         // once an optimum exists (syncerr.c:211).  Most blocks are source - two or three such vertices - sink: one alignment instead of three or four.
         if (edist == INT32_MAX && wk.end_utg != EC_NONE && wk.end_utg != w && w_ln == 1 && n_path < EC_MAX_DFS_PATH && c_len - K <= tl + bw && c_len >= bw + 3) {
             vpend = true, v_arc = w_lp, v_depth = depth + 1;
-            ECW_C(15, 1);                              // 15: levels without an alignment
             continue;
         }
         // wf_ed_core (levdist.c:265-310)
@@ -554,10 +521,8 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
             ++wf_steps, wf_diag += (uint64_t) wv.n;
             if (ecw_step(s.ts, tl, s.cs, c_len, bw, wv, s.ka, s.kb, t_end, q_end)) break;
             ++score;
-            ECW_C(9, 1);                               // 9: wavefront steps beyond the first
             if (ECW_RARE(score > bw)) break;
         }
-        ECW_T(5);                                      // 5: wavefront steps
         t_end += 1, q_end += 1;
         const int32_t ql = c_len;
         const int32_t sc = score + tl - t_end;        // syncerr.c:209
@@ -603,7 +568,7 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
         if (score <= bw && ql - K <= tl + bw && ((wk.end_utg != EC_NONE && wk.end_utg != w) || t_end < tl)) {
             if (n_path < EC_MAX_DFS_PATH) {           // the callee would return at once otherwise (syncerr.c:146-148)
                 if (ECW_LIKELY(w_ln == 1)) vpend = true, v_arc = w_lp, v_depth = depth + 1;
-                else if (w_ln > 1 && !push_frame(w_lp, w_ln, depth + 1)) { ECW_C(12, 1); return false; }      // (no arcs: the callee's loop does not run)
+                else if (w_ln > 1 && !push_frame(w_lp, w_ln, depth + 1)) return false;      // (no arcs: the callee's loop does not run)
             }
         } else {
             ++n_path;
@@ -613,7 +578,6 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
         if (new_opt && (nfr > 0 || vpend)) {
             for (int32_t wi = lane; wi < ((o_len + 15) >> 4); wi += 64) s.os[wi] = s.cs[wi];
         }
-        ECW_T(6);                                      // 6: result handling + push
     }
     ecw_sync();
     status_out = (uint32_t) status, np_out = (uint32_t) np, tried_out = tried, n_path_out = (uint32_t) n_path, wf_steps_out = wf_steps, wf_diag_out = (uint32_t) (wf_diag >> 6);
@@ -651,9 +615,6 @@ struct EcwArgs {
     int32_t skip_l;               // blocks longer than this were routed to a larger tier before the launch (ec_route_kernel): not this launch's business
     int32_t batch;                // blocks taken from the queue per atomic: ECW_BATCH where the blocks are millions and small, 1 where they are few and long
     int32_t arc_budget;           // first tier: arcs after which a block is left to the classes behind it (0: never)
-#ifdef ECW_PROF
-    unsigned long long *prof;
-#endif
 };
 
 // Blocks too long for the first tier's carve-up are known before anything runs (the length is in the work item): they go straight onto the
@@ -759,33 +720,13 @@ __global__ __launch_bounds__(64 * WPB) void ec_wave_kernel(EcwArgs a)
     s.c_path = (uint64_t *) p, p += 2 * a.cap_path;
     s.o_path = (uint64_t *) p, p += 2 * a.cap_path;
     s.frames = (uint8_t *) p;
-#ifdef ECW_PROF
-    for (int i = 0; i < 32; ++i) s.prof[i] = 0;
-    s.t_last = __builtin_readcyclecounter();
-#endif
     const uint64_t total = a.todo? a.n_todo : a.n_work;
     uint64_t pool_at = 0, pool_end = 0;                // this wave's chunk of the path pool
-    ECW_D(13);                                         // 13: waves launched, 12: waves that found work, 14: batches
-#if defined(ECW_PROF) || defined(ECW_CENSUS)
-    bool first_batch = true;
-#endif
-#ifdef ECW_CENSUS
-    if (lane == 0) atomicAdd(&ecw_census[0], 1ULL);
-#endif
     for (;;) {
-        ECW_T(7);                                      // 7: queue + output
         unsigned long long t0 = 0;
         if (lane == 0) t0 = atomicAdd(a.next, (unsigned long long) a.batch);
         t0 = ecw_uni64(t0);
         if (t0 >= total) break;
-#ifdef ECW_CENSUS
-        if (first_batch && lane == 0) atomicAdd(&ecw_census[1], 1ULL);
-        first_batch = false;
-#endif
-#ifdef ECW_PROF
-        if (first_batch) { ECW_D(12); first_batch = false; }
-        ECW_D(14);
-#endif
         const int cnt = total - t0 < (uint64_t) a.batch? (int) (total - t0) : a.batch;
         // lane i holds block i of the batch
         uint64_t my_wi = 0;
@@ -832,12 +773,8 @@ __global__ __launch_bounds__(64 * WPB) void ec_wave_kernel(EcwArgs a)
             o.ticks = MODE != 0? (uint32_t) (__builtin_amdgcn_s_memrealtime() - tick0) : 0u;
             if (lane == 0) a.out[wi] = o;
             ecw_sync();
-            ECW_C(10, 1);                              // 10: blocks
         }
     }
-#ifdef ECW_PROF
-    if (lane == 0) for (int i = 0; i < 32; ++i) atomicAdd(a.prof + i, s.prof[i]);
-#endif
 }
 
 }  // namespace oatk

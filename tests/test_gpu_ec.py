@@ -145,24 +145,22 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("graph", ["host", "device", "device-tiers", "device-tiers-serial", "device-heavy", "device-heavy-mix", "device-heavy-spill", "device-fused", "device-fused-spill", "device-fused-nocert", "device-fused-nw2", "device-fused-nw4", "device-fused-nw8", "device-fused-nw16"])
+@pytest.mark.parametrize("graph", ["host", "device", "device-tiers", "device-tiers-serial", "device-heavy", "device-heavy-mix", "device-heavy-spill", "device-fused", "device-fused-spill", "device-fused-nw2", "device-fused-nw4", "device-fused-nw8", "device-fused-nw16"])
 @pytest.mark.parametrize("case", range(len(CASES)))
 def test_device_ec_matches_reference(hip, case, graph, monkeypatch):
-    # the table test for long arcs (ec_fused.hpp CERT) is on by default since round 6; device-fused-nocert: without.  device-fused-nw4 / 8 / 16: the second stage's narrowest
-    # class of workgroups has that many waves (by default the classes are one wave -- ec_heavy.hpp without a budget -- and 4, 8 and 16 waves of ec_fused.hpp by the block's band, and these cases' blocks all fit one wave or four)
-    monkeypatch.setenv("OATK_DEBUG_EC_CERT", "0" if graph == "device-fused-nocert" else "1")
+    # device-fused-nw4 / 8 / 16: the second stage's narrowest class of workgroups has that many waves (by default the classes are one wave -- ec_heavy.hpp without a
+    # budget -- and 4, 8 and 16 waves of ec_fused.hpp by the block's band, and these cases' blocks all fit one wave or four)
     monkeypatch.setenv("OATK_DEBUG_EC_FUSED_MIN_NW", graph[len("device-fused-nw"):] if graph.startswith("device-fused-nw") else "0")
     K, S, c, mk = CASES[case]
     reads = mk()
     # tiny first tier: most blocks run in the classes behind it -- routed there by length and run beside the first tier, or left over by it.
     #   device-tiers[-serial]: the tiers of round 4 (one wave per block, larger LDS carve-ups, HBM slabs: OATK_DEBUG_EC_HEAVY=0)
-    #   device-heavy:          everything longer than 48 bases in the first class of the workgroup solver (ec_heavy.hpp, one diagonal per lane)
-    #   device-heavy-mix:      48 < l <= 160 in the first class, <= 400 in the second (two diagonals per lane), the rest in the third (six)
-    #   device-heavy-spill:    as device-heavy with an LDS frame arena of 64 bytes: every DFS frame goes to the HBM slab
+    #   device-heavy:          everything longer than 48 bases in the first class (ec_heavy.hpp, one wave per block), default step budget
+    #   device-heavy-mix:      48 < l <= 160 in the first class, <= 400 in the second (one wave, eight registers per lane), the rest in the third (four waves, six)
+    #   device-heavy-spill:    as device-heavy with an LDS frame arena of 64 bytes: every DFS frame of the one-wave classes goes to the HBM slab
     t0, t1 = (48, 160) if graph.startswith("device-tiers") or graph == "device-heavy-mix" else ((48, 0) if graph.startswith("device-heavy") or graph.startswith("device-fused") else (0, 0))
-    monkeypatch.setenv("OATK_DEBUG_EC_FUSED", "0" if graph in ("device-heavy", "device-heavy-spill") else "1")
     # device-fused: every block that takes more than one wavefront step goes past its budget and starts again in ec_fused.hpp (several steps per barrier); device-heavy-mix:
-    # more than eight; by default three thousand
+    # more than eight; by default a thousand
     monkeypatch.setenv("OATK_DEBUG_EC_STEP_BUDGET", "1" if graph.startswith("device-fused") else ("8" if graph == "device-heavy-mix" else "0"))
     monkeypatch.setenv("OATK_DEBUG_EC_SERIAL_TIERS", "1" if graph == "device-tiers-serial" else "0")
     # which solver: "device" leaves the choice to the library (by the graph: round 4's tiers when the live graph does not branch anywhere, else the classes with budgets and the
