@@ -84,7 +84,8 @@ __global__ __launch_bounds__(256) void cons_rl_kernel(ConsArgs a)
     const int K = a.K;
     for (int t0 = 0; t0 < K; t0 += CONS_Q * 64) {
         for (uint32_t i = tid; i < CONS_Q * 64; i += 256) tot[i] = 0;
-        if (tid == 0) s_m = 0, s_first = ~0ULL;
+        // the occurrences that take part do not depend on t0: counted in the first pass, kept for the rounding of every later one
+        if (tid == 0 && t0 == 0) s_m = 0, s_first = ~0ULL;
         __syncthreads();
         uint32_t acc[CONS_Q];
 #pragma unroll

@@ -83,3 +83,31 @@ def long_run_reads(seed, K):
         r = bytes(r)
         reads.append(A.revcomp(r) if rng.integers(0, 2) else r)
     return reads
+
+
+def late_run_reads(seed, K, n_reads=150):
+    """reads for k above 1024: HiFi-like reads of 8-10 k bases (hoco length several k) over a genome of about 30 k bases where a homopolymer
+    of 260-700 bases follows every k/3 random bases -- so syncmers have runs beyond the 255 escape past their position 1024, and reads of
+    both strands cover each; run-length errors give the consensus something to average"""
+    import adversarial as A
+    rng = np.random.default_rng(seed)
+    g = bytearray()
+    j = 0
+    while len(g) < 30 * K:
+        ln = (260, 300, 450, 700)[j % 4]
+        g += A.rand_dna(rng, K // 3) + b"ACGT"[j % 4:j % 4 + 1] * ln
+        j += 1
+    g = bytes(g)
+    reads = []
+    for i in range(n_reads):
+        ln = int(rng.integers(8 * K, 10 * K))
+        st = int(rng.integers(0, len(g) - ln))
+        r = bytearray(g[st:st + ln])
+        for p in sorted(rng.integers(1, len(r) - 1, size=30).tolist(), reverse=True):
+            if rng.integers(0, 2):
+                r.insert(p, r[p])
+            elif r[p] == r[p - 1]:
+                del r[p]
+        r = bytes(r)
+        reads.append(A.revcomp(r) if i & 1 else r)
+    return reads

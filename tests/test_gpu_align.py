@@ -78,6 +78,7 @@ CASES = [
     (301, 21, 5, lambda: T.sample_reads(T.genome_with_repeats(7, 25000, unit=1500, copies=4), 320, 4000, 0.003, 8)),
     (101, 11, 5, lambda: T.sample_reads(T.genome_with_repeats(9, 9000, unit=600, copies=3), 300, 1500, 0.004, 10)),
     (1001, 31, 6, lambda: T.sample_reads(T.genome_with_repeats(5, 50000), 260, 9000, 0.001, 6)),
+    T.CASES[8], T.CASES[9],                                 # k above 1024
 ]
 
 

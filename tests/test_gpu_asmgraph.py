@@ -53,7 +53,7 @@ def test_device_asmgraph_matches_golden(hip, case, stage):
 
 @needs_ref
 @pytest.mark.parametrize("stage", ["raw", "ec"])
-@pytest.mark.parametrize("case,a", [(0, 0.35), (1, 0.0), (2, 0.35), (3, 0.9), (4, 0.35), (5, 0.2), (6, 0.5)])
+@pytest.mark.parametrize("case,a", [(0, 0.35), (1, 0.0), (2, 0.35), (3, 0.9), (4, 0.35), (5, 0.2), (6, 0.5), (8, 0.35), (9, 0.35)])
 def test_device_asmgraph_matches_reference(hip, case, a, stage):
     K, S, c, mk = T.CASES[case]
     db, scm = device_dbs(hip, mk(), K, S)                   # reference-layout structs built from the device scan + count

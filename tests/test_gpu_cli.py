@@ -42,6 +42,20 @@ def test_cli_fasta_everything_from_the_device(tmp_path, K, S, cov, err):
     assert tab["scg_syncmer_consensus"][0] > 20 and tab["calc_syncmer_overlap"][0] > 20      # the consensus hooks were served from the device tables
 
 
+@pytest.mark.parametrize("K,S,devices", [(1501, 31, None), (2049, 21, None), (1501, 31, "0,0")])
+def test_cli_above_k1024(tmp_path, K, S, devices):
+    """k above 1024 (the drop-in declines only k beyond oatk_hip_max_k()): the consensus walks a syncmer's positions in passes of 1024, with one handle
+    (oatk_hip_consensus) and over several (the sharded totals)"""
+    reads = A.hifi_like(150, 60000 if K < 2000 else 80000, 15000 if K < 2000 else 18000, seed=K, err=0.0002)
+    fa = str(tmp_path / "reads.fa")
+    R.write_fasta(reads, fa)
+    tab, log = both(tmp_path, fa, K, S, 6, env={"OATK_DEVICES": devices} if devices else None)
+    for f in SIX:
+        assert tab[f][0] >= 1 and tab[f][2] == 0, (f, tab[f], log[-2000:])
+    assert tab["scg_syncmer_consensus"][0] > 20 and tab["scg_syncmer_consensus"][2] == 0
+    assert tab["calc_syncmer_overlap"][0] > 20 and tab["calc_syncmer_overlap"][2] == 0
+
+
 def test_cli_without_ec_and_unzip(tmp_path):
     reads = A.hifi_like(260, 50000, 5000, seed=5)
     fa = str(tmp_path / "reads.fa")

@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 def device_consensus(hip, min_cov):
     hip.consensus(min_cov)
-    return {k: hip.fetch("CONS_" + k) for k in ("SEL", "SLOT", "RL", "MSEQ", "FIRST")}
+    return {k: hip.fetch("CONS_" + k) for k in ("SEL", "SLOT", "RL", "MSEQ", "FIRST", "TOT")}
 
 
 def compare_with_oracle(hip, reads, K, S, after_ec, min_cov, c_ec=4):
@@ -43,10 +43,12 @@ def compare_with_oracle(hip, reads, K, S, after_ec, min_cov, c_ec=4):
     assert np.array_equal(D["SLOT"], slot)
     view, keep = CU.make_view(sr)
     rl = D["RL"].reshape(len(want_sel), K)
+    dtot = D["TOT"].reshape(len(want_sel), K)
     n_long = 0
     for s_i, i in enumerate(want_sel.tolist()):
         tot, m, first = CU.oracle_rl(view, occ[int(occ_off[i]):int(occ_off[i + 1])], K)
         assert m == int(D["MSEQ"][s_i]) and first == int(D["FIRST"][s_i]), i
+        assert np.array_equal(dtot[s_i], tot), i
         if m:
             want = np.floor(tot.astype(np.float64) / m + 0.5).astype(np.uint32)        # lround of a non-negative quotient
             assert np.array_equal(rl[s_i], want), i

@@ -142,6 +142,11 @@ CASES = [
     (101, 11, 5, lambda: sample_reads(genome_with_repeats(9, 9000, unit=600, copies=3), 300, 1500, 0.004, 10)),
     # chains longer than a wave (about a hundred syncmers per read), mixed with short ones: the lane-serial walk beside the wave-per-read one
     (101, 11, 5, lambda: A.hifi_like(150, 20000, 6000, seed=463, err=0.003) + A.hifi_like(150, 20000, 1500, seed=467, err=0.003)),
+    # k above 1024 (ec_cap_c grows by 2 k: other LDS sizes of the classes and tiers); K None: oatk_hip_max_k(), read from the library in the test
+    # (errors rarer than above: a k-mer of several thousand bases must come through clean often enough to anchor the blocks)
+    (1501, 31, 6, lambda: A.hifi_like(150, 60000, 15000, seed=1501, err=0.0002)),
+    (2049, 21, 6, lambda: A.hifi_like(150, 80000, 18000, seed=2049, err=0.00015)),
+    (None, 31, 6, lambda: A.hifi_like(120, 120000, 22000, seed=4016, err=0.0001)),
 ]
 
 
@@ -152,6 +157,7 @@ def test_device_ec_matches_reference(hip, case, graph, monkeypatch):
     # budget -- and 4, 8 and 16 waves of ec_fused.hpp by the block's band, and these cases' blocks all fit one wave or four)
     monkeypatch.setenv("OATK_DEBUG_EC_FUSED_MIN_NW", graph[len("device-fused-nw"):] if graph.startswith("device-fused-nw") else "0")
     K, S, c, mk = CASES[case]
+    K = K or hip.L.oatk_hip_max_k()
     reads = mk()
     # tiny first tier: most blocks run in the classes behind it -- routed there by length and run beside the first tier, or left over by it.
     #   device-tiers[-serial]: the tiers of round 4 (one wave per block, larger LDS carve-ups, HBM slabs: OATK_DEBUG_EC_HEAVY=0)

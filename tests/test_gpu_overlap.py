@@ -82,6 +82,7 @@ def test_pair_tables_equal_the_walk_over_the_chains(hip, K, S, c, err, with_ec):
     (301, 21, 5, lambda: T.sample_reads(T.genome_with_repeats(7, 25000, unit=1500, copies=4), 320, 4000, 0.003, 8)),
     (1001, 31, 6, lambda: A.hifi_like(200, 40000, 9000, seed=1009, err=0.0005)),
     (101, 11, 5, lambda: T.sample_reads(T.genome_with_repeats(9, 9000, unit=600, copies=3), 300, 1500, 0.004, 10)),
+    T.CASES[8], T.CASES[9],                                 # k above 1024
 ])
 def test_unitig_consensus_served_from_the_device(hip, K, S, c, mk):
     """the reference builds its graph and unitigs on structs filled by the device; every unitig's sequence from oatk_scg_unitig_consensus

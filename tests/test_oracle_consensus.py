@@ -23,7 +23,7 @@ def check_all(db, scm, K, rng, n_pick=60):
         tot, m, first = CU.oracle_rl(view, sc["occ"][occ_off[i]:occ_off[i + 1]], K)
         n_rl += int(tot.sum() > 0)
         for rev in (0, 1):
-            for beg in (0, 1, 17, K // 2, K - 1, -3):
+            for beg in (0, 1, 17, K // 2, K - 1, -3) + ((1023, 1024, 1025) if K > 1024 else ()):
                 for hoco in (0, 1):
                     want = CU.reference_string(db, scm, i, rev, beg, hoco)
                     got = CU.oracle_string(view, tot, m, first, K, rev, beg, hoco)
@@ -32,10 +32,10 @@ def check_all(db, scm, K, rng, n_pick=60):
     return n_checked, n_rl
 
 
-@pytest.mark.parametrize("K,S", [(101, 11), (301, 21)])
+@pytest.mark.parametrize("K,S", [(101, 11), (301, 21), (1501, 31), (2049, 21), (4016, 31)])
 def test_consensus_oracle_matches_reference(K, S):
     rng = np.random.default_rng(K)
-    reads = CU.long_run_reads(K, K)
+    reads = CU.long_run_reads(K, K) if K <= 1024 else CU.late_run_reads(K, K)      # past 1024: runs beyond the 255 escape at late positions
     db = R.SrDb.from_reads(reads, K, S, threads=2)
     scm = R.ScmDb(db)
     assert int((db.flatten()["ho_rl"] == 255).sum()) > 0          # long runs are in play

@@ -10,9 +10,11 @@ import ref_lib as R
 pytestmark = pytest.mark.skipif(not R.available(), reason="oracle/_ref not built (needs /root/reference)")
 
 
-@pytest.mark.parametrize("K,S", [(1001, 31), (101, 11), (40, 8)])
+@pytest.mark.parametrize("K,S", [(1001, 31), (101, 11), (40, 8), (1501, 31), (2049, 21), (4016, 31)])
 def test_scan_and_count_side_by_side(K, S):
     reads = A.reads(K, S, seed=123, scale=0.4) + A.hifi_like(40, 20000 if K > 500 else 5000, 6000 if K > 500 else 1200, seed=K)
+    if K > 1024:                                            # reads whose hoco length is well above k
+        reads += A.hifi_like(40, 120000, 20000, seed=K + 1)
     o0 = O.scan(reads, K, S, 0)
     db = R.SrDb.from_reads(reads, K, S, threads=2)
     ref = db.flatten(n_nn=o0["n_nn"])
