@@ -98,8 +98,9 @@ int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist);
  *   EG_IDX_P u64[2 n_scm] (valid where EG_IDX_N > 0)   EG_IDX_N u32[2 n_scm]
  *   EG_ARC_V u64[n_arc]  EG_ARC_W u64[n_arc]  EG_ARC_LS u32[n_arc]  EG_ARC_COV u32[n_arc]  EG_ARC_COMP u8[n_arc] */
 int oatk_hip_ec_graph(oatk_hip_ctx *ctx);
-/* The LIGHT graph: all that read_error_correction (syncerr.c:819) asks of the graph when err_arc_c >= err_mer_c, as at its one call site
- * (run_syncasm.c:124 passes min_k_cov for both).  find_error_syncmers (:679-757) deletes every syncmer seen fewer than err_mer_c times and
+/* The LIGHT graph: all that read_error_correction (syncerr.c:819) asks of the graph when err_arc_c >= err_mer_c and max_err_c >= err_mer_c, as at
+ * its one call site (run_syncasm.c:124 passes min_k_cov for both and 10 min_k_cov).  find_error_syncmers (:679-757) deletes every syncmer seen
+ * fewer than err_mer_c times (below max_err_c: a syncmer seen max_err_c times or more is kept whatever its coverage, arcs and all) and
  * every arc that touches one; before that it asks of such an arc only that it exists (:699-706) -- it cannot be "good", an arc being seen at
  * most as often as its rarer end.  So only pairs between two syncmers with coverage >= err_mer_c are sorted into arcs, and the rest leave
  * one flag per oriented vertex.  Marks, corrected reads and refreshed table are identical to those from the full graph; the arc arrays

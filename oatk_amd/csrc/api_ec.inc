@@ -648,8 +648,8 @@ extern "C" int oatk_hip_ec_mark(oatk_hip_ctx *ctx, uint32_t err_mer_c, uint32_t 
     EcState *e = ctx->ec;
     e->done = false, e->marked = false, e->imp_used = 0;
     if (e->g_n_vtx != ec_n_vtx(ctx)) { ctx->err = "EC graph must have one vertex per syncmer"; return OATK_E_ARG; }
-    if (e->light_c && !(err_mer_c >= e->light_c && err_arc_c >= err_mer_c)) {
-        ctx->err = "the resident EC graph is a light one: it serves err_arc_c >= err_mer_c >= the coverage it was built for (oatk_hip_ec_graph_light)";
+    if (e->light_c && !(err_mer_c >= e->light_c && err_arc_c >= err_mer_c && max_err_c >= err_mer_c)) {
+        ctx->err = "the resident EC graph is a light one: it serves err_arc_c >= err_mer_c >= the coverage it was built for, and max_err_c >= err_mer_c (oatk_hip_ec_graph_light)";
         return OATK_E_ARG;
     }
     e->n_vtx = e->g_n_vtx;
@@ -952,9 +952,19 @@ static int ec_second_stage(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, con
     if (nh > (4u << 20)) longer[0] = nh;                               // (unsorted: sixteen waves for all)
     longer[narrowest] = nh;
     for (int i = 1; i <= narrowest; ++i) if (longer[i] < longer[i - 1]) longer[i] = longer[i - 1];
+    // A class whose carve-up does not fit LDS runs nothing (the sixteen waves below max_edist ~ 0.0075: ec_band_cap's 60 000 bases, DESIGN.md 8.3): its blocks are
+    // too long for the classes behind it and go straight on to the slab tier, ahead of what the launches leave over
+    unsigned long long passed = 0;
+    for (int i = 0; i <= narrowest; ++i) {
+        const uint64_t b0 = i? longer[i - 1] : 0, b1 = longer[i];
+        if (b1 <= b0 || lds[i] <= 64 * 1024) continue;
+        CK(hipMemcpyAsync(todo_out + passed, todo + b0, (b1 - b0) * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        passed += b1 - b0;
+    }
+    if (passed) CK(hipMemcpyAsync(cur + 1, &passed, 8, hipMemcpyHostToDevice, ctx->stream));     // (the stream is synchronised before `passed` goes)
+    if (passed && kn.stages) fprintf(stderr, "[ec stages] %llu blocks past a class that does not fit LDS\n", passed);
     auto launch = [&](int i, const uint32_t *list, uint64_t n, hipStream_t st) -> int {
         const int NW = NWS[i];
-        if (lds[i] > 64 * 1024) { ctx->err = "EC solver: the second stage's carve-up does not fit LDS (K too large)"; return OATK_E_STATE; }
         if (qslot >= 60) { ctx->err = "EC solver: more launches than work-queue counters (internal)"; return OATK_E_STATE; }
         EcwArgs a = fa[i];
         a.todo = list, a.n_todo = n, a.next = cur + qslot++, a.skip_l = 0x7FFFFFFF, a.batch = 1, a.arc_budget = 0;
@@ -992,7 +1002,7 @@ static int ec_second_stage(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, con
     bool used_low = false;
     for (int i = 0; i <= narrowest; ++i) {                             // the longest blocks first, each class on a side stream of its own ([4]: the single waves)
         const uint64_t b0 = i? longer[i - 1] : 0, b1 = longer[i];
-        if (b1 <= b0) continue;
+        if (b1 <= b0 || lds[i] > 64 * 1024) continue;
         const int s = NWS[i] == 1? 4 : used_aux;
         CK(hipStreamWaitEvent(e->aux[s], e->fork_ev, 0));
         { int rc = launch(i, todo + b0, b1 - b0, e->aux[s]); if (rc) return rc; }
@@ -1062,9 +1072,13 @@ static int ec_solve_classes(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, co
         return OATK_OK;
     };
     // 1. route by length, the classes of long blocks on streams of their own (longest first: they are the longest chains of dependent steps), the first tier beside them
+    //    A class whose carve-up does not fit LDS runs nothing (class 3 below max_edist ~ 0.0128: ec_band_cap's 60 000 bases, DESIGN.md 8.3): the blocks routed to it
+    //    go onto the second stage's list (routed[4] of them), which hands on to the slab tier what its own classes cannot hold
     EcRoute rt;
     for (int c = 0; c < 4; ++c) rt.list[c] = list[c], rt.cnt[c] = cur + c;
-    rt.cap[0] = T0.usable? T0.cap_t : 0, rt.cap[1] = H[1].routes? H[1].cap_t : 0, rt.cap[2] = H[2].routes? H[2].cap_t : 0, rt.cap[3] = 0x7FFFFFFF;
+    for (int c = 1; c < 4; ++c) if (!H[c].usable) rt.list[c] = list[4], rt.cnt[c] = cur + 4;
+    // (no first tier -- above max_edist ~ 0.049 class 1 holds fewer than its 3072 bases -- sends every block on: a cap of -1, as a trailing block can have 0 bases)
+    rt.cap[0] = T0.usable? T0.cap_t : -1, rt.cap[1] = H[1].routes? H[1].cap_t : 0, rt.cap[2] = H[2].routes? H[2].cap_t : 0, rt.cap[3] = 0x7FFFFFFF;
     unsigned long long routed[5] = {0, 0, 0, 0, 0}, cnts[5] = {0, 0, 0, 0, 0};
     if (n_work) { int rc = ec_route(ctx, e, n_work, rt, routed, sizeof(routed)); if (rc) return rc; }
     { int rc = ec_fork_side_streams(ctx, e); if (rc) return rc; }
@@ -1076,7 +1090,6 @@ static int ec_solve_classes(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, co
     int used_aux = 0;
     for (int c = 3; c >= 1; --c) {
         if (!routed[c]) continue;
-        if (!H[c].usable) { ctx->err = "EC solver: a class of the workgroup solver does not fit LDS (K too large)"; return OATK_E_STATE; }
         if (routed[c] > 1 && routed[c] <= (64u << 10)) {               // (the lists are small: thousands of blocks)
             int rc = ec_sort_longest_first(ctx, e, list[c], routed[c]); if (rc) return rc;
             CK(hipEventRecord(e->fork_ev, ctx->stream));
@@ -1105,11 +1118,11 @@ static int ec_solve_classes(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, co
     CK(hipMemcpyAsync(cnts, cur, sizeof(cnts), hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
     if (cnts[1] > routed[1]) { int rc = launch_class(1, list[1] + routed[1], cnts[1] - routed[1], ctx->stream); if (rc) return rc; }
-    n_big = cnts[1] + routed[2] + routed[3];
+    n_big = cnts[1] + routed[2] + routed[3] + routed[4];
     for (int i = 0; i < used_aux; ++i) CK(hipStreamWaitEvent(ctx->stream, e->aux_ev[i], 0));
     CK(hipMemcpyAsync(cnts, cur, sizeof(cnts), hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
-    if (kn.stages) fprintf(stderr, "[ec stages] first stage done: %llu blocks go on (classes got %llu + %llu + %llu)\n", cnts[4], cnts[1], routed[2], routed[3]);
+    if (kn.stages) fprintf(stderr, "[ec stages] first stage done: %llu blocks go on (classes got %llu + %llu + %llu; %llu past a class that does not fit LDS)\n", cnts[4], cnts[1], routed[2], routed[3], routed[4]);
     if (!cnts[4]) return OATK_OK;
     unsigned long long left = 0;
     { int rc = ec_second_stage(ctx, e, kn, base, list[4], cnts[4], list[1], qslot, hyb_k, left); if (rc) return rc; }
@@ -1142,6 +1155,7 @@ static int ec_solve_tiers(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, cons
     auto launch = [&](int tier, const uint32_t *todo, uint64_t n_todo, hipStream_t st, bool routed, uint64_t max_waves = 0) -> int {
         if (qslot >= 60) { ctx->err = "EC solver: more rounds of left-overs than queue counters (internal)"; return OATK_E_STATE; }
         unsigned long long *queue = cur + qslot++;
+        if (kn.stages) fprintf(stderr, "[ec stages] tier %d: %llu blocks%s\n", tier, (unsigned long long) (todo? n_todo : n_work), todo? (routed? " routed by length" : " left over") : "");
         if (tier == LAST) return ec_launch_slab_tier(ctx, e, base, max_hl, todo, n_todo, queue, st);
         const EcTier &t = T[tier];
         EcwArgs a = base;

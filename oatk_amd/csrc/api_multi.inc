@@ -942,7 +942,7 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
     const uint32_t first_me = (uint32_t) m->first_id[c->rank];
     const int nothing = ctx->n_occ == 0;            // a rank without syncmers corrects nothing and needs no k-mers
     if (n_imported) *n_imported = 0;
-    const bool light = err_mer_c > 0 && err_arc_c >= err_mer_c && !getenv("OATK_DEBUG_FULL_GRAPH");
+    const bool light = err_mer_c > 0 && err_arc_c >= err_mer_c && max_err_c >= err_mer_c && !getenv("OATK_DEBUG_FULL_GRAPH");
 
     // 0. coverage and s-mers over the global ids, as far as this rank will look: its own syncmers, and the candidates (seen >= err_mer_c times over
     //    all shards) that every owner announces -- a few thousand at HiFi error rates.  With thresholds the light graph cannot serve, everything.

@@ -155,7 +155,7 @@ class HipSyncasm:
     # ---- error correction (include/oatk_hip_ec.h) ----
     def ec_graph(self, light_c=0):
         """make_syncmer_graph(sr_db, scm_db, 0, 0.) + hoco arc overlaps on the device (run_syncasm.c:109-117); with light_c > 0 only what
-        read_error_correction(…, err_mer_c = light_c, …, err_arc_c >= err_mer_c, …) needs of it (include/oatk_hip_ec.h: the light graph)"""
+        read_error_correction(…, err_mer_c = light_c, max_err_c >= err_mer_c, err_arc_c >= err_mer_c, …) needs of it (include/oatk_hip_ec.h: the light graph)"""
         if light_c:
             self._check(self.L.oatk_hip_ec_graph_light(self.h, int(light_c)), "oatk_hip_ec_graph_light")
         else:

@@ -96,8 +96,9 @@ def oracle_update_db(n_scm, k_mer, m_pos, n_syncmers):
     return {"cov": cov, "del": de, "occ_off": occ_off, "occ": occ[:len(k_mer)]}
 
 
-def reference_ec(db, scm, g, max_edist, c, a, threads=2):
-    """read_error_correction of the compiled reference with syncasm's arguments (run_syncasm.c:124); returns its stderr summary"""
+def reference_ec(db, scm, g, max_edist, c, a, threads=2, max_err_c=None, err_arc_c=None):
+    """read_error_correction of the compiled reference with syncasm's arguments (run_syncasm.c:124: max_err_c = 10 c, err_arc_c = c unless
+    given); returns its stderr summary"""
     L = R.lib()
     fd, path = tempfile.mkstemp()
     os.close(fd)
@@ -105,7 +106,7 @@ def reference_ec(db, scm, g, max_edist, c, a, threads=2):
     f = os.open(path, os.O_WRONLY | os.O_TRUNC)
     os.dup2(f, 2)
     try:
-        L.refx_ec(db.handle, g, max_edist, c, c * 10, c, a, threads)
+        L.refx_ec(db.handle, g, max_edist, c, c * 10 if max_err_c is None else max_err_c, c if err_arc_c is None else err_arc_c, a, threads)
     finally:
         os.dup2(saved, 2)
         os.close(f)

@@ -18,14 +18,14 @@ pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not U.available(), reason="ora
 SIX = ("sr_read", "sr_db_stat", "collect_syncmer_from_reads", "make_syncmer_graph", "read_error_correction", "scg_read_alignment")
 
 
-def both(tmp_path, files, k, s, c, extra=(), threads=4, env=None):
+def both(tmp_path, files, k, s, c, extra=(), threads=4, env=None, min_final=100):
     ref, dev = str(tmp_path / "ref"), str(tmp_path / "dev")
     U.run_cli(U.CLI_REF, files, ref, k, c, threads, extra=["-s", str(s)] + list(extra))
     e = {"OATK_DROPIN_LOG": "1"}
     e.update(env or {})
     _, err = U.run_cli(U.CLI_DROPIN, files, dev, k, c, threads, env=e, extra=["-s", str(s)] + list(extra))
     for suffix in (".utg.gfa", ".utg.final.gfa"):
-        assert os.path.getsize(ref + suffix) > 100, suffix
+        assert os.path.getsize(ref + suffix) > (100 if suffix == ".utg.gfa" else min_final), suffix
         assert filecmp.cmp(ref + suffix, dev + suffix, shallow=False), suffix
     return U.served_table(err), err
 
@@ -54,6 +54,24 @@ def test_cli_above_k1024(tmp_path, K, S, devices):
         assert tab[f][0] >= 1 and tab[f][2] == 0, (f, tab[f], log[-2000:])
     assert tab["scg_syncmer_consensus"][0] > 20 and tab["scg_syncmer_consensus"][2] == 0
     assert tab["calc_syncmer_overlap"][0] > 20 and tab["calc_syncmer_overlap"][2] == 0
+
+
+@pytest.mark.parametrize("c,extra,devices", [(6, ["-a", "0"], None), (6, ["-a", "0.5"], None), (6, ["-a", "1"], None), (1, [], None), (2, [], None),
+                                             (6, ["-a", "0.5"], "0,0"), (2, [], "0,0")])
+def test_cli_other_arc_fraction_and_coverage(tmp_path, c, extra, devices):
+    """-a (max_arc_f of the error marks and of the assembly graph) and -c below 3, on one handle and on two: the reference's bytes, every call served
+    by the device"""
+    reads = A.hifi_like(200, 40000, 5000, seed=401 + c, err=0.001)
+    fa = str(tmp_path / "reads.fa")
+    R.write_fasta(reads, fa)
+    # (-a 1 keeps only arcs seen as often as their rarer end: the final graph is all but empty, and still the reference's bytes)
+    a1 = extra == ["-a", "1"]
+    tab, log = both(tmp_path, fa, 301, 21, c, extra=extra, env={"OATK_DEVICES": devices} if devices else None, min_final=0 if a1 else 100)
+    for f in SIX:
+        if a1 and f == "scg_read_alignment":       # (-a 1: the final graph has no syncmer left, and the original aligns the reads to nothing)
+            assert "the graph carries no syncmer index" in log
+            continue
+        assert tab[f][0] >= 1 and tab[f][2] == 0, (f, tab[f], log[-2000:])
 
 
 def test_cli_without_ec_and_unzip(tmp_path):

@@ -26,21 +26,23 @@ CASES = [
     # three shards, one of them empty; four shards
     (101, 11, 5, lambda: E.sample_reads(E.genome_with_repeats(9, 9000, unit=600, copies=3), 300, 1500, 0.004, 10), (0.0, 0.4, 0.4, 1.0)),
     (301, 21, 6, lambda: A.hifi_like(300, 30000, 4000, seed=311, err=0.003), (0.0, 0.2, 0.5, 0.7, 1.0)),
+    # other thresholds than syncasm's defaults: c = 2, max_arc_f = 0.5 (a sixth entry: max_arc_f, 0.35 where it is missing)
+    (301, 21, 2, lambda: A.hifi_like(300, 30000, 4000, seed=313, err=0.003), (0.0, 0.5, 1.0), 0.5),
 ]
 
 
-def single(hip, reads, K, S, c):
+def single(hip, reads, K, S, c, a=0.35):
     seq, off, lens = pack_reads(reads)
     hip.scan_host(seq, off, lens, K, S)
     hip.count()
     cnt = hip.fetch_count()
     hip.ec_graph()
-    st = hip.ec(0.02, c, 0.35)
+    st = hip.ec(0.02, c, a)
     want = {k: hip.fetch(k) for k in ["EC_N_SCM", "EC_KMER", "EC_MPOS", "EC_SMER", "EC_SCM_COV", "EC_SCM_DEL"]}
     return cnt, st, want
 
 
-def run_ranks(world, make_comm, reads, bounds, K, S, c, mask=None, devices=None):
+def run_ranks(world, make_comm, reads, bounds, K, S, c, mask=None, devices=None, a=0.35):
     out, errs = [None] * world, []
 
     def work(rank):
@@ -57,7 +59,7 @@ def run_ranks(world, make_comm, reads, bounds, K, S, c, mask=None, devices=None)
             merged = {k: h.fetch(k) for k in ("MG_H", "MG_S", "MG_COV", "MG_L2G", "MG_LCOV")}
             merged["range"] = h.multi_range()
             local_h = h.fetch("SCM_H")
-            st, n_imp = h.ec_sharded(comm, 0.02, c, 0.35)
+            st, n_imp = h.ec_sharded(comm, 0.02, c, a)
             res = {k: h.fetch(k) for k in ("EC_N_SCM", "EC_KMER", "EC_MPOS", "EC_SMER", "MG_EC_COV", "MG_EC_DEL")}
             out[rank] = (ng, merged, local_h, st, n_imp, res)
             _lib.load().oatk_comm_destroy(comm)
@@ -82,7 +84,8 @@ def test_sharded_through_the_c_collectives_equals_one_handle(hip, case, graph, m
     full: every pair of every shard travels (any thresholds)"""
     if graph == "full":
         monkeypatch.setenv("OATK_DEBUG_FULL_GRAPH", "1")
-    K, S, c, mk, frac = CASES[case]
+    K, S, c, mk, frac = CASES[case][:5]
+    a = CASES[case][5] if len(CASES[case]) > 5 else 0.35
     reads = mk()
     bounds = [int(round(f * len(reads))) for f in frac]
     world = len(bounds) - 1
@@ -90,10 +93,10 @@ def test_sharded_through_the_c_collectives_equals_one_handle(hip, case, graph, m
     grp = L.oatk_comm_group_create(world)
     assert grp
     try:
-        out = run_ranks(world, lambda r: L.oatk_comm_group_rank(grp, r), reads, bounds, K, S, c)
+        out = run_ranks(world, lambda r: L.oatk_comm_group_rank(grp, r), reads, bounds, K, S, c, a=a)
     finally:
         L.oatk_comm_group_destroy(grp)
-    cnt, st, want = single(hip, reads, K, S, c)
+    cnt, st, want = single(hip, reads, K, S, c, a)
     order = np.argsort(cnt["h"], kind="stable")         # the merged table is in hash order; one handle numbers syncmers the same way
     assert np.array_equal(order, np.arange(len(order)))
     first = 0
