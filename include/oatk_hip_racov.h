@@ -1,0 +1,70 @@
+/*
+ * include/oatk_hip_racov.h -- C ABI of the coverage estimates from read alignments on the device: scg_ra_utg_coverage (syncasm.c:1882-2065,
+ * with make_ma_block / find_lcs :1652-1878 and the EM over the multiple-alignment blocks) and the duplet sums of scg_ra_arc_coverage
+ * (:2067-2138, before its refinement).  Results are the reference's doubles before its (uint32_t) casts; the host adaptor
+ * (include/oatk_syncasm.h: oatk_scg_ra_utg_coverage / oatk_scg_ra_arc_coverage) writes them into the graph.
+ *
+ * The alignments are the resident ones of the last oatk_hip_read_alignment (aln == NULL) or uploaded; the reads' chains are the resident
+ * batch's (reads == NULL; after oatk_hip_ec: the corrected chains) or uploaded.  The graph is passed in, flattened, HOST pointers.
+ */
+#ifndef OATK_HIP_RACOV_H
+#define OATK_HIP_RACOV_H
+
+#include "oatk_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct {
+    uint64_t n_scm, n_utg, n_arc;
+    const uint64_t *su_off;    /* [n_scm + 1] scg->idx_u as offsets (as in oatk_ra_graph_t)                                         */
+    const uint64_t *su_uid;    /* [su_off[n_scm]] unitig << 1 | strand                                                             */
+    const uint32_t *su_pos;    /*                 position on the unitig                                                           */
+    const uint32_t *scm_cov;   /* [n_scm] syncmer_t.cov                                                                            */
+    const uint64_t *utg_off;   /* [n_utg + 1] offsets of the unitigs' syncmer lists; utg_off[i + 1] - utg_off[i] = vtx[i].n         */
+    const uint64_t *utg_a;     /* [utg_off[n_utg]] vtx[].a back to back                                                            */
+    const uint64_t *idx_p;     /* [2 n_utg] asmg_t.idx_p / idx_n (arc coverage only; may be NULL for the unitig coverage)          */
+    const uint64_t *idx_n;
+    const uint64_t *arc_v;     /* [n_arc] asmg_arc_t.v, .w, .link_id, .comp, .del in array order (arc coverage only)                */
+    const uint64_t *arc_w;
+    const uint64_t *arc_link;
+    const uint8_t *arc_comp;
+    const uint8_t *arc_del;
+} oatk_racov_graph_t;
+
+/* uploaded alignments: scg_ra_v flattened in its order (sid = index of the read's chain) */
+typedef struct {
+    uint64_t n_aln, n_frg;
+    const uint32_t *sid;       /* [n_aln]                                                                                           */
+    const uint64_t *off;       /* [n_aln + 1] fragments of alignment i                                                             */
+    const double *s;           /* [n_aln]                                                                                           */
+    const uint64_t *uid;       /* [n_frg] ra_frg_t.uid, u_beg, u_end, s_beg, s_end                                                 */
+    const uint32_t *u_beg, *u_end, *s_beg, *s_end;
+} oatk_racov_aln_t;
+
+/* uploaded chains: the reads' k_mer arrays back to back (syncmer id << 1 | flag) */
+typedef struct {
+    uint64_t n_reads;
+    const uint64_t *off;       /* [n_reads + 1]                                                                                     */
+    const uint64_t *k_mer;
+} oatk_racov_reads_t;
+
+/* utg_cov[n_utg]: avg_covs after the third round and MAX(1., .) (:2040-2044); *n_iter: the `i` of the EM's "ended at iteration" line.
+ * verbose > 2 prints the reference's EM lines to stderr.  With no alignment nothing is written (the caller prints the reference's warning).
+ * OATK_E_SPLIT: make_ma_block's LCS matrices of this input would take more than the working limit (oatk_hip_debug_racov_cap); nothing is
+ * written and the caller runs the original.  OATK_E_ARG: an alignment that does not fit the graph (the reference would read out of bounds). */
+int oatk_hip_ra_utg_coverage(oatk_hip_ctx *ctx, const oatk_racov_graph_t *g, const oatk_racov_reads_t *reads, const oatk_racov_aln_t *aln,
+                             int verbose, double *utg_cov, uint64_t *n_iter);
+
+/* arc_cov[n_arc]: for every arc that is not deleted, the spanning-duplet sum of its key link_id << 1 | comp, 0 when it has none
+ * (:2131-2137 before the (uint32_t)); deleted arcs get 0.  OATK_E_ARG when two consecutive fragments have no arc (asmg_arc == NULL). */
+int oatk_hip_ra_arc_coverage(oatk_hip_ctx *ctx, const oatk_racov_graph_t *g, const oatk_racov_aln_t *aln, double *arc_cov);
+
+/* Test hook: the most LCS-matrix cells (4 bytes each) the unitig coverage may hold at once, over all reads; 0 = default (2^31, 8 GiB). */
+int oatk_hip_debug_racov_cap(oatk_hip_ctx *ctx, uint64_t cells);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -226,6 +226,17 @@ typedef struct { size_t n, m; oatk_scg_ra_t *a; } oatk_scg_ra_v;
 int oatk_scg_read_alignment(oatk_hip_ctx *ctx, oatk_sr_db_t *sr_db, oatk_scg_ra_v *ra_v, oatk_scg_t *g, int for_unzip, uint64_t *n_skipped,
                             uint32_t **skipped);
 
+/* scg_ra_utg_coverage (syncasm.c:1882-2065) and scg_ra_arc_coverage up to its refinement (:2067-2138) on the device
+ * (include/oatk_hip_racov.h): vtx[].cov / arc[].cov of g->utg_asmg as the reference leaves them; the arc caller then runs the reference's
+ * scg_refine_arc_coverage(g, verbose) or asmg_arc_fix_cov(g->utg_asmg) itself.  With OATK_RACOV_RESIDENT_READS the
+ * caller vouches that sr_db is the batch resident in ctx (the chains are not uploaded); with OATK_RACOV_RESIDENT_ALN that ra_v is what
+ * oatk_scg_read_alignment wrote last on ctx, unchanged (the alignments are not uploaded).  Returns an OATK_* code; nothing is written
+ * unless it is OATK_OK (OATK_E_SPLIT: over the device's working limit -- run the original).  The unitig call with no alignment prints the
+ * reference's warning and changes nothing, like the reference. */
+enum { OATK_RACOV_RESIDENT_READS = 1, OATK_RACOV_RESIDENT_ALN = 2 };
+int oatk_scg_ra_utg_coverage(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, const oatk_scg_ra_v *ra_v, oatk_scg_t *g, unsigned flags, int verbose);
+int oatk_scg_ra_arc_coverage(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, const oatk_scg_ra_v *ra_v, oatk_scg_t *g, unsigned flags, int verbose);
+
 /* same destructors as the reference (syncmer.c:1047-1110) for objects that are not handed to it */
 void oatk_sr_db_clean(oatk_sr_db_t *sr_db);
 

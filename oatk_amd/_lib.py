@@ -52,6 +52,7 @@ EXPORTS = [
     "oatk_hip_ec_set_global", "oatk_hip_ec_pairs", "oatk_hip_ec_graph_from_pairs", "oatk_hip_ec_graph_from_segments", "oatk_hip_ec_export_kmers", "oatk_hip_ec_import_kmers",
     "oatk_hip_ec_reserve_import", "oatk_hip_consensus", "oatk_hip_consensus_ids", "oatk_hip_ingest", "oatk_hip_ingest_host", "oatk_hip_scan_ingested", "oatk_hip_stat", "oatk_hip_stat_keys", "oatk_hip_stat_from_keys",
     "oatk_hip_asm_graph", "oatk_hip_asm_pairs", "oatk_hip_asm_graph_from_pairs", "oatk_hip_overlap_hist", "oatk_hip_overlap_pairs", "oatk_hip_overlap_hist_from_pairs", "oatk_hip_read_alignment", "oatk_hip_debug_align_two_pass",
+    "oatk_hip_ra_utg_coverage", "oatk_hip_ra_arc_coverage", "oatk_hip_debug_racov_cap",
 ]
 
 
@@ -65,6 +66,24 @@ class RaGraph(C.Structure):
     """oatk_ra_graph_t (include/oatk_hip_align.h): what scg_read_alignment reads from scg_t, flattened, host pointers"""
     _fields_ = [("n_scm", C.c_uint64), ("n_utg", C.c_uint64), ("n_arc", C.c_uint64), ("su_off", C.c_void_p), ("su_uid", C.c_void_p), ("su_pos", C.c_void_p),
                 ("utg_n", C.c_void_p), ("idx_p", C.c_void_p), ("idx_n", C.c_void_p), ("arc_w", C.c_void_p), ("arc_ln", C.c_void_p), ("arc_del", C.c_void_p)]
+
+
+class RacovGraph(C.Structure):
+    """oatk_racov_graph_t (include/oatk_hip_racov.h): what scg_ra_utg_coverage / scg_ra_arc_coverage read from scg_t, flattened, host pointers"""
+    _fields_ = [("n_scm", C.c_uint64), ("n_utg", C.c_uint64), ("n_arc", C.c_uint64), ("su_off", C.c_void_p), ("su_uid", C.c_void_p), ("su_pos", C.c_void_p),
+                ("scm_cov", C.c_void_p), ("utg_off", C.c_void_p), ("utg_a", C.c_void_p), ("idx_p", C.c_void_p), ("idx_n", C.c_void_p), ("arc_v", C.c_void_p),
+                ("arc_w", C.c_void_p), ("arc_link", C.c_void_p), ("arc_comp", C.c_void_p), ("arc_del", C.c_void_p)]
+
+
+class RacovAln(C.Structure):
+    """oatk_racov_aln_t: scg_ra_v flattened"""
+    _fields_ = [("n_aln", C.c_uint64), ("n_frg", C.c_uint64), ("sid", C.c_void_p), ("off", C.c_void_p), ("s", C.c_void_p), ("uid", C.c_void_p),
+                ("u_beg", C.c_void_p), ("u_end", C.c_void_p), ("s_beg", C.c_void_p), ("s_end", C.c_void_p)]
+
+
+class RacovReads(C.Structure):
+    """oatk_racov_reads_t: the reads' chains back to back"""
+    _fields_ = [("n_reads", C.c_uint64), ("off", C.c_void_p), ("k_mer", C.c_void_p)]
 
 
 class StatRaw(C.Structure):
@@ -179,6 +198,9 @@ def load():
     L.oatk_hip_stat_from_keys.argtypes = [vp, vp, vp, C.c_uint64, vp, C.POINTER(StatRaw)]
     L.oatk_hip_debug_align_two_pass.argtypes = [vp, C.c_int]
     L.oatk_hip_read_alignment.argtypes = [vp, C.POINTER(RaGraph), vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
+    L.oatk_hip_ra_utg_coverage.argtypes = [vp, C.POINTER(RacovGraph), C.POINTER(RacovReads), C.POINTER(RacovAln), C.c_int, vp, C.POINTER(C.c_uint64)]
+    L.oatk_hip_ra_arc_coverage.argtypes = [vp, C.POINTER(RacovGraph), C.POINTER(RacovAln), vp]
+    L.oatk_hip_debug_racov_cap.argtypes = [vp, C.c_uint64]
     L.oatk_hip_overlap_pairs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.oatk_hip_overlap_hist_from_pairs.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.oatk_hip_overlap_hist.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

@@ -383,6 +383,7 @@ struct oatk_hip_ctx {
     struct AgState *ag = nullptr;       // assembly graph buffers (api_graph.inc)
     struct OvlState *ovl = nullptr;     // pair-distance tables (api_ovl.inc)
     struct RaState *ra = nullptr;       // read alignment buffers (api_align.inc)
+    struct RcState *rc = nullptr;       // coverage from read alignments (api_racov.inc)
     struct MultiState *multi = nullptr; // merged table / sharded correction (api_multi.inc)
 };
 
@@ -440,6 +441,7 @@ static void t_collect(oatk_hip_ctx *ctx, int first, int last)
 #include "api_cons.inc"
 #include "api_ovl.inc"
 #include "api_align.inc"
+#include "api_racov.inc"
 #include "api_ingest.inc"
 #include "api_stat.inc"
 #include "api_multi.inc"
@@ -504,6 +506,7 @@ void oatk_hip_destroy(oatk_hip_ctx *ctx)
     ag_state_free(ctx);
     ovl_state_free(ctx);
     ra_state_free(ctx);
+    rc_state_free(ctx);
     multi_state_free(ctx);
     for (int i = 0; i <= OATK_T_COUNT_; ++i) {
         (void) hipEventDestroy(ctx->ev[i][0]);

@@ -1,0 +1,175 @@
+/*
+ * oatk_amd/csrc/host/racov_host.c -- host side of scg_ra_utg_coverage (syncasm.c:1882-2065) and of scg_ra_arc_coverage up to its
+ * refinement (:2067-2138) on the device (include/oatk_hip_racov.h).
+ *
+ * Flattens what the two functions read from the reference's scg_t -- the syncmer -> unitig index, the syncmers' cov, the unitigs' syncmer
+ * lists and the arcs with their index -- and, unless the caller vouches that they are the handle's own (flags), the alignments and the
+ * reads' chains; then writes vtx[].cov / arc[].cov through the layout mirrors, with the reference's (uint32_t) casts into the 30-bit
+ * fields.  The arc caller finishes with the reference's own scg_refine_arc_coverage or asmg_arc_fix_cov.
+ * Nothing is written unless the device call succeeds: on OATK_E_SPLIT the caller runs the original.
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "oatk_hip_racov.h"
+#include "oatk_syncasm.h"
+
+typedef unsigned __int128 u128_t;
+
+typedef struct {
+    oatk_racov_graph_t g;
+    uint64_t *su_off, *su_uid, *utg_off, *utg_a, *arc_v, *arc_w, *arc_link;
+    uint32_t *su_pos, *scm_cov;
+    uint8_t *arc_comp, *arc_del;
+} rc_graph_t;
+
+static void *rc_malloc(size_t n)
+{
+    void *p = malloc(n? n : 1);
+    if (!p) { fprintf(stderr, "[E::%s] out of memory\n", __func__); exit(EXIT_FAILURE); }
+    return p;
+}
+
+static void rc_graph_flatten(const oatk_scg_t *g, int with_arcs, rc_graph_t *f)
+{
+    const oatk_asmg_t *ug = g->utg_asmg;
+    const uint64_t ns = g->scm_db->n, nu = ug->n_vtx, na = ug->n_arc;
+    const u128_t *su0 = (const u128_t *) g->idx_u[0];
+    const uint64_t nsu = (uint64_t) ((const u128_t *) g->idx_u[ns] - su0);
+    uint64_t i, m = 0;
+    memset(f, 0, sizeof(*f));
+    f->su_off = (uint64_t *) rc_malloc(8 * (ns + 1)), f->su_uid = (uint64_t *) rc_malloc(8 * nsu), f->su_pos = (uint32_t *) rc_malloc(4 * nsu);
+    for (i = 0; i <= ns; ++i) f->su_off[i] = (uint64_t) ((const u128_t *) g->idx_u[i] - su0);
+    for (i = 0; i < nsu; ++i) {
+        const u128_t x = su0[i];
+        f->su_uid[i] = (uint64_t) ((x >> 36) & 0x3FFFFFFFFFFULL) << 1 | (uint64_t) ((x >> 78) & 1);       /* scm_utg_uid, scm_utg_rev */
+        f->su_pos[i] = (uint32_t) (x & 0xFFFFFFFFFULL);                                                   /* scm_utg_pos */
+    }
+    f->scm_cov = (uint32_t *) rc_malloc(4 * ns);
+    for (i = 0; i < ns; ++i) f->scm_cov[i] = g->scm_db->a[i].cov;
+    f->utg_off = (uint64_t *) rc_malloc(8 * (nu + 1));
+    for (i = 0; i < nu; ++i) f->utg_off[i] = m, m += ug->vtx[i].n;
+    f->utg_off[nu] = m;
+    f->utg_a = (uint64_t *) rc_malloc(8 * m);
+    for (i = 0; i < nu; ++i) if (ug->vtx[i].n) memcpy(f->utg_a + f->utg_off[i], ug->vtx[i].a, 8 * ug->vtx[i].n);
+    f->g.n_scm = ns, f->g.n_utg = nu, f->g.su_off = f->su_off, f->g.su_uid = f->su_uid, f->g.su_pos = f->su_pos, f->g.scm_cov = f->scm_cov;
+    f->g.utg_off = f->utg_off, f->g.utg_a = f->utg_a;
+    if (!with_arcs) return;
+    f->arc_v = (uint64_t *) rc_malloc(8 * na), f->arc_w = (uint64_t *) rc_malloc(8 * na), f->arc_link = (uint64_t *) rc_malloc(8 * na);
+    f->arc_comp = (uint8_t *) rc_malloc(na), f->arc_del = (uint8_t *) rc_malloc(na);
+    for (i = 0; i < na; ++i) {
+        const oatk_asmg_arc_t *a = &ug->arc[i];
+        f->arc_v[i] = a->v, f->arc_w[i] = a->w, f->arc_link[i] = a->link_id, f->arc_comp[i] = a->comp, f->arc_del[i] = a->del;
+    }
+    f->g.n_arc = na, f->g.idx_p = ug->idx_p, f->g.idx_n = ug->idx_n;
+    f->g.arc_v = f->arc_v, f->g.arc_w = f->arc_w, f->g.arc_link = f->arc_link, f->g.arc_comp = f->arc_comp, f->g.arc_del = f->arc_del;
+}
+
+static void rc_graph_free(rc_graph_t *f)
+{
+    free(f->su_off); free(f->su_uid); free(f->su_pos); free(f->scm_cov); free(f->utg_off); free(f->utg_a);
+    free(f->arc_v); free(f->arc_w); free(f->arc_link); free(f->arc_comp); free(f->arc_del);
+}
+
+typedef struct {
+    oatk_racov_aln_t a;
+    uint32_t *sid, *ub, *ue, *sb, *se;
+    uint64_t *off, *uid;
+    double *s;
+} rc_aln_t;
+
+/* scg_ra_v flattened; -1 when a value does not fit the device's 32-bit fields or a sid is not a read of sr_db */
+static int rc_aln_flatten(const oatk_scg_ra_v *v, uint64_t n_reads, rc_aln_t *f)
+{
+    uint64_t i, j, nf = 0;
+    memset(f, 0, sizeof(*f));
+    for (i = 0; i < v->n; ++i) nf += v->a[i].n;
+    f->sid = (uint32_t *) rc_malloc(4 * v->n), f->off = (uint64_t *) rc_malloc(8 * (v->n + 1)), f->s = (double *) rc_malloc(8 * v->n);
+    f->uid = (uint64_t *) rc_malloc(8 * nf), f->ub = (uint32_t *) rc_malloc(4 * nf), f->ue = (uint32_t *) rc_malloc(4 * nf);
+    f->sb = (uint32_t *) rc_malloc(4 * nf), f->se = (uint32_t *) rc_malloc(4 * nf);
+    for (i = 0, nf = 0; i < v->n; ++i) {
+        const oatk_scg_ra_t *r = &v->a[i];
+        if (r->sid >= n_reads) return -1;
+        f->sid[i] = (uint32_t) r->sid, f->off[i] = nf, f->s[i] = r->s;
+        for (j = 0; j < r->n; ++j, ++nf) {
+            const oatk_ra_frg_t *x = &r->a[j];
+            if (x->u_beg >> 32 || x->u_end >> 32) return -1;
+            f->uid[nf] = x->uid, f->ub[nf] = (uint32_t) x->u_beg, f->ue[nf] = (uint32_t) x->u_end, f->sb[nf] = x->s_beg, f->se[nf] = x->s_end;
+        }
+    }
+    f->off[v->n] = nf;
+    f->a.n_aln = v->n, f->a.n_frg = nf, f->a.sid = f->sid, f->a.off = f->off, f->a.s = f->s;
+    f->a.uid = f->uid, f->a.u_beg = f->ub, f->a.u_end = f->ue, f->a.s_beg = f->sb, f->a.s_end = f->se;
+    return 0;
+}
+
+static void rc_aln_free(rc_aln_t *f)
+{
+    free(f->sid); free(f->off); free(f->s); free(f->uid); free(f->ub); free(f->ue); free(f->sb); free(f->se);
+}
+
+int oatk_scg_ra_utg_coverage(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, const oatk_scg_ra_v *ra_v, oatk_scg_t *g, unsigned flags, int verbose)
+{
+    uint64_t i, n_iter = 0;
+    int rc;
+    if (!ctx) return OATK_E_NODEV;
+    if (ra_v->n == 0) {                                                            /* :1884-1887 */
+        fprintf(stderr, "[W::%s] no read alignment, unitig coverage estimation skipped\n", "scg_ra_utg_coverage");
+        return OATK_OK;
+    }
+    oatk_asmg_t *ug = g->utg_asmg;
+    rc_graph_t fg;
+    rc_aln_t fa;
+    oatk_racov_reads_t rd = {0, 0, 0};
+    uint64_t *r_off = 0, *r_k = 0;
+    rc_graph_flatten(g, 0, &fg);
+    memset(&fa, 0, sizeof(fa));
+    if (!(flags & OATK_RACOV_RESIDENT_ALN) && rc_aln_flatten(ra_v, sr_db->n, &fa)) { rc = OATK_E_ARG; goto done; }
+    if (!(flags & OATK_RACOV_RESIDENT_READS)) {
+        uint64_t m = 0;
+        r_off = (uint64_t *) rc_malloc(8 * (sr_db->n + 1));
+        for (i = 0; i < sr_db->n; ++i) r_off[i] = m, m += sr_db->a[i].n;
+        r_off[sr_db->n] = m;
+        r_k = (uint64_t *) rc_malloc(8 * m);
+        for (i = 0; i < sr_db->n; ++i) if (sr_db->a[i].n) memcpy(r_k + r_off[i], sr_db->a[i].k_mer, 8 * sr_db->a[i].n);
+        rd.n_reads = sr_db->n, rd.off = r_off, rd.k_mer = r_k;
+    }
+    {
+        double *cov = (double *) rc_malloc(8 * ug->n_vtx);
+        rc = oatk_hip_ra_utg_coverage(ctx, &fg.g, (flags & OATK_RACOV_RESIDENT_READS)? 0 : &rd, (flags & OATK_RACOV_RESIDENT_ALN)? 0 : &fa.a, verbose, cov, &n_iter);
+        if (rc == OATK_OK)
+            for (i = 0; i < ug->n_vtx; ++i) ug->vtx[i].cov = (uint32_t) cov[i];      /* :2055-2056 */
+        free(cov);
+    }
+done:
+    rc_graph_free(&fg);
+    rc_aln_free(&fa);
+    free(r_off); free(r_k);
+    return rc;
+}
+
+int oatk_scg_ra_arc_coverage(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, const oatk_scg_ra_v *ra_v, oatk_scg_t *g, unsigned flags, int verbose)
+{
+    uint64_t i;
+    int rc;
+    (void) verbose;
+    if (!ctx) return OATK_E_NODEV;
+    oatk_asmg_t *ug = g->utg_asmg;
+    rc_graph_t fg;
+    rc_aln_t fa;
+    rc_graph_flatten(g, 1, &fg);
+    memset(&fa, 0, sizeof(fa));
+    if (!(flags & OATK_RACOV_RESIDENT_ALN) && rc_aln_flatten(ra_v, sr_db? sr_db->n : UINT64_MAX, &fa)) { rc = OATK_E_ARG; goto done; }
+    {
+        double *cov = (double *) rc_malloc(8 * ug->n_arc);
+        rc = oatk_hip_ra_arc_coverage(ctx, &fg.g, (flags & OATK_RACOV_RESIDENT_ALN)? 0 : &fa.a, cov);
+        if (rc == OATK_OK)
+            for (i = 0; i < ug->n_arc; ++i) if (!ug->arc[i].del) ug->arc[i].cov = (uint32_t) cov[i];      /* :2131-2138 */
+        free(cov);
+    }
+done:
+    rc_graph_free(&fg);
+    rc_aln_free(&fa);
+    return rc;
+}

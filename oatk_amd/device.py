@@ -338,6 +338,47 @@ class HipSyncasm:
                     "oatk_hip_read_alignment")
         return int(na.value), int(nf.value), st
 
+    _RACOV_GRAPH = (("su_off", np.uint64), ("su_uid", np.uint64), ("su_pos", np.uint32), ("scm_cov", np.uint32), ("utg_off", np.uint64), ("utg_a", np.uint64),
+                    ("idx_p", np.uint64), ("idx_n", np.uint64), ("arc_v", np.uint64), ("arc_w", np.uint64), ("arc_link", np.uint64), ("arc_comp", np.uint8),
+                    ("arc_del", np.uint8))
+    _RACOV_ALN = (("sid", np.uint32), ("off", np.uint64), ("s", np.float64), ("uid", np.uint64), ("u_beg", np.uint32), ("u_end", np.uint32),
+                  ("s_beg", np.uint32), ("s_end", np.uint32))
+
+    def _racov_graph(self, graph):
+        keep = {k: np.ascontiguousarray(graph.get(k, np.zeros(0)), dtype=dt) for k, dt in self._RACOV_GRAPH}
+        g = _lib.RacovGraph(int(graph["n_scm"]), len(keep["utg_off"]) - 1, len(keep["arc_w"]), *[keep[k].ctypes.data for k, _ in self._RACOV_GRAPH])
+        return g, keep
+
+    def _racov_aln(self, aln):
+        if aln is None:
+            return None, None
+        keep = {k: np.ascontiguousarray(aln[k], dtype=dt) for k, dt in self._RACOV_ALN}
+        return _lib.RacovAln(len(keep["sid"]), len(keep["uid"]), *[keep[k].ctypes.data for k, _ in self._RACOV_ALN]), keep
+
+    def ra_utg_coverage(self, graph, aln=None, chains=None, verbose=0):
+        """scg_ra_utg_coverage (syncasm.c:1882) against a graph given as a dict shaped like oatk_racov_graph_t (utg_off / utg_a: the unitigs'
+        syncmer lists back to back).  aln: a dict of flat alignments (sid, off, s, uid, u_beg, u_end, s_beg, s_end), None = the resident ones of
+        the last read_alignment; chains: (off, k_mer), None = the resident batch's.  Returns (avg_covs as float64, EM iteration count)."""
+        g, keep_g = self._racov_graph(graph)
+        a, keep_a = self._racov_aln(aln)
+        r = None
+        if chains is not None:
+            keep_r = [np.ascontiguousarray(chains[0], dtype=np.uint64), np.ascontiguousarray(chains[1], dtype=np.uint64)]
+            r = _lib.RacovReads(len(keep_r[0]) - 1, keep_r[0].ctypes.data, keep_r[1].ctypes.data)
+        out = np.zeros(max(g.n_utg, 1), np.float64)
+        it = C.c_uint64(0)
+        self._check(self.L.oatk_hip_ra_utg_coverage(self.h, C.byref(g), None if r is None else C.byref(r), None if a is None else C.byref(a), verbose,
+                                                    out.ctypes.data, C.byref(it)), "oatk_hip_ra_utg_coverage")
+        return out[:g.n_utg], int(it.value)
+
+    def ra_arc_coverage(self, graph, aln=None):
+        """the duplet sums of scg_ra_arc_coverage (syncasm.c:2067-2137) before its (uint32_t) and refinement, per arc (0 for deleted arcs)"""
+        g, keep_g = self._racov_graph(graph)
+        a, keep_a = self._racov_aln(aln)
+        out = np.zeros(max(g.n_arc, 1), np.float64)
+        self._check(self.L.oatk_hip_ra_arc_coverage(self.h, C.byref(g), None if a is None else C.byref(a), out.ctypes.data), "oatk_hip_ra_arc_coverage")
+        return out[:g.n_arc]
+
     def overlap_hist(self):
         """pair-distance tables of every adjacent syncmer pair (calc_syncmer_overlap's tabulation, syncasm.c:477-556); returns (n_pairs, n_entries)"""
         np_, ne = C.c_uint64(), C.c_uint64()
