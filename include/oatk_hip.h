@@ -150,11 +150,11 @@ enum {
     OATK_T_HPC = 0,        /* kernel A: homopolymer compression + pack (scan_hpc.hpp)       */
     OATK_T_SYNCMER,        /* kernel B, reads without ambiguous bases (scan_syncmer.hpp)   */
     OATK_T_SYNCMER_N,      /* kernel B, reads with ambiguous bases                         */
-    OATK_T_SCAN_POST,      /* list sorts + per-read prefix                                 */
-    OATK_T_COUNT_PLACE,    /* place_records                                                */
+    OATK_T_SCAN_POST,      /* list sorts + per-read prefix (the placement is under OATK_T_KMER_HASH) */
+    OATK_T_COUNT_PLACE,    /* kept for the ABI; reads 0: the k-mer hash kernel places the records */
     OATK_T_COUNT_SORT,     /* radix sort by hash                                           */
     OATK_T_COUNT_GROUP,    /* heads + collision verification + ids + finish                */
-    OATK_T_KMER_HASH,      /* MurmurHash64A of every syncmer's k-mer (kmer_hash.hpp)       */
+    OATK_T_KMER_HASH,      /* MurmurHash64A of every syncmer's k-mer + the record to its slot: per-read arrays, sort key, slot record (kmer_hash.hpp) */
     OATK_T_EC_GRAPH,       /* oatk_hip_ec_graph: adjacent pairs, sort, arcs, overlaps      */
     OATK_T_EC_MARK,        /* find_error_syncmers + live arcs + block lists                */
     OATK_T_EC_SOLVE,       /* the path search of every error block, all tiers (ec_wave.hpp) */

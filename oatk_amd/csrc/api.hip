@@ -358,12 +358,14 @@ struct oatk_hip_ctx {
     uint64_t n_reads = 0, seq_bytes = 0, sid0 = 0;
     int K = 0, S = 0;
     bool scanned = false, counted = false;
+    bool slots_packed = false;    // slot_rec holds the batch's slot records (the scan's k-mer hash kernel wrote them); a batch assembled from pieces has none until oatk_hip_count packs them.
+                                  // A slot record is made of pos_lo / pos_smer / pos_mpos and d_off[read] >> 4: whatever writes one of those arrays or moves d_off must clear the flag
+                                  // (today oatk_hip_scan and oatk_hip_scan_append, both through scan_reset_downstream)
 
     // scan outputs
     DevBuf hoco_l, n_scm, n_nn, n_lrl, ho_rl, hoco_s, nbits;
     DevBuf nn_key, lrl_key, lrl_val, nn_key2, lrl_key2, lrl_val2;
-    DevBuf rec_hash, rec_lo, rec_smer, rec_mpos;
-    DevBuf raw_lo, raw_smer, raw_mpos, shard_cnt, shard_prefix;   // sharded append regions (scan_syncmer.hpp)
+    DevBuf raw_lo, raw_smer, raw_mpos, shard_cnt;   // sharded append regions (scan_syncmer.hpp)
     uint32_t region_cap = 0;
     DevBuf counters;      // u32[4]
     uint32_t nn_cap = 0, lrl_cap = 0;
@@ -493,7 +495,7 @@ void oatk_hip_destroy(oatk_hip_ctx *ctx)
     (void) hipStreamSynchronize(ctx->stream);
     DevBuf *all[] = {&ctx->in_seq, &ctx->in_off, &ctx->in_len, &ctx->hoco_l, &ctx->n_scm, &ctx->n_nn, &ctx->n_lrl, &ctx->ho_rl,
                      &ctx->hoco_s, &ctx->nbits, &ctx->nn_key, &ctx->lrl_key, &ctx->lrl_val, &ctx->nn_key2, &ctx->lrl_key2,
-                     &ctx->lrl_val2, &ctx->rec_hash, &ctx->rec_lo, &ctx->rec_smer, &ctx->rec_mpos, &ctx->raw_lo, &ctx->raw_smer, &ctx->raw_mpos, &ctx->shard_cnt, &ctx->shard_prefix, &ctx->counters, &ctx->n_scm64,
+                     &ctx->lrl_val2, &ctx->raw_lo, &ctx->raw_smer, &ctx->raw_mpos, &ctx->shard_cnt, &ctx->counters, &ctx->n_scm64,
                      &ctx->scm_off, &ctx->pos_hash, &ctx->pos_lo, &ctx->pos_smer, &ctx->pos_mpos, &ctx->pos_kid, &ctx->key_hash,
                      &ctx->key_sorted, &ctx->iota, &ctx->perm, &ctx->head, &ctx->head_idx, &ctx->newclus, &ctx->clus_id, &ctx->kloc, &ctx->smer_sorted, &ctx->slot_rec, &ctx->scm_loc,
                      &ctx->bad_head, &ctx->tag, &ctx->tmp_perm, &ctx->flags, &ctx->scm_h, &ctx->scm_s, &ctx->scm_cov,
@@ -701,9 +703,9 @@ int oatk_hip_scan(oatk_hip_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_off
         uint64_t guess = (seq_bytes / 256 + 1024) / NSH + 256;
         if (ctx->region_cap < guess) ctx->region_cap = (uint32_t) guess;
     }
-    ENSURE(shard_cnt, NSH * 4); ENSURE(shard_prefix, NSH * 8);
+    ENSURE(shard_cnt, NSH * 4);
     uint32_t sc[oatk::OATK_REC_SHARDS];
-    uint64_t spfx[oatk::OATK_REC_SHARDS];
+    uint32_t sc_max = 0;                               // records of the fullest shard
 
     for (;;) {
         const size_t raw_n = (size_t) ctx->region_cap * NSH;
@@ -722,7 +724,8 @@ int oatk_hip_scan(oatk_hip_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_off
         if (c[1] > ctx->lrl_cap) ctx->lrl_cap = c[1] + c[1] / 4, again = true;
         uint64_t tot = 0;
         uint32_t mx = 0;
-        for (uint32_t i = 0; i < NSH; ++i) { spfx[i] = tot; tot += sc[i]; if (sc[i] > mx) mx = sc[i]; }
+        for (uint32_t i = 0; i < NSH; ++i) { tot += sc[i]; if (sc[i] > mx) mx = sc[i]; }
+        sc_max = mx;
         if (mx > ctx->region_cap) ctx->region_cap = mx + mx / 4 + 16, again = true;
         if (tot > 0xFFFFFFF0ULL) { ctx->err = "more than 2^32 syncmer occurrences in one batch"; return OATK_E_ARG; }
         ctx->tot_nn = c[0], ctx->tot_lrl = c[1], ctx->n_occ = tot;
@@ -731,33 +734,9 @@ int oatk_hip_scan(oatk_hip_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_off
         // a partial pass may have left ambiguity bits behind: restore the all-zero invariant
         CK(hipMemsetAsync(ctx->nbits.p, 0, ctx->nbits.cap, ctx->stream));
     }
-    // shard regions -> dense record arrays
-    if (ctx->n_occ) {
-        ENSURE(rec_hash, (size_t) ctx->n_occ * 8); ENSURE(rec_lo, (size_t) ctx->n_occ * 8);
-        ENSURE(rec_smer, (size_t) ctx->n_occ * 8); ENSURE(rec_mpos, (size_t) ctx->n_occ * 4);
-        CK(hipMemcpyAsync(ctx->shard_prefix.p, spfx, sizeof(spfx), hipMemcpyHostToDevice, ctx->stream));
-        oatk::CompactArgs ca;
-        ca.raw_lo = ctx->raw_lo.as<uint64_t>(), ca.raw_smer = ctx->raw_smer.as<uint64_t>(), ca.raw_mpos = ctx->raw_mpos.as<uint32_t>();
-        ca.shard_cnt = ctx->shard_cnt.as<uint32_t>(), ca.shard_prefix = ctx->shard_prefix.as<uint64_t>(), ca.region_cap = ctx->region_cap;
-        ca.rec_lo = ctx->rec_lo.as<uint64_t>(), ca.rec_smer = ctx->rec_smer.as<uint64_t>(), ca.rec_mpos = ctx->rec_mpos.as<uint32_t>();
-        hipLaunchKernelGGL(oatk::compact_records_kernel, dim3(NSH), dim3(256), 0, ctx->stream, ca);
-        CK(hipStreamSynchronize(ctx->stream));     // spfx lives on this stack frame
-    }
     if (ctx->timing) t_collect(ctx, OATK_T_HPC, OATK_T_SYNCMER_N);
 
-    // ---- k-mer hashes of all records, one lane per syncmer (kmer_hash.hpp) ----
-    if (ctx->n_occ) {
-        oatk::KmerHashArgs kh;
-        kh.hoco_s = ctx->hoco_s.as<uint8_t>(), kh.off = ctx->d_off, kh.sid0 = ctx->sid0;
-        kh.rec_lo = ctx->rec_lo.as<uint64_t>(), kh.rec_mpos = ctx->rec_mpos.as<uint32_t>(), kh.rec_hash = ctx->rec_hash.as<uint64_t>();
-        kh.n_rec = (uint32_t) ctx->n_occ, kh.K = ctx->K;
-        const int nw = ((ctx->K - 1) / 4 + 1 + 7) / 8;
-        t_begin(ctx, OATK_T_KMER_HASH);
-        hipLaunchKernelGGL(oatk::kmer_hash_kernel, dim3((unsigned) ((ctx->n_occ + KMH_REC - 1) / KMH_REC)), dim3(64), (size_t) KMH_REC * (nw + 1) * 8, ctx->stream, kh);
-        t_end(ctx, OATK_T_KMER_HASH);
-    }
-
-    // ---- post: order the rare-event lists, per-read slot offsets ----
+    // ---- post: order the rare-event lists, per-read slot offsets (kernel B's per-read counts are all they need) ----
     t_begin(ctx, OATK_T_SCAN_POST);
     ctx->nn_sorted_in_2 = ctx->lrl_sorted_in_2 = false;
     if (ctx->tot_nn > 1) {
@@ -787,29 +766,37 @@ int oatk_hip_scan(oatk_hip_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_off
         CK(rocprim::exclusive_scan(ctx->tmp.p, tb, ctx->n_scm64.as<uint64_t>(), ctx->scm_off.as<uint64_t>(), (uint64_t) 0, n_reads + 1,
                                    rocprim::plus<uint64_t>(), ctx->stream));
     }
-    // records -> per-read slots (also the low-key order the count needs)
+    t_end(ctx, OATK_T_SCAN_POST);
+
+    // ---- k-mer hashes of all records, and every record to its slot scm_off[read] + ordinal (kmer_hash.hpp): the per-read arrays, the sort's
+    //      key and value (also the low-key order the count needs) and the slot records of the count's gathers, straight from the shard regions ----
     {
-        using namespace oatk;
         size_t n = ctx->n_occ? ctx->n_occ : 1;
         ENSURE(pos_hash, n * 8); ENSURE(pos_lo, n * 8); ENSURE(pos_smer, n * 8); ENSURE(pos_mpos, n * 4);
-        ENSURE(key_hash, n * 8); ENSURE(iota, n * 4);
-        if (ctx->n_occ) {
-            PlaceArgs p;
-            p.rec_hash = ctx->rec_hash.as<uint64_t>(), p.rec_lo = ctx->rec_lo.as<uint64_t>(), p.rec_smer = ctx->rec_smer.as<uint64_t>();
-            p.rec_mpos = ctx->rec_mpos.as<uint32_t>(), p.n_rec = (uint32_t) ctx->n_occ, p.sid0 = ctx->sid0;
-            p.scm_off = ctx->scm_off.as<uint64_t>(), p.hash_mask = ctx->hash_mask;
-            p.pos_hash = ctx->pos_hash.as<uint64_t>(), p.pos_lo = ctx->pos_lo.as<uint64_t>(), p.pos_smer = ctx->pos_smer.as<uint64_t>();
-            p.pos_mpos = ctx->pos_mpos.as<uint32_t>(), p.key_hash = ctx->key_hash.as<uint64_t>(), p.iota = ctx->iota.as<uint32_t>();
-            t_begin(ctx, OATK_T_COUNT_PLACE);
-            hipLaunchKernelGGL(place_records_kernel, dim3((unsigned) ((ctx->n_occ + 255) / 256)), dim3(256), 0, ctx->stream, p);
-            t_end(ctx, OATK_T_COUNT_PLACE);
-        }
+        ENSURE(key_hash, n * 8); ENSURE(iota, n * 4); ENSURE(slot_rec, n * 32);
     }
-    t_end(ctx, OATK_T_SCAN_POST);
+    if (ctx->n_occ) {
+        oatk::KmerHashArgs kh;
+        kh.hoco_s = ctx->hoco_s.as<uint8_t>(), kh.off = ctx->d_off, kh.sid0 = ctx->sid0;
+        kh.raw_lo = ctx->raw_lo.as<uint64_t>(), kh.raw_smer = ctx->raw_smer.as<uint64_t>(), kh.raw_mpos = ctx->raw_mpos.as<uint32_t>();
+        kh.shard_cnt = ctx->shard_cnt.as<uint32_t>(), kh.region_cap = ctx->region_cap;
+        kh.scm_off = ctx->scm_off.as<uint64_t>(), kh.hash_mask = ctx->hash_mask;
+        kh.pos_hash = ctx->pos_hash.as<uint64_t>(), kh.pos_lo = ctx->pos_lo.as<uint64_t>(), kh.pos_smer = ctx->pos_smer.as<uint64_t>();
+        kh.pos_mpos = ctx->pos_mpos.as<uint32_t>(), kh.key_hash = ctx->key_hash.as<uint64_t>(), kh.iota = ctx->iota.as<uint32_t>();
+        kh.slot_rec = ctx->slot_rec.as<uint4>(), kh.K = ctx->K;
+        const int nw = ((ctx->K - 1) / 4 + 1 + 7) / 8;
+        // grid.y = the shard, grid.x cut for the fullest one: blocks past their shard's count return at once.  Reads are dealt to the shards round-robin, so at
+        // any size worth timing the shards are even (config 3: within a few per cent); a small or lopsided batch launches mostly empty blocks, which cost it nothing
+        // that matters (1024 x a few blocks).  A dense index through a prefix of the counts would need that prefix on the device first.
+        t_begin(ctx, OATK_T_KMER_HASH);
+        hipLaunchKernelGGL(oatk::kmer_hash_kernel, dim3((sc_max + KMH_REC - 1) / KMH_REC, NSH), dim3(64), (size_t) KMH_REC * (nw + 1) * 8, ctx->stream, kh);
+        t_end(ctx, OATK_T_KMER_HASH);
+    }
     CK(hipGetLastError());
     CK(hipStreamSynchronize(ctx->stream));
     if (ctx->timing) { t_collect(ctx, OATK_T_SCAN_POST, OATK_T_COUNT_PLACE); t_collect(ctx, OATK_T_KMER_HASH, OATK_T_KMER_HASH); }
     ctx->scanned = true;
+    ctx->slots_packed = ctx->n_occ != 0;
     return OATK_OK;
 }
 
@@ -828,6 +815,7 @@ __global__ void append_iota_kernel(uint32_t *iota, uint64_t first, uint64_t n)
 static void scan_reset_downstream(oatk_hip_ctx *ctx)
 {
     ctx->scanned = ctx->counted = false;
+    ctx->slots_packed = false;                 // (an append changes the per-slot arrays under the slot records)
     if (ctx->ec) ctx->ec->done = ctx->ec->marked = ctx->ec->graph_resident = ctx->ec->global = false;
     if (ctx->cons) ctx->cons->done = false;
     if (ctx->ag) ctx->ag->done = false;
@@ -1020,12 +1008,17 @@ sort_again:
     g.flags = ctx->flags.as<uint32_t>();
     ENSURE(slot_rec, n * 32);
     g.slot_rec = ctx->slot_rec.as<uint4>();
-    hipLaunchKernelGGL(pack_slots_kernel, dim3(nb), dim3(256), 0, ctx->stream, g);
-    hipLaunchKernelGGL(pair_sum_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->key_hash.as<uint64_t>(), (const uint32_t *) nullptr, (uint32_t) n, ctx->flags.as<uint32_t>(), 8);
-    hipLaunchKernelGGL(pair_sum_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->key_sorted.as<uint64_t>(), ctx->perm.as<uint32_t>(), (uint32_t) n, ctx->flags.as<uint32_t>(), 12);
+    if (!ctx->slots_packed) {                  // a batch assembled from pieces: the scan's hash kernel wrote them otherwise
+        hipLaunchKernelGGL(pack_slots_kernel, dim3(nb), dim3(256), 0, ctx->stream, g);
+        ctx->slots_packed = true;
+    }
+    hipLaunchKernelGGL((pair_sum_kernel<false>), dim3(2048), dim3(256), 0, ctx->stream, ctx->key_hash.as<uint64_t>(), (const uint32_t *) nullptr, (uint32_t) n, ctx->flags.as<uint32_t>(), 8,
+                       (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr);
     // Optimistic order (round 4): heads -> ids -> ONE pass through the permutation (the verification's gathers + the table's and the reads' ids) -> verification.
     // A hash group with two k-mers (never seen outside the forced-collision tests) takes the pessimistic order afterwards: split, gather again, ids again, write again.
-    hipLaunchKernelGGL(heads_only_kernel, dim3(nb), dim3(256), 0, ctx->stream, g);
+    // (the pass over the sorted keys that checks the sort also marks the heads)
+    hipLaunchKernelGGL((pair_sum_kernel<true>), dim3(2048), dim3(256), 0, ctx->stream, ctx->key_sorted.as<uint64_t>(), ctx->perm.as<uint32_t>(), (uint32_t) n, ctx->flags.as<uint32_t>(), 12,
+                       g.head, g.newclus, g.head_idx);
     {   // head_idx := index of the latest head at or before i
         size_t tb = 0;
         CK(rocprim::inclusive_scan(nullptr, tb, ctx->head_idx.as<uint32_t>(), ctx->head_idx.as<uint32_t>(), n, rocprim::maximum<uint32_t>(), ctx->stream));
@@ -1045,7 +1038,7 @@ sort_again:
         n_scm = last_id;                    // inclusive scan: last value = number of clusters
         ENSURE(scm_h, (size_t) n_scm * 8); ENSURE(scm_s, (size_t) n_scm * 8); ENSURE(scm_cov, (size_t) n_scm * 4); ENSURE(scm_loc, (size_t) n_scm * 8);
         ENSURE(scm_occ_off, ((size_t) n_scm + 1) * 8);
-        f.perm = ctx->perm.as<uint32_t>(), f.newclus = ctx->newclus.as<uint32_t>(), f.clus_id = ctx->clus_id.as<uint32_t>(), f.n_rec = (uint32_t) n;
+        f.perm = ctx->perm.as<uint32_t>(), f.newclus = ctx->newclus.as<uint32_t>(), f.clus_id1 = ctx->clus_id.as<uint32_t>(), f.n_rec = (uint32_t) n;
         f.sorted_key = ctx->key_sorted.as<uint64_t>(), f.smer_sorted = ctx->smer_sorted.as<uint64_t>();
         f.loc = ctx->kloc.as<uint64_t>(), f.scm_loc = ctx->scm_loc.as<uint64_t>();
         f.scm_h = ctx->scm_h.as<uint64_t>(), f.scm_s = ctx->scm_s.as<uint64_t>(), f.scm_occ_off = ctx->scm_occ_off.as<uint64_t>();
@@ -1056,8 +1049,7 @@ sort_again:
     hipLaunchKernelGGL(gather_finish_kernel, dim3(nb), dim3(256), 0, ctx->stream, g, f, ctx->clus_id.as<uint32_t>(), n_scm);
     CK(hipMemsetAsync(ctx->bad_head.p, 0, n * 4, ctx->stream));
     hipLaunchKernelGGL(verify_group_kernel, dim3((unsigned) ((n + 8 * OATK_VG_STRIP - 1) / (8 * OATK_VG_STRIP))), dim3(256), 0, ctx->stream, g, ctx->bad_head.as<uint32_t>());
-    // clus_id holds id + 1: shift in place (check_smer_kernel and the collision path read ids)
-    CK(rocprim::transform(ctx->clus_id.as<uint32_t>(), ctx->clus_id.as<uint32_t>(), n, [] __device__(uint32_t v) { return v - 1u; }, ctx->stream));
+    // (clus_id holds id + 1, and every reader takes it so)
     uint32_t fl[16];
     CK(hipMemcpyAsync(fl, ctx->flags.p, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
@@ -1080,7 +1072,6 @@ sort_again:
                            ctx->tag.as<uint32_t>(), ctx->tmp_perm.as<uint32_t>());
         hipLaunchKernelGGL(regather_kernel, dim3(nb), dim3(256), 0, ctx->stream, g);
         { int rc = ids(); if (rc) return rc; }
-        CK(rocprim::transform(ctx->clus_id.as<uint32_t>(), ctx->clus_id.as<uint32_t>(), n, [] __device__(uint32_t v) { return v - 1u; }, ctx->stream));
         hipLaunchKernelGGL(finish_heads_kernel, dim3(nb), dim3(256), 0, ctx->stream, f, n_scm);
     }
     hipLaunchKernelGGL(check_smer_kernel, dim3(nb), dim3(256), 0, ctx->stream, f);

@@ -1187,8 +1187,8 @@ static int ec_solve_tiers(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, cons
     // 1. route by length (one pass over the work items), then the LDS tiers side by side.  A long block is a long chain of dependent steps and
     //    its tier's carve-up lets few waves onto a CU, so run after the first tier the larger tiers are a tail of mostly idle CUs (0.8 ms for
     //    86 blocks at config 2; 4 waves per CU for 4 ms at config 3).  Run BESIDE it they must not crowd it out either: a larger tier starts
-    //    first with a small share of every CU's LDS (a wave per CU, a wave per two CUs), the first tier fills the rest, and when that is
-    //    done a second launch of each larger tier, as wide as it likes, helps empty the same queue.
+    //    first with a small share of every CU's LDS (a wave per CU, a wave per two CUs) and the first tier fills the rest.  Each larger tier
+    //    is launched ONCE, with a wave of its own for every block routed to it (the second tier capped at two waves per CU).
     EcRoute rt;
     for (int t = 0; t <= LAST; ++t) rt.cap[t] = T[t].usable? T[t].cap_t : 0, rt.list[t] = list[t], rt.cnt[t] = cur + t;
     rt.cap[LAST] = 0x7FFFFFFF;

@@ -112,6 +112,14 @@ __device__ __forceinline__ uint64_t murmur_mix_word(uint64_t w)
     return w;
 }
 
+// A value that is the same in every active lane, moved to a scalar register (only right where it IS the same: the first active lane's is taken).
+__device__ __forceinline__ int32_t wave_uniform(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+// Lane `lane`'s v as a scalar, for a `lane` that is the same in every active lane: one v_readlane.  (__shfl with such an index is a ds_bpermute,
+// a wait on LDS and a v_readfirstlane.)
+__device__ __forceinline__ uint32_t wave_read(uint32_t v, int lane) { return (uint32_t) __builtin_amdgcn_readlane((int32_t) v, wave_uniform(lane)); }
+// The value of the lane below (lane 0 keeps its own, as __shfl_up(v, 1) has it) by a DPP wave shift, without LDS; every lane of the wave must be active.
+__device__ __forceinline__ uint32_t wave_prev(uint32_t v) { return (uint32_t) __builtin_amdgcn_update_dpp((int32_t) v, (int32_t) v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false); }
+
 // inclusive wave scan (sum) over 64 lanes
 __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v, int lane)
 {

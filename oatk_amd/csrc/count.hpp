@@ -3,9 +3,10 @@
 // Replaces `collect_syncmer_from_reads` + `process_kmer_cluster` (syncmer.c:1397-1451, :1270-1393).
 // The reference sorts 128-bit (hash, sid<<32|idx<<1|rev) records, walks equal-hash groups, splits true
 // 64-bit collisions by comparing the k-mer sequences, and hands out dense IDs in that order.  Here:
-//   1. place_records: scan records are unordered but carry (sid, ordinal), and the per-read counts are
+//   1. placement: scan records are unordered but carry (sid, ordinal), and the per-read counts are
 //      known, so each record has an exact slot scm_off[read] + ordinal.  Scattering them there yields the
-//      per-read arrays (m_pos, s_mer, hash) AND a sequence already ordered by the low 64 key bits.
+//      per-read arrays (m_pos, s_mer, hash) AND a sequence already ordered by the low 64 key bits.  The
+//      scan's k-mer hash kernel does it as it finishes a record (kmer_hash.hpp).
 //   2. one stable 64-bit radix sort of (hash -> slot) finishes the 128-bit order.
 //   3. mark_heads / verify_group: equal-hash neighbours are compared base-for-base with their group head
 //      (one wave per record, one 32-base word per lane) -- the collision check the reference performs.
@@ -17,57 +18,6 @@
 #include "common.hpp"
 
 namespace oatk {
-
-// shard regions -> dense record arrays (shard i's records land at prefix[i] ...)
-struct CompactArgs {
-    const uint64_t *raw_lo, *raw_smer;
-    const uint32_t *raw_mpos;
-    const uint32_t *shard_cnt;
-    const uint64_t *shard_prefix;
-    uint32_t region_cap;
-    uint64_t *rec_lo, *rec_smer;
-    uint32_t *rec_mpos;
-};
-
-__global__ __launch_bounds__(256) void compact_records_kernel(CompactArgs a)
-{
-    const uint32_t sh = blockIdx.x, n = a.shard_cnt[sh];
-    const size_t src = (size_t) sh * a.region_cap;
-    const uint64_t dst = a.shard_prefix[sh];
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-        a.rec_lo[dst + i] = a.raw_lo[src + i];
-        a.rec_smer[dst + i] = a.raw_smer[src + i];
-        a.rec_mpos[dst + i] = a.raw_mpos[src + i];
-    }
-}
-
-struct PlaceArgs {
-    const uint64_t *rec_hash, *rec_lo, *rec_smer;
-    const uint32_t *rec_mpos;
-    uint32_t n_rec;
-    uint64_t sid0;
-    const uint64_t *scm_off;      // exclusive prefix of n_scm over reads
-    uint64_t hash_mask;           // debug knob (tests force collisions); ~0 in production
-    uint64_t *pos_hash, *pos_lo, *pos_smer;
-    uint32_t *pos_mpos;
-    uint64_t *key_hash;           // masked copy used as the sort key
-    uint32_t *iota;
-};
-
-__global__ void place_records_kernel(PlaceArgs a)
-{
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n_rec) return;
-    uint64_t lo = a.rec_lo[i];
-    uint64_t rd = (lo >> 32) - a.sid0;
-    uint64_t p = a.scm_off[rd] + ((uint32_t) lo >> 1);
-    a.pos_hash[p] = a.rec_hash[i];
-    a.key_hash[p] = a.rec_hash[i] & a.hash_mask;
-    a.pos_lo[p] = lo;
-    a.pos_smer[p] = a.rec_smer[i];
-    a.pos_mpos[p] = a.rec_mpos[i];
-    a.iota[p] = (uint32_t) p;
-}
 
 // 32 oriented k-mer bases [32*wd, 32*wd+32) MSB-first, zero beyond K, straight from the hoco string in HBM
 __device__ __forceinline__ uint64_t kmer_word_global(const uint32_t *hs32, uint32_t pos, uint32_t rev, int K, int wd)
@@ -113,12 +63,13 @@ struct GroupArgs {
     // and the s-mer of every sorted record -- finish_heads and check_smer then read them in order instead of gathering them again
     const uint64_t *pos_smer;
     uint64_t *occ_sorted, *smer_sorted;
-    // ... and fetched as ONE 32-byte record per slot (pack_slots_kernel): occurrence word, s-mer, k-mer locator.  Three arrays indexed by the same
+    // ... and fetched as ONE 32-byte record per slot (kmer_hash_kernel; pack_slots_kernel for a batch assembled from pieces): occurrence word, s-mer, k-mer locator.  Three arrays indexed by the same
     // random slot cost three 64-byte fetches and the locator a fourth, dependent one (the read's offset); packed side by side in slot order -- a
     // streaming pass -- they cost one
     uint4 *slot_rec;
 };
 
+// (only for per-slot arrays that did not come out of kmer_hash_kernel, which writes the same records: oatk_hip_scan_append)
 __global__ void pack_slots_kernel(GroupArgs a)
 {
     uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -191,8 +142,15 @@ __device__ __forceinline__ void pair_sums(uint64_t key, uint32_t slot, uint64_t 
     x *= 0xD6E8FEB86659FD93ULL; x ^= x >> 29; x += key;
     s1 = x;
 }
-// perm == nullptr: the pairs are (key[i], i) -- the sort's input; otherwise (key[i], perm[i]) and the keys are checked to ascend
-__global__ __launch_bounds__(256) void pair_sum_kernel(const uint64_t *key, const uint32_t *perm, uint32_t n, uint32_t *flags, int at)
+// perm == nullptr: the pairs are (key[i], i) -- the sort's input; otherwise (key[i], perm[i]) and the keys are checked to ascend.
+// HEADS (the sort's output only): the pass that compares every sorted key with the one in front of it also says where an equal-hash group starts -- head,
+// newclus and head_idx as the optimistic order wants them (round 4: with the ids known from a scan of these flags BEFORE the verification -- on the
+// assumption, checked afterwards, that no hash group holds two k-mers -- one pass through the permutation both gathers what verify_group needs and writes
+// what finish_heads_kernel wrote in a second pass (gather_finish_kernel); a collision falls back to the two passes below).  The three arrays are only
+// touched when HEADS is set.
+template <bool HEADS>
+__global__ __launch_bounds__(256) void pair_sum_kernel(const uint64_t *key, const uint32_t *perm, uint32_t n, uint32_t *flags, int at,
+                                                       uint32_t *head, uint32_t *newclus, uint32_t *head_idx)
 {
     __shared__ uint64_t part[2][4];
     uint64_t s0 = 0, s1 = 0;
@@ -215,6 +173,10 @@ __global__ __launch_bounds__(256) void pair_sum_kernel(const uint64_t *key, cons
             pair_sums(k[u], v[u], a, b);
             s0 += a, s1 += b;
             if (k[u] < kp[u]) inv = true;
+            if (HEADS) {
+                const uint32_t i = (uint32_t) (i0 + u * stride), h = i == 0 || k[u] != kp[u];
+                head[i] = h, newclus[i] = h, head_idx[i] = h? i : 0u;
+            }
         }
     }
     #pragma unroll
@@ -226,19 +188,6 @@ __global__ __launch_bounds__(256) void pair_sum_kernel(const uint64_t *key, cons
         atomicAdd((unsigned long long *) (flags + at), (unsigned long long) (part[0][0] + part[0][1] + part[0][2] + part[0][3]));
         atomicAdd((unsigned long long *) (flags + at + 2), (unsigned long long) (part[1][0] + part[1][1] + part[1][2] + part[1][3]));
     }
-}
-
-// round 4: the heads alone (sorted keys only).  With the ids known from a scan of these flags BEFORE the verification -- on the assumption, checked
-// afterwards, that no hash group holds two k-mers -- one pass through the permutation both gathers what verify_group needs and writes what
-// finish_heads_kernel wrote in a second pass (gather_finish_kernel); a collision falls back to the two passes below.
-__global__ void heads_only_kernel(GroupArgs a)
-{
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n_rec) return;
-    const uint32_t h = i == 0 || a.sorted_key[i] != a.sorted_key[i - 1];
-    a.head[i] = h;
-    a.newclus[i] = h;
-    a.head_idx[i] = h? i : 0u;
 }
 
 __global__ void mark_heads_kernel(GroupArgs a)
@@ -386,7 +335,7 @@ __global__ void split_collisions_kernel(GroupArgs a, const uint32_t *bad_head, u
 struct FinishArgs {
     const uint32_t *perm;
     const uint32_t *newclus;
-    const uint32_t *clus_id;      // inclusive scan of newclus, minus one
+    const uint32_t *clus_id1;     // inclusive scan of newclus: id + 1
     uint32_t n_rec;
     const uint64_t *sorted_key, *smer_sorted;     // smer_sorted: the s-mer of every sorted record (mark_heads_kernel)
     uint64_t *scm_h, *scm_s;
@@ -402,7 +351,7 @@ __global__ void finish_heads_kernel(FinishArgs a, uint32_t n_scm)
 {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_rec) return;
-    uint32_t p = a.perm[i], id = a.clus_id[i];
+    uint32_t p = a.perm[i], id = a.clus_id1[i] - 1u;
     a.pos_kid[p] = (uint64_t) id << 1;
     if (a.newclus[i]) {
         a.scm_h[id] = a.sorted_key[i];
@@ -438,7 +387,7 @@ __global__ void check_smer_kernel(FinishArgs a)
 {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_rec) return;
-    uint32_t id = a.clus_id[i];
+    uint32_t id = a.clus_id1[i] - 1u;
     if (a.smer_sorted[i] != a.scm_s[id]) a.flags[1] = 1u;
 }
 

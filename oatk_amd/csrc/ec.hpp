@@ -256,14 +256,20 @@ struct EcAssembleArgs {
 // instead of one lane striding through its own read.  Four kernels use it -- block count, block list, and the two passes of the chain
 // assembly -- and the lane-per-read versions above remain for reads with more than 64 syncmers (lane 0 runs them).
 // ---------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t ecr_u32(uint32_t v, int lane) { return (uint32_t) __builtin_amdgcn_readfirstlane((int32_t) __shfl((int32_t) v, lane)); }
+// entry `lane` of v, in a scalar register: `lane` is the same in every active lane of the wave wherever these are called, so it goes to an SGPR and v_readlane
+// takes the value (a __shfl is a ds_bpermute, a wait on LDS and a v_readfirstlane -- inside the walk's serial loop)
+__device__ __forceinline__ int32_t ecr_s(int32_t v) { return wave_uniform(v); }
+__device__ __forceinline__ uint32_t ecr_u32(uint32_t v, int lane) { return wave_read(v, lane); }
 __device__ __forceinline__ uint64_t ecr_u64(uint64_t v, int lane) { return (uint64_t) ecr_u32((uint32_t) (v >> 32), lane) << 32 | ecr_u32((uint32_t) v, lane); }
 __device__ __forceinline__ uint64_t ecr_above(int32_t j) { return j < 0? ~0ULL : (j >= 63? 0ULL : ~0ULL << (j + 1)); }      // lanes > j
 
-// km, mp, del: this lane's chain entry (lane < n <= 64); every argument of the callbacks is wave-uniform
+// km, mp, del: this lane's chain entry (lane < n <= 64); every argument of the callbacks is wave-uniform.  The whole wave walks (lanes at or beyond n
+// stay active) and n is the read's, so beg, end, nb and everything the loop branches on -- ballots, their trailing-zero counts, broadcast entries -- are the
+// same in every lane: ecr_s says so where such a value enters the loop, and the loop's state then lives in scalar registers
 template <class FB, class FC>
-__device__ int ec_blocks_wave(int lane, int32_t n, uint64_t km, uint32_t mp, bool del, uint32_t hoco_l, int K, FB on_block, FC on_copy)
+__device__ int ec_blocks_wave(int lane, int32_t n_, uint64_t km, uint32_t mp, bool del, uint32_t hoco_l, int K, FB on_block, FC on_copy)
 {
+    const int32_t n = ecr_s(n_);
     const bool in = lane < n;
     const uint64_t goodm = __ballot(in && !del && !(km & 1ULL)), delm = __ballot(in && del);
     const uint32_t pos = mp >> 1;
@@ -273,7 +279,7 @@ __device__ int ec_blocks_wave(int lane, int32_t n, uint64_t km, uint32_t mp, boo
         uint32_t beg_pos = beg < 1? 0u : ecr_u32(pos, beg - 1) + (uint32_t) K;
         beg_pos += EC_MIN_ERR_SEQ_LEN;
         const uint64_t m = __ballot(pos >= beg_pos) & goodm & ecr_above(beg);
-        end = m? (int32_t) __builtin_ctzll(m) : (beg + 1 < n? n : beg + 1);
+        end = ecr_s(m? (int32_t) __builtin_ctzll(m) : (beg + 1 < n? n : beg + 1));
         if (beg >= 0 || end < n) {
             EcBlock b;
             if (beg < 0) {
@@ -308,6 +314,7 @@ __device__ int ec_blocks_wave(int lane, int32_t n, uint64_t km, uint32_t mp, boo
         } else {
             beg = end + 1;
         }
+        beg = ecr_s(beg);
         if (beg > n) break;
         on_copy(end, beg);
     }

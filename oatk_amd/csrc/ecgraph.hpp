@@ -88,8 +88,8 @@ __global__ __launch_bounds__(256) void egr_pair_light_wave_kernel(uint64_t n_rea
     const uint32_t mp = in? m_pos[o + lane] : 0;
     const uint64_t v1 = (km >> 1) << 1 | (mp & 1u);
     const uint32_t p1 = mp >> 1;
-    const uint64_t v0 = (uint64_t) __shfl_up((long long) v1, 1);
-    const uint32_t p0 = (uint32_t) __shfl_up((int) p1, 1);
+    const uint64_t v0 = (uint64_t) wave_prev((uint32_t) (v1 >> 32)) << 32 | wave_prev((uint32_t) v1);     // the whole wave is here: r and n are the wave's
+    const uint32_t p0 = wave_prev(p1);
     if (in && lane == 0) keys[o] = EGR_INVALID, dist[o] = 0, keep[o] = 0;
     if (in && lane > 0) emit(o + lane, v0, p0, v1, p1);
 }
@@ -349,7 +349,7 @@ __global__ __launch_bounds__(64) void egr_mode_kernel(uint64_t n_runs, const uin
     if (big) {
         uint32_t base = 0;
         if (lane == __builtin_ctzll(big)) base = atomicAdd(&flags[4], (uint32_t) __builtin_popcountll(big));
-        base = (uint32_t) __shfl((int32_t) base, __builtin_ctzll(big));
+        base = wave_read(base, __builtin_ctzll(big));
         if (is_big) big_list[base + (uint32_t) __builtin_popcountll(big & ((1ULL << lane) - 1ULL))] = (uint32_t) i;
     }
 }
@@ -377,14 +377,14 @@ __global__ __launch_bounds__(64) void egr_mode_big_kernel(const uint32_t *counts
             uint64_t rest = __ballot(in);
             while (rest && !h.overflow) {
                 const int f = __builtin_ctzll(rest);
-                const int32_t x = __builtin_amdgcn_readfirstlane(__shfl(d, f));
+                const int32_t x = (int32_t) wave_read((uint32_t) d, f);
                 const uint64_t eq = __ballot(in && d == x) & rest;
                 rest &= ~eq;
                 uint32_t calls = (uint32_t) __builtin_popcountll(eq);
-                const uint32_t wf = (uint32_t) __builtin_amdgcn_readfirstlane((int32_t) __shfl(w, f));
+                const uint32_t wf = wave_read(w, f);
                 if (swgt) {
                     calls = 0;
-                    for (uint64_t q = eq; q; q &= q - 1) calls += (uint32_t) __builtin_amdgcn_readfirstlane((int32_t) __shfl(w, __builtin_ctzll(q)));
+                    for (uint64_t q = eq; q; q &= q - 1) calls += wave_read(w, __builtin_ctzll(q));
                 }
                 tot += calls;
                 const bool fresh = h.add(x, (int32_t) calls);

@@ -1,24 +1,36 @@
-// oatk_amd/csrc/kmer_hash.hpp -- MurmurHash64A of oriented k-mers, one LANE per syncmer.
+// oatk_amd/csrc/kmer_hash.hpp -- MurmurHash64A of oriented k-mers, and every syncmer record to its slot.
 //
 // Replaces `kmer_hash64` (syncmer.c:175-226) for all syncmer records of a batch at once.  Inside the scan kernel the
 // hash is poison for a wave64 machine: a 251-byte k-mer is a 31-step dependent chain that keeps one lane busy while
-// 63 idle.  Here a wave owns 64 records: first all 64 lanes cooperatively fetch and pre-mix the 8-byte Murmur blocks
-// (coalesced reads of each record's contiguous hoco bytes, results parked in LDS), then every lane runs the dependent
-// chain of ITS record, so the chain phase issues with all 64 lanes active.
+// 63 idle.  Here a wave owns KMH_REC = 16 records: first four lanes per record fetch and pre-mix the 8-byte Murmur blocks
+// (runs of consecutive source words of the record's hoco bytes, results parked in LDS), then one lane per record runs the
+// dependent chain of ITS record and writes the record out: hash, occurrence word, s-mer and position to the per-read
+// arrays at slot scm_off[read] + ordinal, the sort's key and value, and the slot record of the count's gathers.
 #pragma once
 #include "common.hpp"
 #include "count.hpp"   // kmer_word_global
 
 namespace oatk {
 
+// The kernel takes its records where kernel B left them -- the shard regions (scan_syncmer.hpp) -- and writes each to its slot scm_off[read] + ordinal:
+// the per-read arrays, the sort's key and value, and the 32-byte record the count gathers (count.hpp: pack_slots_kernel writes the same for a batch
+// that did not come from here): per record it holds all of that in registers anyway.
 struct KmerHashArgs {
     const uint8_t *hoco_s;        // read r at off[r] / 4
     const uint64_t *off;
     uint64_t sid0;
-    const uint64_t *rec_lo;       // sid << 32 | ordinal << 1 | rev
-    const uint32_t *rec_mpos;     // pos << 1 | rev
-    uint64_t *rec_hash;           // out
-    uint32_t n_rec;
+    const uint64_t *raw_lo;       // sid << 32 | ordinal << 1 | rev         shard sh's records at [sh * region_cap, + shard_cnt[sh])
+    const uint64_t *raw_smer;
+    const uint32_t *raw_mpos;     // pos << 1 | rev
+    const uint32_t *shard_cnt;
+    uint32_t region_cap;
+    const uint64_t *scm_off;      // exclusive prefix of n_scm over reads
+    uint64_t hash_mask;           // debug knob (tests force collisions); ~0 in production
+    uint64_t *pos_hash, *pos_lo, *pos_smer;       // out, per slot
+    uint32_t *pos_mpos;
+    uint64_t *key_hash;           // masked copy used as the sort key
+    uint32_t *iota;
+    uint4 *slot_rec;              // two per slot: (occurrence word, s-mer), (k-mer locator, 0)
     int K;
 };
 
@@ -44,14 +56,22 @@ __global__ __launch_bounds__(64, OATK_KMH_WAVES) void kmer_hash_kernel(KmerHashA
 {
     extern __shared__ uint64_t kmix[];          // KMH_REC records x (NW + 1)
     const uint32_t lane = threadIdx.x, rr = lane >> 2, q = lane & 3u;
-    const uint32_t base = blockIdx.x * (uint32_t) KMH_REC;
+    const uint32_t base = blockIdx.x * (uint32_t) KMH_REC;           // blockIdx.y: the shard; the grid is cut for the fullest one
+    uint32_t cnt = a.shard_cnt[blockIdx.y];
+    cnt = cnt < a.region_cap? cnt : a.region_cap;
+    if (base >= cnt) return;
+    const size_t src = (size_t) blockIdx.y * a.region_cap + base;
     const int K = a.K;
     const int nbytes = (K - 1) / 4 + 1, nfull = nbytes >> 3, nrem = nbytes & 7, NW = nfull + (nrem? 1 : 0);
     const int stride = NW + 1;
-    const uint32_t nrec = a.n_rec - base < (uint32_t) KMH_REC? a.n_rec - base : (uint32_t) KMH_REC;
+    const uint32_t nrec = cnt - base < (uint32_t) KMH_REC? cnt - base : (uint32_t) KMH_REC;
+    uint64_t lo = 0;
+    uint32_t mp = 0, hsw32 = 0;
     if (rr < nrec) {
-        const uint32_t mp = a.rec_mpos[base + rr], rev = mp & 1u, pos = mp >> 1;      // (four lanes, one address)
-        const int64_t hsw = (int64_t) (a.off[(a.rec_lo[base + rr] >> 32) - a.sid0] >> 4);      // 32-bit word index of the read's hoco string
+        mp = a.raw_mpos[src + rr], lo = a.raw_lo[src + rr];                           // (four lanes, one address)
+        const uint32_t rev = mp & 1u, pos = mp >> 1;
+        const int64_t hsw = (int64_t) (a.off[(lo >> 32) - a.sid0] >> 4);              // 32-bit word index of the read's hoco string
+        hsw32 = (uint32_t) hsw;
         const uint32_t *hs32 = (const uint32_t *) a.hoco_s;
         uint64_t *out = &kmix[rr * (uint32_t) stride];
         const int per = (NW + 3) >> 2;                                        // blocks per lane
@@ -116,6 +136,13 @@ __global__ __launch_bounds__(64, OATK_KMH_WAVES) void kmer_hash_kernel(KmerHashA
             }
         }
     }
+    // lane l < nrec finishes record l, whose words lanes 4 l .. 4 l + 3 hold (handed over by shuffle, once per sixteen records: loading them again would put
+    // a second chain of two dependent gathers, occurrence word -> read offset, in front of the stores); its slot and its s-mer are asked for before the barrier
+    const int from = (int) (lane & 15u) * 4;
+    const uint64_t my_lo = (uint64_t) (uint32_t) __shfl((int) (lo >> 32), from) << 32 | (uint32_t) __shfl((int) lo, from);
+    const uint32_t my_mp = (uint32_t) __shfl((int) mp, from), my_hsw = (uint32_t) __shfl((int) hsw32, from);
+    uint64_t my_p = 0, my_sm = 0;
+    if (lane < nrec) my_p = a.scm_off[(my_lo >> 32) - a.sid0] + ((uint32_t) my_lo >> 1), my_sm = a.raw_smer[src + lane];
     __syncthreads();
     if (lane < nrec) {
         const uint64_t *km = &kmix[lane * (uint32_t) stride];
@@ -123,7 +150,10 @@ __global__ __launch_bounds__(64, OATK_KMH_WAVES) void kmer_hash_kernel(KmerHashA
         for (int wd = 0; wd < nfull; ++wd) h = (h ^ km[wd]) * OATK_MURMUR_M;
         if (nrem) h = (h ^ km[nfull]) * OATK_MURMUR_M;
         h ^= h >> 47; h *= OATK_MURMUR_M; h ^= h >> 47;
-        a.rec_hash[base + lane] = h;
+        a.pos_hash[my_p] = h, a.key_hash[my_p] = h & a.hash_mask;
+        a.pos_lo[my_p] = my_lo, a.pos_smer[my_p] = my_sm, a.pos_mpos[my_p] = my_mp, a.iota[my_p] = (uint32_t) my_p;
+        a.slot_rec[2 * (size_t) my_p] = make_uint4((uint32_t) my_lo, (uint32_t) (my_lo >> 32), (uint32_t) my_sm, (uint32_t) (my_sm >> 32));
+        a.slot_rec[2 * (size_t) my_p + 1] = make_uint4(my_mp, my_hsw, 0u, 0u);     // the locator: (word index of the read's hoco string) << 32 | pos << 1 | rev
     }
 }
 
