@@ -784,12 +784,11 @@ int oatk_hip_scan(oatk_hip_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_off
         kh.pos_hash = ctx->pos_hash.as<uint64_t>(), kh.pos_lo = ctx->pos_lo.as<uint64_t>(), kh.pos_smer = ctx->pos_smer.as<uint64_t>();
         kh.pos_mpos = ctx->pos_mpos.as<uint32_t>(), kh.key_hash = ctx->key_hash.as<uint64_t>(), kh.iota = ctx->iota.as<uint32_t>();
         kh.slot_rec = ctx->slot_rec.as<uint4>(), kh.K = ctx->K;
-        const int nw = ((ctx->K - 1) / 4 + 1 + 7) / 8;
         // grid.y = the shard, grid.x cut for the fullest one: blocks past their shard's count return at once.  Reads are dealt to the shards round-robin, so at
         // any size worth timing the shards are even (config 3: within a few per cent); a small or lopsided batch launches mostly empty blocks, which cost it nothing
         // that matters (1024 x a few blocks).  A dense index through a prefix of the counts would need that prefix on the device first.
         t_begin(ctx, OATK_T_KMER_HASH);
-        hipLaunchKernelGGL(oatk::kmer_hash_kernel, dim3((sc_max + KMH_REC - 1) / KMH_REC, NSH), dim3(64), (size_t) KMH_REC * (nw + 1) * 8, ctx->stream, kh);
+        hipLaunchKernelGGL(oatk::kmer_hash_kernel, dim3((sc_max + KMH_WG_REC - 1) / KMH_WG_REC, NSH), dim3(KMH_WG_WAVES * 64), oatk::kmh_lds_bytes(ctx->K), ctx->stream, kh);
         t_end(ctx, OATK_T_KMER_HASH);
     }
     CK(hipGetLastError());

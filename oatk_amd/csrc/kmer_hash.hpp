@@ -2,10 +2,13 @@
 //
 // Replaces `kmer_hash64` (syncmer.c:175-226) for all syncmer records of a batch at once.  Inside the scan kernel the
 // hash is poison for a wave64 machine: a 251-byte k-mer is a 31-step dependent chain that keeps one lane busy while
-// 63 idle.  Here a wave owns KMH_REC = 16 records: first four lanes per record fetch and pre-mix the 8-byte Murmur blocks
-// (runs of consecutive source words of the record's hoco bytes, results parked in LDS), then one lane per record runs the
-// dependent chain of ITS record and writes the record out: hash, occurrence word, s-mer and position to the per-read
-// arrays at slot scm_off[read] + ordinal, the sort's key and value, and the slot record of the count's gathers.
+// 63 idle.  Here a workgroup of four waves owns KMH_WG_REC = 64 records.  First every wave prepares KMH_REC = 16 of them:
+// four lanes per record fetch and pre-mix the 8-byte Murmur blocks (runs of consecutive source words of the record's
+// hoco bytes, results parked in LDS).  Then, behind one barrier, the workgroup's first wave runs the dependent chains of
+// all 64 records, one lane per record -- a full wave: a wave64 instruction under a quarter-full mask costs a full issue
+// slot, and the chain is a third of the kernel's instructions -- and writes the records out: hash, occurrence word,
+// s-mer and position to the per-read arrays at slot scm_off[read] + ordinal, the sort's key and value, and the slot
+// record of the count's gathers.  The other three waves leave at the barrier.
 #pragma once
 #include "common.hpp"
 #include "count.hpp"   // kmer_word_global
@@ -34,7 +37,9 @@ struct KmerHashArgs {
     int K;
 };
 
-#define KMH_REC 16                // records per wave: most lanes idle in the short chain phase, but four times the waves fit a CU's LDS (64: 1.12 ms, 32: 0.75, 16: 0.56, 8: 0.67)
+#define KMH_REC 16                // records a wave prepares, four lanes each (r03, one wave per workgroup: 64: 1.12 ms, 32: 0.75, 16: 0.56, 8: 0.67)
+#define KMH_WG_WAVES 4            // waves per workgroup
+#define KMH_WG_REC (KMH_REC * KMH_WG_WAVES)       // = 64 records per workgroup: one lane each in the chain phase
 #define KMH_WPL 8                 // Murmur blocks a lane prepares in one go (their source words are loaded together; four: 3.68 against 2.95 ms, r04)
 
 // r03: FOUR LANES PER RECORD, each preparing a run of consecutive 8-byte Murmur blocks of its record.  A run of blocks is a run of consecutive source
@@ -49,29 +54,38 @@ __device__ __forceinline__ uint32_t kmh_rev_in_bytes(uint32_t x)
     return ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
 }
 
+// LDS of a workgroup: per record its pre-mixed blocks, an ODD number of 64-bit words apart, so that the 64 lanes of the chain phase, each reading block w of
+// its own record, fall on different banks (63.5 KB at the largest k the scan takes).
+__host__ __device__ inline int kmh_lds_stride(int K)
+{
+    const int nbytes = (K - 1) / 4 + 1;
+    return ((nbytes + 7) >> 3) | 1;
+}
+__host__ __device__ inline size_t kmh_lds_bytes(int K) { return (size_t) KMH_WG_REC * kmh_lds_stride(K) * 8; }
+
 #ifndef OATK_KMH_WAVES
 #define OATK_KMH_WAVES 8                 // waves per SIMD the register allocation aims at: the kernel is a chain of dependent gathers, its rate is records in flight (r03m, 400 k reads: 0.94 ms at five waves, 0.60 at eight)
 #endif
-__global__ __launch_bounds__(64, OATK_KMH_WAVES) void kmer_hash_kernel(KmerHashArgs a)
+__global__ __launch_bounds__(KMH_WG_WAVES * 64, OATK_KMH_WAVES) void kmer_hash_kernel(KmerHashArgs a)
 {
-    extern __shared__ uint64_t kmix[];          // KMH_REC records x (NW + 1)
-    const uint32_t lane = threadIdx.x, rr = lane >> 2, q = lane & 3u;
-    const uint32_t base = blockIdx.x * (uint32_t) KMH_REC;           // blockIdx.y: the shard; the grid is cut for the fullest one
+    extern __shared__ uint64_t kmix[];          // kmh_lds_bytes(K)
+    const uint32_t lane = threadIdx.x & 63u, q = lane & 3u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (in a scalar register: what it decides is a branch, not an exec mask)
+    const uint32_t rr = wave * (uint32_t) KMH_REC + (lane >> 2);     // the record lanes 4 (rr & 15) .. + 3 of this wave prepare
+    const uint32_t base = blockIdx.x * (uint32_t) KMH_WG_REC;        // blockIdx.y: the shard; the grid is cut for the fullest one
     uint32_t cnt = a.shard_cnt[blockIdx.y];
     cnt = cnt < a.region_cap? cnt : a.region_cap;
     if (base >= cnt) return;
     const size_t src = (size_t) blockIdx.y * a.region_cap + base;
     const int K = a.K;
     const int nbytes = (K - 1) / 4 + 1, nfull = nbytes >> 3, nrem = nbytes & 7, NW = nfull + (nrem? 1 : 0);
-    const int stride = NW + 1;
-    const uint32_t nrec = cnt - base < (uint32_t) KMH_REC? cnt - base : (uint32_t) KMH_REC;
-    uint64_t lo = 0;
-    uint32_t mp = 0, hsw32 = 0;
+    const int stride = kmh_lds_stride(K);
+    const uint32_t nrec = cnt - base < (uint32_t) KMH_WG_REC? cnt - base : (uint32_t) KMH_WG_REC;
     if (rr < nrec) {
-        mp = a.raw_mpos[src + rr], lo = a.raw_lo[src + rr];                           // (four lanes, one address)
+        const uint32_t mp = a.raw_mpos[src + rr];                                     // (four lanes, one address)
+        const uint64_t lo = a.raw_lo[src + rr];
         const uint32_t rev = mp & 1u, pos = mp >> 1;
         const int64_t hsw = (int64_t) (a.off[(lo >> 32) - a.sid0] >> 4);              // 32-bit word index of the read's hoco string
-        hsw32 = (uint32_t) hsw;
         const uint32_t *hs32 = (const uint32_t *) a.hoco_s;
         uint64_t *out = &kmix[rr * (uint32_t) stride];
         const int per = (NW + 3) >> 2;                                        // blocks per lane
@@ -136,20 +150,26 @@ __global__ __launch_bounds__(64, OATK_KMH_WAVES) void kmer_hash_kernel(KmerHashA
             }
         }
     }
-    // lane l < nrec finishes record l, whose words lanes 4 l .. 4 l + 3 hold (handed over by shuffle, once per sixteen records: loading them again would put
-    // a second chain of two dependent gathers, occurrence word -> read offset, in front of the stores); its slot and its s-mer are asked for before the barrier
-    const int from = (int) (lane & 15u) * 4;
-    const uint64_t my_lo = (uint64_t) (uint32_t) __shfl((int) (lo >> 32), from) << 32 | (uint32_t) __shfl((int) lo, from);
-    const uint32_t my_mp = (uint32_t) __shfl((int) mp, from), my_hsw = (uint32_t) __shfl((int) hsw32, from);
-    uint64_t my_p = 0, my_sm = 0;
-    if (lane < nrec) my_p = a.scm_off[(my_lo >> 32) - a.sid0] + ((uint32_t) my_lo >> 1), my_sm = a.raw_smer[src + lane];
+    // The first wave finishes the workgroup's records, lane l record l.  It loads the record's words itself, 64 consecutive ones per array, and from the
+    // occurrence word the read's slot offset and the locator's word index (lines its workgroup has just had in the cache): two dependent loads, the first asked for
+    // in front of the barrier and the second hidden by the chain, where handing them over would take LDS the largest k does not leave.  The chain itself runs on ALL 64
+    // lanes, also in a shard's last workgroup, where lanes past nrec hash the last record once more and store nothing: no exec mask around the loop.
+    const uint32_t mine = lane < nrec? lane : nrec - 1;              // (a lane past nrec goes through the motions on the shard's last record)
+    uint64_t my_lo = 0;
+    if (wave == 0) my_lo = a.raw_lo[src + mine];                     // (on its way while the other waves arrive)
     __syncthreads();
+    if (wave != 0) return;
+    const uint64_t my_sm = a.raw_smer[src + mine];
+    const uint32_t my_mp = a.raw_mpos[src + mine];
+    const uint64_t my_off = a.scm_off[(my_lo >> 32) - a.sid0];       // (waited for behind the chain)
+    const uint32_t my_hsw = (uint32_t) (a.off[(my_lo >> 32) - a.sid0] >> 4);
+    const uint64_t *km = &kmix[mine * (uint32_t) stride];
+    uint64_t h = OATK_MURMUR_SEED ^ ((uint64_t) (uint32_t) nbytes * OATK_MURMUR_M);
+    for (int wd = 0; wd < nfull; ++wd) h = (h ^ km[wd]) * OATK_MURMUR_M;
+    if (nrem) h = (h ^ km[nfull]) * OATK_MURMUR_M;
+    h ^= h >> 47; h *= OATK_MURMUR_M; h ^= h >> 47;
     if (lane < nrec) {
-        const uint64_t *km = &kmix[lane * (uint32_t) stride];
-        uint64_t h = OATK_MURMUR_SEED ^ ((uint64_t) (uint32_t) nbytes * OATK_MURMUR_M);
-        for (int wd = 0; wd < nfull; ++wd) h = (h ^ km[wd]) * OATK_MURMUR_M;
-        if (nrem) h = (h ^ km[nfull]) * OATK_MURMUR_M;
-        h ^= h >> 47; h *= OATK_MURMUR_M; h ^= h >> 47;
+        const uint64_t my_p = my_off + ((uint32_t) my_lo >> 1);
         a.pos_hash[my_p] = h, a.key_hash[my_p] = h & a.hash_mask;
         a.pos_lo[my_p] = my_lo, a.pos_smer[my_p] = my_sm, a.pos_mpos[my_p] = my_mp, a.iota[my_p] = (uint32_t) my_p;
         a.slot_rec[2 * (size_t) my_p] = make_uint4((uint32_t) my_lo, (uint32_t) (my_lo >> 32), (uint32_t) my_sm, (uint32_t) (my_sm >> 32));
