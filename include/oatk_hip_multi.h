@@ -32,7 +32,9 @@
  * (tests/mock_rccl_run.py) -- not yet on two physical GPUs: no multi-GPU node has been available to its builders.  Treat it as experimental
  * until tests/test_gpu_multi_c.py has passed on such a node.  A communicator is bound to the device it was created for: a call with a handle of
  * another device is refused (OATK_E_ARG), and a rank that fails between collectives aborts the communicator / poisons the group so that its
- * peers return an error instead of waiting for it.
+ * peers return an error instead of waiting for it.  The same status holds for the coverage estimates over sharded reads (include/oatk_hip_racov.h:
+ * oatk_hip_ra_*_coverage_sharded, whose chain of broadcasts is an all-gather with one contributor): run with 1 - 3 ranks over the local group on one GPU
+ * (tests/test_gpu_racov_sharded.py), never on two physical GPUs.
  */
 #ifndef OATK_HIP_MULTI_H
 #define OATK_HIP_MULTI_H
@@ -90,6 +92,8 @@ enum { OATK_BUF_MG_H = 220, OATK_BUF_MG_S, OATK_BUF_MG_COV, OATK_BUF_MG_L2G, OAT
  * produce them from sharded reads; every rank makes the same call; results are bit-identical to one handle holding all the reads
  * (tests/test_gpu_multi_tail.py).  Per rank, the traffic of each is bounded by what the result itself weighs -- none grows with the number
  * of ranks the way an all-gather of every shard's chains would.
+ *
+ * The coverage estimates from read alignments (scg_ra_utg_coverage, scg_ra_arc_coverage) over sharded reads are in include/oatk_hip_racov.h.
  *
  * oatk_hip_gather_table   the table as it stands -- after oatk_hip_merge_counts: what collect_syncmer_from_reads returns; after
  *                         oatk_hip_ec_sharded: what update_syncmer_db leaves -- assembled on rank `root` (ids for oatk_hip_buffer, valid there):

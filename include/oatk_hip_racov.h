@@ -6,11 +6,15 @@
  *
  * The alignments are the resident ones of the last oatk_hip_read_alignment (aln == NULL) or uploaded; the reads' chains are the resident
  * batch's (reads == NULL; after oatk_hip_ec: the corrected chains) or uploaded.  The graph is passed in, flattened, HOST pointers.
+ *
+ * Both estimates exist for one handle holding all reads and, as collectives over an oatk_comm (include/oatk_hip_multi.h), for reads sharded
+ * by record over several handles: the *_sharded entry points below return, on every rank, the doubles the one-handle call returns.
  */
 #ifndef OATK_HIP_RACOV_H
 #define OATK_HIP_RACOV_H
 
 #include "oatk_hip.h"
+#include "oatk_hip_multi.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -60,6 +64,31 @@ int oatk_hip_ra_utg_coverage(oatk_hip_ctx *ctx, const oatk_racov_graph_t *g, con
 /* arc_cov[n_arc]: for every arc that is not deleted, the spanning-duplet sum of its key link_id << 1 | comp, 0 when it has none
  * (:2131-2137 before the (uint32_t)); deleted arcs get 0.  OATK_E_ARG when two consecutive fragments have no arc (asmg_arc == NULL). */
 int oatk_hip_ra_arc_coverage(oatk_hip_ctx *ctx, const oatk_racov_graph_t *g, const oatk_racov_aln_t *aln, double *arc_cov);
+
+/* The same two estimates with the reads SHARDED BY RECORD: every rank makes the same call with the same graph (global syncmer ids); rank r
+ * holds a contiguous range of the reads, rank order is read order.  aln == NULL: the handle's resident alignments of its last
+ * oatk_hip_read_alignment; reads == NULL: its resident chains from the source that alignment used -- after oatk_hip_ec_sharded the
+ * corrected chains in global ids (what the one-handle call refuses to serve).  Non-NULL reads / aln are THIS RANK'S slice, uploaded: sid
+ * indexes the slice's own chains, records in the order of the whole set.  A rank without alignments still takes part.
+ *
+ * Results are identical on every rank and equal, double for double, what the one-handle call returns for all reads; no sum is
+ * re-associated:
+ *   first round   the per-position counts are integers: one all-reduce of u32[utg_off[n_utg]], then the same IQR code on every rank
+ *   make_ma_block per read, local; the working limit (OATK_E_SPLIT, oatk_hip_debug_racov_cap) applies per rank, and the ranks agree on
+ *                 the verdict before anything is written: one rank over the limit, OATK_E_SPLIT on all
+ *   EM            a unitig's sum takes its addends in (read, block, member) order and the shards are consecutive stretches of it: rank r
+ *                 starts every sum from rank r - 1's result and hands its own on; the last rank's n_utg sums go to everybody, the update
+ *                 and diff run on every rank alike, all leave at the same iteration.  n_utg doubles per rank and iteration, whatever
+ *                 the number of reads.  verbose > 2: rank 0 prints the reference's lines
+ *   third round   the graph and the averages only: every rank computes it
+ *   arc duplets   per link, a rank's events are a stretch of the reference's put order: the table (seen flags and values of both keys of
+ *                 every link, 18 bytes per link) is handed from rank to rank and the last rank's goes to everybody.  A missing arc on any
+ *                 rank is OATK_E_ARG on all
+ * If no rank has an alignment the unitig call writes nothing.  A rank that fails between two collectives poisons the group like the
+ * other sharded calls do.  The one-handle entry points run the same kernels with zero carries and no collective. */
+int oatk_hip_ra_utg_coverage_sharded(oatk_hip_ctx *ctx, oatk_comm *comm, const oatk_racov_graph_t *g, const oatk_racov_reads_t *reads,
+                                     const oatk_racov_aln_t *aln, int verbose, double *utg_cov, uint64_t *n_iter);
+int oatk_hip_ra_arc_coverage_sharded(oatk_hip_ctx *ctx, oatk_comm *comm, const oatk_racov_graph_t *g, const oatk_racov_aln_t *aln, double *arc_cov);
 
 /* Test hook: the most LCS-matrix cells (4 bytes each) the unitig coverage may hold at once, over all reads; 0 = default (2^31, 8 GiB). */
 int oatk_hip_debug_racov_cap(oatk_hip_ctx *ctx, uint64_t cells);

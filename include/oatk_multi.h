@@ -6,7 +6,8 @@
  * that hand-off: an oatk_multi owns one device handle per GPU (include/oatk_hip.h) and one communicator per handle (include/oatk_hip_multi.h); its
  * entry points mirror those of include/oatk_syncasm.h one for one and leave the SAME structs -- one sr_db_t, one syncmer_db_t with every syncmer's
  * occurrences in (sid, idx) order (syncmer.c:1353-1360, syncerr.c:796-805), one asmg_t, one consensus / distance table set, one scg_ra_v -- so the
- * reference's serial tail (unitigging, cleaning, unzipping, GFA) runs on them unchanged.  Results are bit-identical to one handle holding all reads
+ * reference's serial tail (unitigging, cleaning, unzipping, GFA) runs on them unchanged; the tail's two coverage estimates from read alignments, whose
+ * work grows with the reads, have their N-handle form here too.  Results are bit-identical to one handle holding all reads
  * (tests/test_gpu_cli.py::test_cli_over_several_handles: both GFA files byte-identical with 2 and 4 handles).
  *
  * Who talks to whom: handle r holds the reads of the r-th part of the input (contiguous read ids).  Scan and count are local.  The collectives run on
@@ -53,6 +54,14 @@ oatk_consensus_t *oatk_multi_consensus_fetch(oatk_multi *m, uint32_t min_cov, in
 oatk_overlap_t *oatk_multi_overlap_fetch(oatk_multi *m, uint32_t min_cov, int *rc);
 /* scg_read_alignment (alignment.c:596): every handle aligns its own reads against the same graph, no exchange */
 int oatk_multi_scg_read_alignment(oatk_multi *m, oatk_sr_db_t *sr_db, oatk_scg_ra_v *ra_v, oatk_scg_t *g, int for_unzip, uint64_t *n_skipped);
+/* scg_ra_utg_coverage (syncasm.c:1882) and scg_ra_arc_coverage up to its refinement (:2067-2138), as oatk_scg_ra_utg_coverage / oatk_scg_ra_arc_coverage
+ * leave them: vtx[].cov / the live arcs' cov of g->utg_asmg.  Every handle works on the alignments and corrected chains of its own reads where they
+ * lie, resident (include/oatk_hip_racov.h: the *_sharded calls); what travels is the size of the graph, not of the reads.  ra_v must be what
+ * oatk_multi_scg_read_alignment wrote last, for this g and unchanged (OATK_E_STATE otherwise, as for foreign reads).  Nothing is written unless the
+ * code is OATK_OK (OATK_E_SPLIT: some handle is over the working limit -- run the original); the unitig call with no alignment prints the reference's
+ * warning once and changes nothing.  The arc caller finishes with the reference's scg_refine_arc_coverage or asmg_arc_fix_cov itself. */
+int oatk_multi_scg_ra_utg_coverage(oatk_multi *m, const oatk_sr_db_t *sr_db, const oatk_scg_ra_v *ra_v, oatk_scg_t *g, int verbose);
+int oatk_multi_scg_ra_arc_coverage(oatk_multi *m, const oatk_sr_db_t *sr_db, const oatk_scg_ra_v *ra_v, oatk_scg_t *g, int verbose);
 
 #ifdef __cplusplus
 }

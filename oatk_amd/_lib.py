@@ -52,8 +52,38 @@ EXPORTS = [
     "oatk_hip_ec_set_global", "oatk_hip_ec_pairs", "oatk_hip_ec_graph_from_pairs", "oatk_hip_ec_graph_from_segments", "oatk_hip_ec_export_kmers", "oatk_hip_ec_import_kmers",
     "oatk_hip_ec_reserve_import", "oatk_hip_consensus", "oatk_hip_consensus_ids", "oatk_hip_ingest", "oatk_hip_ingest_host", "oatk_hip_scan_ingested", "oatk_hip_stat", "oatk_hip_stat_keys", "oatk_hip_stat_from_keys",
     "oatk_hip_asm_graph", "oatk_hip_asm_pairs", "oatk_hip_asm_graph_from_pairs", "oatk_hip_overlap_hist", "oatk_hip_overlap_pairs", "oatk_hip_overlap_hist_from_pairs", "oatk_hip_read_alignment", "oatk_hip_debug_align_two_pass",
-    "oatk_hip_ra_utg_coverage", "oatk_hip_ra_arc_coverage", "oatk_hip_debug_racov_cap",
+    "oatk_hip_ra_utg_coverage", "oatk_hip_ra_arc_coverage", "oatk_hip_debug_racov_cap", "oatk_hip_ra_utg_coverage_sharded", "oatk_hip_ra_arc_coverage_sharded",
 ]
+
+# the N-handle mirror in liboatk_host.so (include/oatk_multi.h) of entry points listed above; EXPORTS itself is checked against liboatk_hip.so
+HOST_EXPORTS = ["oatk_multi_scg_ra_utg_coverage", "oatk_multi_scg_ra_arc_coverage"]
+
+
+def load_host():
+    """liboatk_host.so with the argtypes of include/oatk_multi.h (the N-handle entry points the tests and timing scripts drive)"""
+    H = C.CDLL(HOST_LIB_PATH)
+    vp = C.c_void_p
+    H.oatk_sr_db_new.restype = vp
+    H.oatk_sr_db_new.argtypes = [C.c_int, C.c_int]
+    H.oatk_multi_create.restype = vp
+    H.oatk_multi_create.argtypes = [C.POINTER(C.c_int), C.c_int]
+    H.oatk_multi_destroy.argtypes = [vp]
+    H.oatk_multi_ctx.restype = vp
+    H.oatk_multi_ctx.argtypes = [vp, C.c_int]
+    H.oatk_multi_last_error.restype = C.c_char_p
+    H.oatk_multi_last_error.argtypes = [vp]
+    H.oatk_multi_range.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    H.oatk_multi_sr_read_files.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.c_int]
+    H.oatk_multi_collect_syncmer_from_reads.restype = vp
+    H.oatk_multi_collect_syncmer_from_reads.argtypes = [vp, vp, C.POINTER(C.c_int)]
+    H.oatk_multi_read_error_correction.argtypes = [vp, vp, vp, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, vp]
+    H.oatk_multi_make_syncmer_asmg.restype = vp
+    H.oatk_multi_make_syncmer_asmg.argtypes = [vp, vp, C.c_uint32, C.c_double, C.POINTER(C.c_int)]
+    H.oatk_multi_scg_read_alignment.argtypes = [vp, vp, vp, vp, C.c_int, C.POINTER(C.c_uint64)]
+    H.oatk_multi_scg_ra_utg_coverage.argtypes = [vp, vp, vp, vp, C.c_int]
+    H.oatk_multi_scg_ra_arc_coverage.argtypes = [vp, vp, vp, vp, C.c_int]
+    H.oatk_host_debug_window.argtypes = [C.c_uint64]
+    return H
 
 
 class EcGraph(C.Structure):
@@ -201,6 +231,8 @@ def load():
     L.oatk_hip_ra_utg_coverage.argtypes = [vp, C.POINTER(RacovGraph), C.POINTER(RacovReads), C.POINTER(RacovAln), C.c_int, vp, C.POINTER(C.c_uint64)]
     L.oatk_hip_ra_arc_coverage.argtypes = [vp, C.POINTER(RacovGraph), C.POINTER(RacovAln), vp]
     L.oatk_hip_debug_racov_cap.argtypes = [vp, C.c_uint64]
+    L.oatk_hip_ra_utg_coverage_sharded.argtypes = [vp, vp, C.POINTER(RacovGraph), C.POINTER(RacovReads), C.POINTER(RacovAln), C.c_int, vp, C.POINTER(C.c_uint64)]
+    L.oatk_hip_ra_arc_coverage_sharded.argtypes = [vp, vp, C.POINTER(RacovGraph), C.POINTER(RacovAln), vp]
     L.oatk_hip_overlap_pairs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.oatk_hip_overlap_hist_from_pairs.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.oatk_hip_overlap_hist.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

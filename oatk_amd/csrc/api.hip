@@ -443,11 +443,11 @@ static void t_collect(oatk_hip_ctx *ctx, int first, int last)
 #include "api_cons.inc"
 #include "api_ovl.inc"
 #include "api_align.inc"
-#include "api_racov.inc"
 #include "api_ingest.inc"
 #include "api_stat.inc"
 #include "api_multi.inc"
 #include "api_multi_tail.inc"
+#include "api_racov.inc"
 
 static void staging_free(oatk_hip_ctx *ctx)
 {

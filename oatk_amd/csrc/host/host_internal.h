@@ -6,6 +6,7 @@
 #ifndef OATK_HOST_INTERNAL_H
 #define OATK_HOST_INTERNAL_H
 
+#include "oatk_hip_racov.h"
 #include "oatk_hip_stat.h"
 #include "oatk_syncasm.h"
 
@@ -28,6 +29,12 @@ int oatk_host_read_alignment_n(oatk_hip_ctx **ctx, const uint64_t *first, int n,
                                uint64_t *n_skipped, uint32_t **skipped);
 /* sr_read (syncmer.c:487) for files with the reads spread over n handles by position in the input: first[0 .. n] receives the read ranges */
 int oatk_host_sr_read_files_n(oatk_hip_ctx **ctx, int n, oatk_sr_db_t *sr_db, char **files, int n_files, uint64_t *first, uint64_t m_data);
+/* host/racov_host.c for host/multi_host.c: scg_t flattened into what include/oatk_hip_racov.h reads (free with oatk_host_racov_graph_free(keep)), and the
+ * reference's write-back of the doubles into vtx[].cov / the live arcs' cov */
+const oatk_racov_graph_t *oatk_host_racov_graph(const oatk_scg_t *g, int with_arcs, void **keep);
+void oatk_host_racov_graph_free(void *keep);
+void oatk_host_racov_write_utg(oatk_scg_t *g, const double *cov);
+void oatk_host_racov_write_arc(oatk_scg_t *g, const double *cov);
 
 
 typedef struct { uint8_t *p, *end; } oatk_name_bump_t;

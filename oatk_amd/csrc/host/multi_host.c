@@ -16,7 +16,9 @@
 
 #include "oatk_hip_cons.h"
 #include "oatk_hip_ec.h"
+#include "oatk_hip_align.h"
 #include "oatk_hip_graph.h"
+#include "oatk_hip_racov.h"
 #include "oatk_multi.h"
 #include "host_internal.h"
 
@@ -27,6 +29,10 @@ struct oatk_multi {
     oatk_comm_group *grp;          /* ranks that share a device talk through the in-process group */
     uint64_t first[65];            /* handle r holds reads [first[r], first[r + 1]) */
     int have_reads;
+    /* what oatk_multi_scg_read_alignment wrote last: the handles' resident alignments are these and no others (the coverage calls check it) */
+    int have_ra;
+    const void *ra_v, *ra_a, *ra_g;
+    uint64_t ra_n;
     char err[512];
 };
 
@@ -430,7 +436,89 @@ oatk_overlap_t *oatk_multi_overlap_fetch(oatk_multi *m, uint32_t min_cov, int *r
 int oatk_multi_scg_read_alignment(oatk_multi *m, oatk_sr_db_t *sr_db, oatk_scg_ra_v *ra_v, oatk_scg_t *g, int for_unzip, uint64_t *n_skipped)
 {
     if (!m->have_reads || m->first[m->n] != sr_db->n) { snprintf(m->err, sizeof(m->err), "the handles do not hold this database's reads"); return OATK_E_STATE; }
+    m->have_ra = 0;
     const int rc = oatk_host_read_alignment_n(m->ctx, m->first, m->n, sr_db, ra_v, g, for_unzip, n_skipped, 0);
     if (rc && rc != OATK_E_SPLIT) { int r; for (r = 0; r < m->n; ++r) if (oatk_hip_last_error(m->ctx[r])[0]) { note_err(m, r, rc); break; } }
+    if (!rc) {                                                                     /* (without reads or live unitigs nothing ran, alignment.c:598) */
+        uint64_t i, n_live = 0;
+        for (i = 0; i < g->utg_asmg->n_vtx; ++i) n_live += !g->utg_asmg->vtx[i].del;
+        if (sr_db->n && n_live) m->have_ra = 1, m->ra_v = ra_v, m->ra_a = ra_v->a, m->ra_n = ra_v->n, m->ra_g = g;
+    }
     return rc;
+}
+
+/* ------------------------------------------------ scg_ra_utg_coverage / scg_ra_arc_coverage ------------------------------------------------ */
+
+typedef struct { const oatk_racov_graph_t *g; int verbose; double *out[64]; uint64_t it[64]; } racov_arg_t;
+
+static int racov_utg_rank(oatk_multi *m, int rank, void *arg)
+{
+    racov_arg_t *a = (racov_arg_t *) arg;
+    return oatk_hip_ra_utg_coverage_sharded(m->ctx[rank], m->comm[rank], a->g, 0, 0, a->verbose, a->out[rank], &a->it[rank]);
+}
+
+static int racov_arc_rank(oatk_multi *m, int rank, void *arg)
+{
+    racov_arg_t *a = (racov_arg_t *) arg;
+    return oatk_hip_ra_arc_coverage_sharded(m->ctx[rank], m->comm[rank], a->g, 0, a->out[rank]);
+}
+
+/* the handles' resident alignments are ra_v's: it is what oatk_multi_scg_read_alignment wrote last, for this graph, and still as long */
+static int racov_resident(oatk_multi *m, const oatk_scg_ra_v *ra_v, const oatk_scg_t *g)
+{
+    uint64_t n = 0;
+    int r;
+    if (!m->have_ra || m->ra_v != (const void *) ra_v || m->ra_a != (const void *) ra_v->a || m->ra_n != ra_v->n || m->ra_g != (const void *) g) {
+        snprintf(m->err, sizeof(m->err), "the alignments are not what oatk_multi_scg_read_alignment wrote last for this graph");
+        return OATK_E_STATE;
+    }
+    for (r = 0; r < m->n; ++r) {
+        const void *d = 0;
+        uint64_t b = 0;
+        if (oatk_hip_buffer(m->ctx[r], OATK_BUF_RA_ALN_SID, &d, &b) != OATK_OK) { note_err(m, r, OATK_E_STATE); return OATK_E_STATE; }
+        n += b / 4;
+    }
+    if (n != ra_v->n) { snprintf(m->err, sizeof(m->err), "the handles hold %lu alignments, ra_v %lu", (unsigned long) n, (unsigned long) ra_v->n); return OATK_E_STATE; }
+    return OATK_OK;
+}
+
+static int racov_run(oatk_multi *m, oatk_scg_t *g, int arcs, int verbose)
+{
+    const uint64_t n_out = arcs? g->utg_asmg->n_arc : g->utg_asmg->n_vtx;
+    void *keep = 0;
+    racov_arg_t *a = (racov_arg_t *) calloc(1, sizeof(racov_arg_t));
+    int r, rc;
+    a->g = oatk_host_racov_graph(g, arcs, &keep), a->verbose = verbose;          /* flattened once, read by every handle's thread */
+    for (r = 0; r < m->n; ++r) a->out[r] = (double *) xmalloc(8 * n_out);
+    rc = run_ranks(m, arcs? racov_arc_rank : racov_utg_rank, a);
+    if (rc == OATK_OK) {                                                           /* (the same doubles on every rank) */
+        if (arcs) oatk_host_racov_write_arc(g, a->out[0]);
+        else oatk_host_racov_write_utg(g, a->out[0]);
+    }
+    for (r = 0; r < m->n; ++r) free(a->out[r]);
+    oatk_host_racov_graph_free(keep);
+    free(a);
+    return rc;
+}
+
+int oatk_multi_scg_ra_utg_coverage(oatk_multi *m, const oatk_sr_db_t *sr_db, const oatk_scg_ra_v *ra_v, oatk_scg_t *g, int verbose)
+{
+    int rc;
+    (void) sr_db;
+    if (!m) return OATK_E_NODEV;
+    if (ra_v->n == 0) {                                                            /* :1884-1887 */
+        fprintf(stderr, "[W::%s] no read alignment, unitig coverage estimation skipped\n", "scg_ra_utg_coverage");
+        return OATK_OK;
+    }
+    if ((rc = racov_resident(m, ra_v, g)) != OATK_OK) return rc;
+    return racov_run(m, g, 0, verbose);
+}
+
+int oatk_multi_scg_ra_arc_coverage(oatk_multi *m, const oatk_sr_db_t *sr_db, const oatk_scg_ra_v *ra_v, oatk_scg_t *g, int verbose)
+{
+    int rc;
+    (void) sr_db, (void) verbose;
+    if (!m) return OATK_E_NODEV;
+    if ((rc = racov_resident(m, ra_v, g)) != OATK_OK) return rc;
+    return racov_run(m, g, 1, 0);
 }

@@ -14,6 +14,7 @@
 
 #include "oatk_hip_racov.h"
 #include "oatk_syncasm.h"
+#include "host_internal.h"
 
 typedef unsigned __int128 u128_t;
 
@@ -138,8 +139,7 @@ int oatk_scg_ra_utg_coverage(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, const
     {
         double *cov = (double *) rc_malloc(8 * ug->n_vtx);
         rc = oatk_hip_ra_utg_coverage(ctx, &fg.g, (flags & OATK_RACOV_RESIDENT_READS)? 0 : &rd, (flags & OATK_RACOV_RESIDENT_ALN)? 0 : &fa.a, verbose, cov, &n_iter);
-        if (rc == OATK_OK)
-            for (i = 0; i < ug->n_vtx; ++i) ug->vtx[i].cov = (uint32_t) cov[i];      /* :2055-2056 */
+        if (rc == OATK_OK) oatk_host_racov_write_utg(g, cov);
         free(cov);
     }
 done:
@@ -151,7 +151,6 @@ done:
 
 int oatk_scg_ra_arc_coverage(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, const oatk_scg_ra_v *ra_v, oatk_scg_t *g, unsigned flags, int verbose)
 {
-    uint64_t i;
     int rc;
     (void) verbose;
     if (!ctx) return OATK_E_NODEV;
@@ -164,12 +163,41 @@ int oatk_scg_ra_arc_coverage(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, const
     {
         double *cov = (double *) rc_malloc(8 * ug->n_arc);
         rc = oatk_hip_ra_arc_coverage(ctx, &fg.g, (flags & OATK_RACOV_RESIDENT_ALN)? 0 : &fa.a, cov);
-        if (rc == OATK_OK)
-            for (i = 0; i < ug->n_arc; ++i) if (!ug->arc[i].del) ug->arc[i].cov = (uint32_t) cov[i];      /* :2131-2138 */
+        if (rc == OATK_OK) oatk_host_racov_write_arc(g, cov);
         free(cov);
     }
 done:
     rc_graph_free(&fg);
     rc_aln_free(&fa);
     return rc;
+}
+
+/* ---- what the N-handle forms (host/multi_host.c) share with the adaptors above: the graph flattened once for all handles, and the write-back ---- */
+const oatk_racov_graph_t *oatk_host_racov_graph(const oatk_scg_t *g, int with_arcs, void **keep)
+{
+    rc_graph_t *f = (rc_graph_t *) rc_malloc(sizeof(rc_graph_t));
+    rc_graph_flatten(g, with_arcs, f);
+    *keep = f;
+    return &f->g;
+}
+
+void oatk_host_racov_graph_free(void *keep)
+{
+    if (!keep) return;
+    rc_graph_free((rc_graph_t *) keep);
+    free(keep);
+}
+
+void oatk_host_racov_write_utg(oatk_scg_t *g, const double *cov)
+{
+    oatk_asmg_t *ug = g->utg_asmg;
+    uint64_t i;
+    for (i = 0; i < ug->n_vtx; ++i) ug->vtx[i].cov = (uint32_t) cov[i];             /* :2055-2056 */
+}
+
+void oatk_host_racov_write_arc(oatk_scg_t *g, const double *cov)
+{
+    oatk_asmg_t *ug = g->utg_asmg;
+    uint64_t i;
+    for (i = 0; i < ug->n_arc; ++i) if (!ug->arc[i].del) ug->arc[i].cov = (uint32_t) cov[i];      /* :2131-2138 */
 }

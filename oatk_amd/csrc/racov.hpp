@@ -4,7 +4,8 @@
 // Every double these kernels form is formed like the reference forms it: FP contraction is off inside each kernel that touches one
 // (`#pragma clang fp contract(off)`: gcc for baseline x86-64 never fuses a * b + c), and every sum whose addends may be fractional is
 // a sequential replay in the reference's order -- per unitig (EM, IQR means) or per link (duplets).  Only the first round's counts are
-// summed by atomics: integral addends, partial sums far below 2^53.
+// summed by atomics: integral addends, partial sums far below 2^53.  With reads sharded by record the replays are chained
+// through the ranks: the EM's sums and the duplet table start from what the previous rank left (a carry-in, zeros for one handle).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -367,16 +368,18 @@ __global__ void rc_covt_kernel(RcArgs a, const double *avg, double *covt)
     }
 }
 // covs[u]: u's contributions in the reference's order (:1994-1995) -- the fractional ones one by one, the runs of integral ones between
-// them by rc_add_run; x not positive and finite: all one by one
+// them by rc_add_run; x not positive and finite: all one by one.  carry (may be NULL = zeros): where every unitig's sum starts -- with reads
+// sharded by record a rank's contributions are a stretch of the reference's order, and its sums go on from the previous rank's
 __global__ void rc_em_kernel(uint64_t n_utg, const uint64_t *seg_beg, const uint64_t *seg_end, const uint32_t *blk, const double *covt,
-                             const uint32_t *ma_n, const double *avg, const uint64_t *E, const uint64_t *ef, const uint64_t *fpos, double *covs)
+                             const uint32_t *ma_n, const double *avg, const uint64_t *E, const uint64_t *ef, const uint64_t *fpos, const double *carry,
+                             double *covs)
 {
 #pragma clang fp contract(off)
     const uint64_t u = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= n_utg) return;
     const double x = avg[u];
     const uint64_t c0 = seg_beg[u], c1 = seg_end[u];
-    double s = 0.;
+    double s = carry? carry[u] : 0.;
     if (!(x > 0. && x <= DBL_MAX)) {
         for (uint64_t c = c0; c < c1; ++c) {
             const uint32_t b = blk[c];
@@ -486,7 +489,8 @@ __global__ void rc_duplet_kernel(RcArgs a, RcArcArgs g, uint64_t *key, uint32_t 
         }
     }
 }
-// kh_dbl's puts replayed per link in read order: both keys of a link (link << 1 | 0/1) live in val2[2 * link + b], have2 says which were put
+// kh_dbl's puts replayed per link in read order: both keys of a link (link << 1 | 0/1) live in val2[2 * link + b], have2 says which were put.
+// The replay goes on from what val2 / have2 hold: zeros, or with reads sharded by record the table as the previous rank left it
 __global__ void rc_link_kernel(uint64_t n, uint64_t n_link, const uint64_t *key, const uint32_t *ev, const uint8_t *bits, const double *score,
                                double *val2, uint8_t *have2)
 {
@@ -494,8 +498,8 @@ __global__ void rc_link_kernel(uint64_t n, uint64_t n_link, const uint64_t *key,
     const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || key[i] >= n_link || (i > 0 && key[i - 1] == key[i])) return;
     const uint64_t L = key[i];
-    double v[2] = {0., 0.};
-    bool h[2] = {false, false};
+    double v[2] = {val2[2 * L], val2[2 * L + 1]};
+    bool h[2] = {have2[2 * L] != 0, have2[2 * L + 1] != 0};
     for (uint64_t c = i; c < n && key[c] == L; ++c) {
         const uint32_t e = ev[c];
         const int l = bits[e] & 1, k = (bits[e] & 2)? l : l ^ 1;

@@ -152,6 +152,31 @@ class HipSyncasm:
         self._check(self.L.oatk_hip_stat_sharded(self.h, comm, C.byref(r)), "oatk_hip_stat_sharded")
         return self._stat_dict(r)
 
+    def ra_utg_coverage_sharded(self, comm, graph, aln=None, chains=None, verbose=0):
+        """ra_utg_coverage with the reads sharded by record (include/oatk_hip_racov.h): every rank calls it with the same graph; aln / chains are
+        this rank's slice (sid indexes the slice's chains), None = the handle's resident ones.  The same (avg_covs, EM iteration count) on every
+        rank, bit for bit what one handle holding all reads returns."""
+        g, keep_g = self._racov_graph(graph)
+        a, keep_a = self._racov_aln(aln)
+        r = None
+        if chains is not None:
+            keep_r = [np.ascontiguousarray(chains[0], dtype=np.uint64), np.ascontiguousarray(chains[1], dtype=np.uint64)]
+            r = _lib.RacovReads(len(keep_r[0]) - 1, keep_r[0].ctypes.data, keep_r[1].ctypes.data)
+        out = np.zeros(max(g.n_utg, 1), np.float64)
+        it = C.c_uint64(0)
+        self._check(self.L.oatk_hip_ra_utg_coverage_sharded(self.h, comm, C.byref(g), None if r is None else C.byref(r), None if a is None else C.byref(a),
+                                                            verbose, out.ctypes.data, C.byref(it)), "oatk_hip_ra_utg_coverage_sharded")
+        return out[:g.n_utg], int(it.value)
+
+    def ra_arc_coverage_sharded(self, comm, graph, aln=None):
+        """ra_arc_coverage with the reads sharded by record: the duplet sums per arc over all ranks' alignments, the same on every rank"""
+        g, keep_g = self._racov_graph(graph)
+        a, keep_a = self._racov_aln(aln)
+        out = np.zeros(max(g.n_arc, 1), np.float64)
+        self._check(self.L.oatk_hip_ra_arc_coverage_sharded(self.h, comm, C.byref(g), None if a is None else C.byref(a), out.ctypes.data),
+                    "oatk_hip_ra_arc_coverage_sharded")
+        return out[:g.n_arc]
+
     # ---- error correction (include/oatk_hip_ec.h) ----
     def ec_graph(self, light_c=0):
         """make_syncmer_graph(sr_db, scm_db, 0, 0.) + hoco arc overlaps on the device (run_syncasm.c:109-117); with light_c > 0 only what
