@@ -35,6 +35,7 @@ typedef struct {
     const uint64_t *arc_link;
     const uint8_t *arc_comp;
     const uint8_t *arc_del;
+    const uint8_t *vtx_del;    /* [n_utg] asmg_vtx_t.del (the triplet scores only; NULL = no unitig is deleted; the coverage calls never read it) */
 } oatk_racov_graph_t;
 
 /* uploaded alignments: scg_ra_v flattened in its order (sid = index of the read's chain) */
@@ -89,6 +90,27 @@ int oatk_hip_ra_arc_coverage(oatk_hip_ctx *ctx, const oatk_racov_graph_t *g, con
 int oatk_hip_ra_utg_coverage_sharded(oatk_hip_ctx *ctx, oatk_comm *comm, const oatk_racov_graph_t *g, const oatk_racov_reads_t *reads,
                                      const oatk_racov_aln_t *aln, int verbose, double *utg_cov, uint64_t *n_iter);
 int oatk_hip_ra_arc_coverage_sharded(oatk_hip_ctx *ctx, oatk_comm *comm, const oatk_racov_graph_t *g, const oatk_racov_aln_t *aln, double *arc_cov);
+
+/* ---- the spanning-triplet table of scg_multiplex (syncasm.c:1110-1166) and its lookups (:1181-1255) ----
+ * The PAIRS are what the reference looks up at :1240, in its order: for every unitig i that is not deleted and has live arcs on both
+ * sides, s over the live arcs out of i << 1 | 1 in array order (pair_in = asmg_comp_arc_id), inside it t over the live arcs out of i << 1
+ * (pair_out = asmg_arc_id).  pair_off[i .. i + 1] delimits unitig i's pairs (empty for the others), *n_pair = pair_off[n_utg].
+ * score[p] is the table's double under the key (pair_in[p], pair_out[p]), have[p] == 0 (score[p] = 0) where the reference finds no key
+ * and reads .001.  The table is built from the alignments resident in the handle (aln == NULL) or uploaded, by the reference's rules:
+ * records of three or more fragments, the unique-syncmer test for records with a fractional score, assignment on a key's first event
+ * and addition afterwards, the mirror key beside it, identity by key value.  Every double is bit for bit the reference's.
+ *   OATK_E_ARG    two consecutive fragments of a record of three or more fragments have no arc (the reference dereferences NULL), or an
+ *                 alignment does not fit the graph, or a link id is 2^32 or more.  Nothing is written.
+ *   OATK_E_NOMEM  n_pair_cap is below the number of pairs: *n_pair holds the number needed, nothing else is written.
+ * Sharded (reads by record, every rank the same graph, rank order is read order): the table -- for every group of keys that the pairs
+ * name, a group being the keys over one unordered pair of link ids, 8 doubles and 8 flags = 72 bytes; at most one group per pair -- is
+ * handed from rank to rank as a carry and the last rank's goes to everybody: per rank one small all-gather (the verdict: a missing arc on
+ * any rank is OATK_E_ARG on all) and 72 bytes per group, whatever the number of reads.  A rank that fails on its own poisons the group
+ * like the other sharded calls.  The one-handle call runs the same kernels with a zero carry and no collective. */
+int oatk_hip_ra_triplet_scores(oatk_hip_ctx *ctx, const oatk_racov_graph_t *g, const oatk_racov_aln_t *aln, uint64_t *pair_off, uint64_t n_pair_cap,
+                               uint64_t *n_pair, uint64_t *pair_in, uint64_t *pair_out, double *score, uint8_t *have);
+int oatk_hip_ra_triplet_scores_sharded(oatk_hip_ctx *ctx, oatk_comm *comm, const oatk_racov_graph_t *g, const oatk_racov_aln_t *aln, uint64_t *pair_off,
+                                       uint64_t n_pair_cap, uint64_t *n_pair, uint64_t *pair_in, uint64_t *pair_out, double *score, uint8_t *have);
 
 /* Test hook: the most LCS-matrix cells (4 bytes each) the unitig coverage may hold at once, over all reads; 0 = default (2^31, 8 GiB). */
 int oatk_hip_debug_racov_cap(oatk_hip_ctx *ctx, uint64_t cells);

@@ -62,6 +62,11 @@ int oatk_multi_scg_read_alignment(oatk_multi *m, oatk_sr_db_t *sr_db, oatk_scg_r
  * warning once and changes nothing.  The arc caller finishes with the reference's scg_refine_arc_coverage or asmg_arc_fix_cov itself. */
 int oatk_multi_scg_ra_utg_coverage(oatk_multi *m, const oatk_sr_db_t *sr_db, const oatk_scg_ra_v *ra_v, oatk_scg_t *g, int verbose);
 int oatk_multi_scg_ra_arc_coverage(oatk_multi *m, const oatk_sr_db_t *sr_db, const oatk_scg_ra_v *ra_v, oatk_scg_t *g, int verbose);
+/* oatk_scg_multiplex_plan (include/oatk_syncasm.h) over the handles' resident alignments: the triplet table is handed from handle to handle
+ * (oatk_hip_ra_triplet_scores_sharded), what travels is the size of the graph.  ra_v must be what oatk_multi_scg_read_alignment wrote last, for
+ * this g and unchanged (OATK_E_STATE otherwise); nothing is written unless the code is OATK_OK */
+int oatk_multi_scg_multiplex_plan(oatk_multi *m, const oatk_scg_ra_v *ra_v, const oatk_scg_t *g, uint32_t max_n_scm, double min_n_r, double min_d_f,
+                                  uint8_t *multi_vtx, int *updated, oatk_triplet_table *tab);
 
 #ifdef __cplusplus
 }

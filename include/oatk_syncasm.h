@@ -237,6 +237,18 @@ enum { OATK_RACOV_RESIDENT_READS = 1, OATK_RACOV_RESIDENT_ALN = 2 };
 int oatk_scg_ra_utg_coverage(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, const oatk_scg_ra_v *ra_v, oatk_scg_t *g, unsigned flags, int verbose);
 int oatk_scg_ra_arc_coverage(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, const oatk_scg_ra_v *ra_v, oatk_scg_t *g, unsigned flags, int verbose);
 
+/* scg_multiplex (syncasm.c:1090-1302) up to its rewrite of the graph: the spanning-triplet table is built on the device from the alignments
+ * (include/oatk_hip_racov.h: oatk_hip_ra_triplet_scores; with OATK_RACOV_RESIDENT_ALN from what oatk_scg_read_alignment left in ctx, nothing is
+ * uploaded), and the per-unitig decisions of :1181-1302 are taken here.  multi_vtx[n_vtx] receives the reference's marks (0 keep every arc pair,
+ * 1 threaded, 2 singleton), *updated what scg_multiplex would return.  tab (may be NULL) receives the table's entries that the lookups at :1240
+ * find, n of them, as (l_in, l_out, value): a maintainer of the reference fills tri_s from them in place of the loop at :1110-1166 and keeps
+ * the rewrite (:1309-1472) as it is.  Free it with oatk_triplet_table_free.  g is not changed.  OATK_E_ARG: two consecutive
+ * fragments of an alignment of three or more have no arc (the reference would crash), or an alignment does not fit the graph. */
+typedef struct { uint64_t n, m; uint64_t *l_in, *l_out; double *val; } oatk_triplet_table;
+int oatk_scg_multiplex_plan(oatk_hip_ctx *ctx, const oatk_scg_ra_v *ra_v, const oatk_scg_t *g, unsigned flags, uint32_t max_n_scm, double min_n_r,
+                            double min_d_f, uint8_t *multi_vtx, int *updated, oatk_triplet_table *tab);
+void oatk_triplet_table_free(oatk_triplet_table *tab);
+
 /* same destructors as the reference (syncmer.c:1047-1110) for objects that are not handed to it */
 void oatk_sr_db_clean(oatk_sr_db_t *sr_db);
 

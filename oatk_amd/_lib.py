@@ -53,10 +53,12 @@ EXPORTS = [
     "oatk_hip_ec_reserve_import", "oatk_hip_consensus", "oatk_hip_consensus_ids", "oatk_hip_ingest", "oatk_hip_ingest_host", "oatk_hip_scan_ingested", "oatk_hip_stat", "oatk_hip_stat_keys", "oatk_hip_stat_from_keys",
     "oatk_hip_asm_graph", "oatk_hip_asm_pairs", "oatk_hip_asm_graph_from_pairs", "oatk_hip_overlap_hist", "oatk_hip_overlap_pairs", "oatk_hip_overlap_hist_from_pairs", "oatk_hip_read_alignment", "oatk_hip_debug_align_two_pass",
     "oatk_hip_ra_utg_coverage", "oatk_hip_ra_arc_coverage", "oatk_hip_debug_racov_cap", "oatk_hip_ra_utg_coverage_sharded", "oatk_hip_ra_arc_coverage_sharded",
+    "oatk_hip_ra_triplet_scores", "oatk_hip_ra_triplet_scores_sharded",
 ]
 
 # the N-handle mirror in liboatk_host.so (include/oatk_multi.h) of entry points listed above; EXPORTS itself is checked against liboatk_hip.so
-HOST_EXPORTS = ["oatk_multi_scg_ra_utg_coverage", "oatk_multi_scg_ra_arc_coverage"]
+HOST_EXPORTS = ["oatk_multi_scg_ra_utg_coverage", "oatk_multi_scg_ra_arc_coverage", "oatk_scg_multiplex_plan", "oatk_multi_scg_multiplex_plan",
+                "oatk_triplet_table_free"]
 
 
 def load_host():
@@ -82,8 +84,17 @@ def load_host():
     H.oatk_multi_scg_read_alignment.argtypes = [vp, vp, vp, vp, C.c_int, C.POINTER(C.c_uint64)]
     H.oatk_multi_scg_ra_utg_coverage.argtypes = [vp, vp, vp, vp, C.c_int]
     H.oatk_multi_scg_ra_arc_coverage.argtypes = [vp, vp, vp, vp, C.c_int]
+    H.oatk_scg_multiplex_plan.argtypes = [vp, vp, vp, C.c_uint, C.c_uint32, C.c_double, C.c_double, vp, C.POINTER(C.c_int), C.POINTER(TripletTable)]
+    H.oatk_multi_scg_multiplex_plan.argtypes = [vp, vp, vp, C.c_uint32, C.c_double, C.c_double, vp, C.POINTER(C.c_int), C.POINTER(TripletTable)]
+    H.oatk_triplet_table_free.restype = None
+    H.oatk_triplet_table_free.argtypes = [C.POINTER(TripletTable)]
     H.oatk_host_debug_window.argtypes = [C.c_uint64]
     return H
+
+
+class TripletTable(C.Structure):
+    """oatk_triplet_table (include/oatk_syncasm.h): the entries of scg_multiplex's tri_s that its lookups find"""
+    _fields_ = [("n", C.c_uint64), ("m", C.c_uint64), ("l_in", C.POINTER(C.c_uint64)), ("l_out", C.POINTER(C.c_uint64)), ("val", C.POINTER(C.c_double))]
 
 
 class EcGraph(C.Structure):
@@ -102,7 +113,7 @@ class RacovGraph(C.Structure):
     """oatk_racov_graph_t (include/oatk_hip_racov.h): what scg_ra_utg_coverage / scg_ra_arc_coverage read from scg_t, flattened, host pointers"""
     _fields_ = [("n_scm", C.c_uint64), ("n_utg", C.c_uint64), ("n_arc", C.c_uint64), ("su_off", C.c_void_p), ("su_uid", C.c_void_p), ("su_pos", C.c_void_p),
                 ("scm_cov", C.c_void_p), ("utg_off", C.c_void_p), ("utg_a", C.c_void_p), ("idx_p", C.c_void_p), ("idx_n", C.c_void_p), ("arc_v", C.c_void_p),
-                ("arc_w", C.c_void_p), ("arc_link", C.c_void_p), ("arc_comp", C.c_void_p), ("arc_del", C.c_void_p)]
+                ("arc_w", C.c_void_p), ("arc_link", C.c_void_p), ("arc_comp", C.c_void_p), ("arc_del", C.c_void_p), ("vtx_del", C.c_void_p)]
 
 
 class RacovAln(C.Structure):
@@ -233,6 +244,9 @@ def load():
     L.oatk_hip_debug_racov_cap.argtypes = [vp, C.c_uint64]
     L.oatk_hip_ra_utg_coverage_sharded.argtypes = [vp, vp, C.POINTER(RacovGraph), C.POINTER(RacovReads), C.POINTER(RacovAln), C.c_int, vp, C.POINTER(C.c_uint64)]
     L.oatk_hip_ra_arc_coverage_sharded.argtypes = [vp, vp, C.POINTER(RacovGraph), C.POINTER(RacovAln), vp]
+    u64p = C.POINTER(C.c_uint64)
+    L.oatk_hip_ra_triplet_scores.argtypes = [vp, C.POINTER(RacovGraph), C.POINTER(RacovAln), vp, C.c_uint64, u64p, vp, vp, vp, vp]
+    L.oatk_hip_ra_triplet_scores_sharded.argtypes = [vp, vp, C.POINTER(RacovGraph), C.POINTER(RacovAln), vp, C.c_uint64, u64p, vp, vp, vp, vp]
     L.oatk_hip_overlap_pairs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.oatk_hip_overlap_hist_from_pairs.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.oatk_hip_overlap_hist.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

@@ -448,6 +448,7 @@ static void t_collect(oatk_hip_ctx *ctx, int first, int last)
 #include "api_multi.inc"
 #include "api_multi_tail.inc"
 #include "api_racov.inc"
+#include "api_multiplex.inc"
 
 static void staging_free(oatk_hip_ctx *ctx)
 {

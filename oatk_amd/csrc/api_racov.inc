@@ -10,7 +10,8 @@ struct RcState {
     DevBuf flag, pos, rd_beg, need_c, need_l, need_u, cell_off, lcs_off, u_off, cells, lcs, rec_lb, rec_ln, st_frg, st_lcsb, st_uid, st_beg, st_len;
     DevBuf ma_n, ma_u, nb, cnt, vals, vals2, avg, covs, covt, key, val, key2, val2, seg_beg, seg_end, diff, err, tmp;
     DevBuf blk_a, em_w, em_e, em_fl, em_ef, em_fpos, ev_key, ev_key2, ev_val, ev_val2, ev_bits, ev_score, lv, arc_out;
-    DevBuf carry;                                  // sharded: what the previous rank hands on (the EM's sums; the duplet table)
+    DevBuf carry;                                  // sharded: what the previous rank hands on (the EM's sums; the duplet table; the triplet table)
+    DevBuf t_grp, t_pslot, t_score, t_have, t_first, t_last;        // the triplet scores (api_multiplex.inc): the groups of keys, every pair's slot, the results
     uint64_t cap_cells = 0;
 };
 
@@ -23,7 +24,8 @@ static void rc_state_free(oatk_hip_ctx *ctx)
                      &g->flag, &g->pos, &g->rd_beg, &g->need_c, &g->need_l, &g->need_u, &g->cell_off, &g->lcs_off, &g->u_off, &g->cells, &g->lcs, &g->rec_lb,
                      &g->rec_ln, &g->st_frg, &g->st_lcsb, &g->st_uid, &g->st_beg, &g->st_len, &g->ma_n, &g->ma_u, &g->nb, &g->cnt, &g->vals, &g->vals2,
                      &g->avg, &g->covs, &g->covt, &g->key, &g->val, &g->key2, &g->val2, &g->seg_beg, &g->seg_end, &g->diff, &g->err, &g->tmp,
-                     &g->blk_a, &g->em_w, &g->em_e, &g->em_fl, &g->em_ef, &g->em_fpos, &g->ev_key, &g->ev_key2, &g->ev_val, &g->ev_val2, &g->ev_bits, &g->ev_score, &g->lv, &g->arc_out, &g->carry};
+                     &g->blk_a, &g->em_w, &g->em_e, &g->em_fl, &g->em_ef, &g->em_fpos, &g->ev_key, &g->ev_key2, &g->ev_val, &g->ev_val2, &g->ev_bits, &g->ev_score, &g->lv, &g->arc_out, &g->carry,
+                     &g->t_grp, &g->t_pslot, &g->t_score, &g->t_have, &g->t_first, &g->t_last};
     for (DevBuf *b : all) b->release();
     delete g;
     ctx->rc = nullptr;

@@ -35,6 +35,14 @@ const oatk_racov_graph_t *oatk_host_racov_graph(const oatk_scg_t *g, int with_ar
 void oatk_host_racov_graph_free(void *keep);
 void oatk_host_racov_write_utg(oatk_scg_t *g, const double *cov);
 void oatk_host_racov_write_arc(oatk_scg_t *g, const double *cov);
+/* scg_ra_v flattened for an upload (NULL: a value does not fit the device's fields, or a sid is no read); free with oatk_host_racov_aln_free(keep) either way */
+const oatk_racov_aln_t *oatk_host_racov_aln(const oatk_scg_ra_v *v, uint64_t n_reads, void **keep);
+void oatk_host_racov_aln_free(void *keep);
+/* host/multiplex_host.c for host/multi_host.c: how many (in, out) arc pairs scg_multiplex looks up in g, and its decisions (syncasm.c:1181-1302) from their
+ * scores in the order of include/oatk_hip_racov.h; tab (may be NULL) receives the entries that exist.  -1: the pairs are not those of g */
+uint64_t oatk_host_multiplex_pairs(const oatk_scg_t *g);
+int oatk_host_multiplex_decide(const oatk_scg_t *g, const uint64_t *pair_off, const uint64_t *pair_in, const uint64_t *pair_out, const double *score,
+                               const uint8_t *have, uint32_t max_n_scm, double min_n_r, double min_d_f, uint8_t *multi_vtx, int *updated, oatk_triplet_table *tab);
 
 
 typedef struct { uint8_t *p, *end; } oatk_name_bump_t;

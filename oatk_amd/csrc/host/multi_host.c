@@ -522,3 +522,37 @@ int oatk_multi_scg_ra_arc_coverage(oatk_multi *m, const oatk_sr_db_t *sr_db, con
     if ((rc = racov_resident(m, ra_v, g)) != OATK_OK) return rc;
     return racov_run(m, g, 1, 0);
 }
+
+/* ------------------------------------------------------------- scg_multiplex ------------------------------------------------------------- */
+
+typedef struct { const oatk_racov_graph_t *g; uint64_t cap, np[64], *off[64], *p_in[64], *p_out[64]; double *score[64]; uint8_t *have[64]; } multiplex_arg_t;
+
+static int multiplex_rank(oatk_multi *m, int rank, void *arg)
+{
+    multiplex_arg_t *a = (multiplex_arg_t *) arg;
+    return oatk_hip_ra_triplet_scores_sharded(m->ctx[rank], m->comm[rank], a->g, 0, a->off[rank], a->cap, &a->np[rank], a->p_in[rank], a->p_out[rank],
+                                              a->score[rank], a->have[rank]);
+}
+
+int oatk_multi_scg_multiplex_plan(oatk_multi *m, const oatk_scg_ra_v *ra_v, const oatk_scg_t *g, uint32_t max_n_scm, double min_n_r, double min_d_f,
+                                  uint8_t *multi_vtx, int *updated, oatk_triplet_table *tab)
+{
+    void *keep = 0;
+    multiplex_arg_t *a;
+    int r, rc;
+    if (!m) return OATK_E_NODEV;
+    if ((rc = racov_resident(m, ra_v, g)) != OATK_OK) return rc;
+    a = (multiplex_arg_t *) calloc(1, sizeof(multiplex_arg_t));
+    a->g = oatk_host_racov_graph(g, 1, &keep), a->cap = oatk_host_multiplex_pairs(g);      /* flattened once, read by every handle's thread */
+    for (r = 0; r < m->n; ++r) {
+        a->off[r] = (uint64_t *) xmalloc(8 * (g->utg_asmg->n_vtx + 1)), a->p_in[r] = (uint64_t *) xmalloc(8 * a->cap + 8), a->p_out[r] = (uint64_t *) xmalloc(8 * a->cap + 8);
+        a->score[r] = (double *) xmalloc(8 * a->cap + 8), a->have[r] = (uint8_t *) xmalloc(a->cap + 8);
+    }
+    rc = run_ranks(m, multiplex_rank, a);
+    if (rc == OATK_OK && oatk_host_multiplex_decide(g, a->off[0], a->p_in[0], a->p_out[0], a->score[0], a->have[0], max_n_scm, min_n_r, min_d_f, multi_vtx, updated, tab))
+        rc = OATK_E_STATE;                                                         /* (the same scores on every rank) */
+    for (r = 0; r < m->n; ++r) { free(a->off[r]); free(a->p_in[r]); free(a->p_out[r]); free(a->score[r]); free(a->have[r]); }
+    oatk_host_racov_graph_free(keep);
+    free(a);
+    return rc;
+}

@@ -22,7 +22,7 @@ typedef struct {
     oatk_racov_graph_t g;
     uint64_t *su_off, *su_uid, *utg_off, *utg_a, *arc_v, *arc_w, *arc_link;
     uint32_t *su_pos, *scm_cov;
-    uint8_t *arc_comp, *arc_del;
+    uint8_t *arc_comp, *arc_del, *vtx_del;
 } rc_graph_t;
 
 static void *rc_malloc(size_t n)
@@ -65,12 +65,15 @@ static void rc_graph_flatten(const oatk_scg_t *g, int with_arcs, rc_graph_t *f)
     }
     f->g.n_arc = na, f->g.idx_p = ug->idx_p, f->g.idx_n = ug->idx_n;
     f->g.arc_v = f->arc_v, f->g.arc_w = f->arc_w, f->g.arc_link = f->arc_link, f->g.arc_comp = f->arc_comp, f->g.arc_del = f->arc_del;
+    f->vtx_del = (uint8_t *) rc_malloc(nu);
+    for (i = 0; i < nu; ++i) f->vtx_del[i] = ug->vtx[i].del;
+    f->g.vtx_del = f->vtx_del;
 }
 
 static void rc_graph_free(rc_graph_t *f)
 {
     free(f->su_off); free(f->su_uid); free(f->su_pos); free(f->scm_cov); free(f->utg_off); free(f->utg_a);
-    free(f->arc_v); free(f->arc_w); free(f->arc_link); free(f->arc_comp); free(f->arc_del);
+    free(f->arc_v); free(f->arc_w); free(f->arc_link); free(f->arc_comp); free(f->arc_del); free(f->vtx_del);
 }
 
 typedef struct {
@@ -185,6 +188,20 @@ void oatk_host_racov_graph_free(void *keep)
 {
     if (!keep) return;
     rc_graph_free((rc_graph_t *) keep);
+    free(keep);
+}
+
+const oatk_racov_aln_t *oatk_host_racov_aln(const oatk_scg_ra_v *v, uint64_t n_reads, void **keep)
+{
+    rc_aln_t *f = (rc_aln_t *) rc_malloc(sizeof(rc_aln_t));
+    *keep = f;
+    return rc_aln_flatten(v, n_reads, f)? 0 : &f->a;
+}
+
+void oatk_host_racov_aln_free(void *keep)
+{
+    if (!keep) return;
+    rc_aln_free((rc_aln_t *) keep);
     free(keep);
 }
 

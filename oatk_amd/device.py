@@ -372,7 +372,44 @@ class HipSyncasm:
     def _racov_graph(self, graph):
         keep = {k: np.ascontiguousarray(graph.get(k, np.zeros(0)), dtype=dt) for k, dt in self._RACOV_GRAPH}
         g = _lib.RacovGraph(int(graph["n_scm"]), len(keep["utg_off"]) - 1, len(keep["arc_w"]), *[keep[k].ctypes.data for k, _ in self._RACOV_GRAPH])
+        if graph.get("vtx_del") is not None:
+            keep["vtx_del"] = np.ascontiguousarray(graph["vtx_del"], dtype=np.uint8)
+            g.vtx_del = keep["vtx_del"].ctypes.data
         return g, keep
+
+    def _triplet_scores(self, comm, graph, aln, n_pair_cap):
+        g, keep_g = self._racov_graph(graph)
+        a, keep_a = self._racov_aln(aln)
+        cap = n_pair_cap
+        if cap is None:                          # what the graph holds: live arcs in x live arcs out of every unitig that is alive
+            live = np.add.reduceat(np.append(keep_g["arc_del"] == 0, False).astype(np.int64),
+                                   np.minimum(np.stack([keep_g["idx_p"], keep_g["idx_p"] + keep_g["idx_n"]], 1).ravel(), g.n_arc).astype(np.int64))[::2]
+            live = np.where(keep_g["idx_n"] > 0, live, 0)
+            alive = 1 - keep_g["vtx_del"].astype(np.int64) if "vtx_del" in keep_g else 1
+            cap = int((live[0::2] * live[1::2] * alive).sum())
+        off = np.zeros(g.n_utg + 1, np.uint64)
+        p_in, p_out = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint64)
+        score, have = np.zeros(max(cap, 1), np.float64), np.zeros(max(cap, 1), np.uint8)
+        n = C.c_uint64(0)
+        args = (C.byref(g), None if a is None else C.byref(a), off.ctypes.data, cap, C.byref(n), p_in.ctypes.data, p_out.ctypes.data, score.ctypes.data,
+                have.ctypes.data)
+        if comm is None:
+            rc = self.L.oatk_hip_ra_triplet_scores(self.h, *args)
+        else:
+            rc = self.L.oatk_hip_ra_triplet_scores_sharded(self.h, comm, *args)
+        self._check(rc, "oatk_hip_ra_triplet_scores" + ("" if comm is None else "_sharded"))
+        k = int(n.value)
+        return {"pair_off": off, "pair_in": p_in[:k], "pair_out": p_out[:k], "score": score[:k], "have": have[:k]}
+
+    def ra_triplet_scores(self, graph, aln=None, n_pair_cap=None):
+        """the spanning-triplet scores of scg_multiplex (syncasm.c:1110-1166) for the (in, out) arc pairs it looks up (:1240), in its order: a dict
+        of pair_off [n_utg + 1], pair_in, pair_out (arc ids), score (float64) and have (0: the reference reads .001).  graph as for
+        ra_arc_coverage plus vtx_del; aln None = the resident alignments."""
+        return self._triplet_scores(None, graph, aln, n_pair_cap)
+
+    def ra_triplet_scores_sharded(self, comm, graph, aln=None, n_pair_cap=None):
+        """ra_triplet_scores with the reads sharded by record: the same result on every rank, bit for bit the one-handle call's"""
+        return self._triplet_scores(comm, graph, aln, n_pair_cap)
 
     def _racov_aln(self, aln):
         if aln is None:
