@@ -11,7 +11,7 @@
 struct EcState {
     DevBuf idx_p, idx_n, arc_v, arc_w, arc_ls, arc_cov, arc_del, conv;   // graph (device copy)
     DevBuf scm_del, err_del, vtx_hs_off, vtx_mpos;
-    DevBuf copy_n, n_blocks, n_blocks64, blk_off, work, out, path_pool, cursor, todo, todo2, slabs, big_slabs, os_slabs;
+    DevBuf copy_n, seg, keep_all, n_blocks, n_blocks64, blk_off, work, out, path_pool, cursor, todo, todo2, slabs, big_slabs, os_slabs;
     DevBuf hyb_slabs[16];         // the hybrid tier's HBM slabs, one buffer per launch of a call (launches may run side by side), sized by the blocks the launch has
     hipStream_t aux[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};       // the larger solver tiers run beside the first one ([4]: of the lowest priority level)
     hipEvent_t aux_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, fork_ev = nullptr;
@@ -43,7 +43,7 @@ static void ec_state_free(oatk_hip_ctx *ctx)
     if (!ctx->ec) return;
     EcState *e = ctx->ec;
     DevBuf *all[] = {&e->idx_p, &e->idx_n, &e->arc_v, &e->arc_w, &e->arc_ls, &e->arc_cov, &e->arc_del, &e->conv, &e->scm_del, &e->err_del,
-                     &e->vtx_hs_off, &e->vtx_mpos, &e->copy_n, &e->n_blocks, &e->n_blocks64, &e->blk_off, &e->work, &e->out, &e->path_pool, &e->cursor,
+                     &e->vtx_hs_off, &e->vtx_mpos, &e->copy_n, &e->seg, &e->keep_all, &e->n_blocks, &e->n_blocks64, &e->blk_off, &e->work, &e->out, &e->path_pool, &e->cursor,
                      &e->todo, &e->todo2, &e->slabs, &e->big_slabs, &e->os_slabs, &e->hyb_slabs[0], &e->hyb_slabs[1], &e->hyb_slabs[2], &e->hyb_slabs[3], &e->hyb_slabs[4], &e->hyb_slabs[5], &e->hyb_slabs[6], &e->hyb_slabs[7], &e->hyb_slabs[8], &e->hyb_slabs[9], &e->hyb_slabs[10], &e->hyb_slabs[11], &e->hyb_slabs[12], &e->hyb_slabs[13], &e->hyb_slabs[14], &e->hyb_slabs[15], &e->new_n, &e->new_n64, &e->new_off, &e->new_k, &e->new_m, &e->new_s, &e->stats,
                      &e->live32, &e->live64, &e->live_off, &e->larc, &e->lidx_p, &e->lidx_n, &e->cov, &e->fwd, &e->key_id, &e->key_sorted, &e->val_occ, &e->occ, &e->occ_off, &e->cov64,
                      &e->g_keys, &e->g_keys2, &e->g_ukeys, &e->g_counts, &e->g_nruns, &e->g_nout, &e->g_nout64, &e->g_outoff, &e->g_akey,
@@ -729,6 +729,7 @@ struct EcKnobs {
     int32_t heavy_cap2 = 0;       // OATK_DEBUG_EC_HEAVY_CAP2: longest block of the second class (tests: blocks the cases would not send there)
     int32_t heavy_fl = 0;         // OATK_DEBUG_EC_HEAVY_FL: bytes of the classes' LDS frame arena (tests: 64 sends every frame to HBM)
     int32_t waves = 32;           // OATK_DEBUG_EC_WAVES: first-tier waves per CU (tools/solverbench.py)
+    bool assemble_walk = false;   // OATK_DEBUG_EC_ASSEMBLE_WALK=1: the corrected chains by a third walk (ec_new_n_kernel, ec_assemble_wave_kernel<1>) instead of from the blocks' descriptors (A/B, tests)
 };
 static EcKnobs ec_knobs_read()
 {
@@ -741,6 +742,7 @@ static EcKnobs ec_knobs_read()
     k.min_nw = num("OATK_DEBUG_EC_FUSED_MIN_NW", 2, 0);
     k.heavy_cap2 = num("OATK_DEBUG_EC_HEAVY_CAP2", 1, 0), k.heavy_fl = num("OATK_DEBUG_EC_HEAVY_FL", 64, 0) & ~7;
     k.waves = num("OATK_DEBUG_EC_WAVES", 1, 32);
+    { const char *e = getenv("OATK_DEBUG_EC_ASSEMBLE_WALK"); k.assemble_walk = e && e[0] == '1'; }
     return k;
 }
 
@@ -1282,8 +1284,9 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     { int rc = ec_exclusive_scan_u32(ctx, e, e->n_blocks, e->n_blocks64, e->blk_off, nr, &n_work); if (rc) return rc; }
     EENSURE(work, (n_work + 1) * sizeof(EcWork)); EENSURE(out, (n_work + 1) * sizeof(EcBlockOut));
     e->n_work = n_work;
-    EENSURE(new_n, (nr + 1) * 4); EENSURE(copy_n, (nr + 1) * 4);
-    hipLaunchKernelGGL(ec_list_blocks_wave_kernel, rblocks, dim3(256), 0, ctx->stream, rd, lv, (const uint8_t *) e->scm_del.p, e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->copy_n.as<uint32_t>());
+    EENSURE(new_n, (nr + 1) * 4); EENSURE(copy_n, (nr + 1) * 4); EENSURE(seg, (n_work + 1) * sizeof(EcSeg)); EENSURE(keep_all, nr + 1);
+    hipLaunchKernelGGL(ec_list_blocks_wave_kernel, rblocks, dim3(256), 0, ctx->stream, rd, lv, (const uint8_t *) e->scm_del.p, e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->copy_n.as<uint32_t>(),
+                       e->seg.as<EcSeg>(), e->keep_all.as<uint8_t>());
     t_end(ctx, OATK_T_EC_MARK);
     t_begin(ctx, OATK_T_EC_SOLVE);
 
@@ -1325,10 +1328,12 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     aa.rd = rd, aa.scm_del = (const uint8_t *) e->scm_del.p, aa.scm_s = g.scm_s, aa.blk_off = e->blk_off.as<uint64_t>();
     aa.out = e->out.as<EcBlockOut>(), aa.path_pool = e->path_pool.as<uint64_t>(), aa.new_n = e->new_n.as<uint32_t>(), aa.new_off = nullptr;
     aa.new_k_mer = nullptr, aa.new_s_mer = nullptr, aa.new_m_pos = nullptr, aa.old_s_mer = ctx->pos_smer.as<uint64_t>();
-    aa.stats = (unsigned long long *) e->stats.p, aa.pass = 1;
+    aa.stats = (unsigned long long *) e->stats.p, aa.pass = 1, aa.seg = e->seg.as<EcSeg>(), aa.keep_all = e->keep_all.as<uint8_t>();
     if (n_work) hipLaunchKernelGGL(ec_block_stats_kernel, dim3((unsigned) (n_work / 256 + 1 < 512? n_work / 256 + 1 : 512)), dim3(256), 0, ctx->stream, e->work.as<EcWork>(),
                                    e->out.as<EcBlockOut>(), n_work, (unsigned long long *) e->stats.p);
-    hipLaunchKernelGGL(ec_new_n_kernel, blocks(nr), dim3(256), 0, ctx->stream, nr, e->copy_n.as<uint32_t>(), e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->out.as<EcBlockOut>(), e->new_n.as<uint32_t>());
+    // the chains' lengths and then the chains from the descriptors the list walk left, nobody walking a chain again (ec.hpp: EcSeg)
+    if (kn.assemble_walk) hipLaunchKernelGGL(ec_new_n_kernel, blocks(nr), dim3(256), 0, ctx->stream, nr, e->copy_n.as<uint32_t>(), e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->out.as<EcBlockOut>(), e->new_n.as<uint32_t>());
+    else hipLaunchKernelGGL(ec_new_n_seg_kernel, blocks(nr), dim3(256), 0, ctx->stream, nr, e->copy_n.as<uint32_t>(), e->blk_off.as<uint64_t>(), e->seg.as<EcSeg>(), e->out.as<EcBlockOut>(), e->new_n.as<uint32_t>());
     uint64_t tot = 0;
     { int rc = ec_exclusive_scan_u32(ctx, e, e->new_n, e->new_n64, e->new_off, nr, &tot); if (rc) return rc; }
     e->new_tot = tot;
@@ -1336,7 +1341,8 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     EENSURE(key_id, (tot + 1) * 4); EENSURE(key_sorted, (tot + 1) * 4); EENSURE(val_occ, (tot + 1) * 8); EENSURE(occ, (tot + 1) * 8);
     aa.new_off = e->new_off.as<uint64_t>(), aa.new_k_mer = e->new_k.as<uint64_t>(), aa.new_m_pos = e->new_m.as<uint32_t>(), aa.new_s_mer = e->new_s.as<uint64_t>();
     aa.key_id = e->key_id.as<uint32_t>(), aa.val_occ = e->val_occ.as<uint64_t>(), aa.sid0 = ctx->sid0;
-    hipLaunchKernelGGL(ec_assemble_wave_kernel<1>, rblocks, dim3(256), 0, ctx->stream, aa);
+    if (kn.assemble_walk) hipLaunchKernelGGL(ec_assemble_wave_kernel<1>, rblocks, dim3(256), 0, ctx->stream, aa);
+    else hipLaunchKernelGGL(ec_assemble_seg_kernel, rblocks, dim3(256), 0, ctx->stream, aa);
 
     // ---- update_syncmer_db ----
     EENSURE(cov, (nv + 1) * 4); EENSURE(fwd, (nv + 1) * 4);

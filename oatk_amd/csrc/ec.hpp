@@ -198,6 +198,37 @@ struct __attribute__((aligned(16))) EcWork {   // one block, self-contained for 
     uint32_t pad;                 // (list kernel -> ec_new_n_kernel) chain entries the read keeps if this block is NOT corrected (syncerr.c:533-542)
 };
 
+// What the assembly needs of a block besides its outcome, left by the walk that lists the blocks (one per EcWork, same index): the chain indices that
+// delimit it.  With them the corrected chain is a table of segments -- per block the originals kept in front of it, then its body (the optimum path's
+// interior, or the originals it keeps) -- and nobody walks the chain again (ec_new_n_seg_kernel, ec_assemble_seg_kernel).
+#define EC_SEG_R 1u               // leading block (EcBlock::r)
+#define EC_SEG_OPEN 2u            // end_utg == EC_NONE
+struct EcSeg {
+    uint32_t beg;                 // EcBlock::beg
+    uint32_t end_fl;              // min(EcBlock::end, n) << 2 | EC_SEG_*
+};
+__device__ __forceinline__ EcSeg ec_seg_of(const EcBlock &b, int32_t n)
+{
+    EcSeg d;
+    d.beg = (uint32_t) b.beg;
+    d.end_fl = (uint32_t) (b.end < n? b.end : n) << 2 | (b.end_utg == EC_NONE? EC_SEG_OPEN : 0u) | (b.r? EC_SEG_R : 0u);
+    return d;
+}
+// original entries kept in front of a block: from the end of the block before it (0 for the first) up to and including its left anchor -- what on_copy sees
+// between two blocks (ec_blocks: [end, beg) with beg one past the next block's anchor); a leading block starts the chain and has nothing in front
+__device__ __forceinline__ uint32_t ec_seg_front(const EcSeg &d, uint32_t prev_end)
+{
+    return (d.end_fl & EC_SEG_R) || d.beg + 1u <= prev_end? 0u : d.beg + 1u - prev_end;
+}
+// entries a block contributes itself: the optimum path's interior (syncerr.c:513-532), or the originals it keeps when it is not corrected (:533-542)
+__device__ __forceinline__ uint32_t ec_seg_body(const EcSeg &d, uint32_t status, uint32_t np_)
+{
+    const int32_t np = (int32_t) np_, beg = (int32_t) d.beg, end = (int32_t) (d.end_fl >> 2);
+    if (status == EC_SUCCESS) return d.end_fl & EC_SEG_R? (uint32_t) (np >= 1? np - 1 : 0) : (uint32_t) ((np >= 2? np - 2 : 0) + ((d.end_fl & EC_SEG_OPEN) && np > 1? 1 : 0));
+    if (d.end_fl & EC_SEG_R) return (uint32_t) beg;                     // copy(0, beg)
+    return end > beg + 1? (uint32_t) (end - beg - 1) : 0u;             // copy(beg + 1, min(end, n)), which is empty when beg + 1 >= n
+}
+
 __global__ void ec_live_flag_kernel(uint64_t n_arc, const uint8_t *arc_del, uint32_t *live)
 {
     uint64_t a = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -247,6 +278,8 @@ struct EcAssembleArgs {
     const uint64_t *old_s_mer;
     unsigned long long *stats;    // [11]
     int pass;
+    const EcSeg *seg;             // [n_work] (ec_assemble_seg_kernel)
+    const uint8_t *keep_all;      // [n_reads] 1 = the read has no good syncmer and keeps its chain (ec_assemble_seg_kernel)
 };
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -381,7 +414,8 @@ __global__ __launch_bounds__(256) void ec_count_blocks_wave_kernel(EcReads rd, c
     }
 }
 
-__global__ __launch_bounds__(256) void ec_list_blocks_wave_kernel(EcReads rd, EcLive lv, const uint8_t *scm_del, const uint64_t *blk_off, EcWork *work, uint32_t *copy_n)
+__global__ __launch_bounds__(256) void ec_list_blocks_wave_kernel(EcReads rd, EcLive lv, const uint8_t *scm_del, const uint64_t *blk_off, EcWork *work, uint32_t *copy_n, EcSeg *seg,
+                                                                  uint8_t *keep_all)
 {
     const uint64_t r0 = ((uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6)) * ECR_RPW;
     const int lane = threadIdx.x & 63;
@@ -389,14 +423,19 @@ __global__ __launch_bounds__(256) void ec_list_blocks_wave_kernel(EcReads rd, Ec
     EcrRead q[ECR_RPW];
     ecr_load(rd, scm_del, r0, lane, q);
     EcWork *wq[ECR_RPW];
+    EcSeg *sq[ECR_RPW];
     uint32_t hq[ECR_RPW];
 #pragma unroll
-    for (int k = 0; k < ECR_RPW; ++k) wq[k] = q[k].n >= 0? work + blk_off[q[k].r] : nullptr, hq[k] = q[k].n >= 0? (uint32_t) (rd.off[q[k].r] >> 6) : 0u;
+    for (int k = 0; k < ECR_RPW; ++k) {
+        const uint64_t b0 = q[k].n >= 0? blk_off[q[k].r] : 0;
+        wq[k] = q[k].n >= 0? work + b0 : nullptr, sq[k] = q[k].n >= 0? seg + b0 : nullptr, hq[k] = q[k].n >= 0? (uint32_t) (rd.off[q[k].r] >> 6) : 0u;
+    }
 #pragma unroll
     for (int k = 0; k < ECR_RPW; ++k) {
         const EcrRead &x = q[k];
         if (x.n < 0) continue;
         EcWork *w = wq[k];
+        EcSeg *sg = sq[k];
         const uint32_t hs16 = hq[k];
         const int32_t n = x.n;
         auto put = [&](int i, const EcBlock &b) {
@@ -407,6 +446,7 @@ __global__ __launch_bounds__(256) void ec_list_blocks_wave_kernel(EcReads rd, Ec
             const int32_t last = b.end < n? b.end : n;
             y.pad = b.r? (uint32_t) b.beg : (b.beg + 1 < n && last > b.beg + 1? (uint32_t) (last - b.beg - 1) : 0u);
             w[i] = y;
+            sg[i] = ec_seg_of(b, n);
         };
         // ... and what it copies between the blocks whatever becomes of them; a read without a good syncmer keeps its chain (syncerr.c:562-572)
         uint32_t cp = 0;
@@ -415,6 +455,7 @@ __global__ __launch_bounds__(256) void ec_list_blocks_wave_kernel(EcReads rd, Ec
             if (lane == 0) {
                 const int nbs = ec_blocks(scm_del, rd.k_mer + x.o, rd.m_pos + x.o, x.n, x.hoco_l, rd.K, put, on_copy);
                 copy_n[x.r] = nbs < 0? (uint32_t) n : cp;
+                keep_all[x.r] = nbs < 0;
             }
             continue;
         }
@@ -424,7 +465,7 @@ __global__ __launch_bounds__(256) void ec_list_blocks_wave_kernel(EcReads rd, Ec
         const int nb = ec_blocks_wave(lane, x.n, x.km, x.mp, x.del, x.hoco_l, rd.K,
                                       [&](int i, const EcBlock &b) { if (i < 64) { if (lane == i) mine = b; } else if (lane == 0) put(i, b); }, on_copy);
         if (lane < nb) put(lane, mine);
-        if (lane == 0) copy_n[x.r] = nb < 0? (uint32_t) n : cp;
+        if (lane == 0) copy_n[x.r] = nb < 0? (uint32_t) n : cp, keep_all[x.r] = nb < 0;
     }
 }
 
@@ -597,6 +638,122 @@ __global__ __launch_bounds__(256) void ec_assemble_wave_kernel(EcAssembleArgs a)
             wpos += (uint32_t) n;
         }
         if (!PASS && lane == 0) a.new_n[x.r] = (uint32_t) (wpos - w0);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The corrected chains WITHOUT a walk: from the descriptors the list walk left (EcSeg) and the blocks' outcomes.  A read with blocks 0 .. nb - 1 becomes
+//   front(0) body(0) front(1) body(1) ... front(nb - 1) body(nb - 1)
+// front(i) = the originals [end(i - 1), beg(i)] (ec_seg_front), body(i) = ec_seg_body entries; the last block of a read always ends at or beyond n (the walk
+// leaves its loop nowhere else), so nothing follows it.  A read without a block is one without a good syncmer (the first round of the walk either finds the
+// leading block or gives the read up) and keeps its chain; the list walk says so in keep_all[] all the same.
+// ---------------------------------------------------------------------------------------------------------------------------------
+// the chains' lengths: a lane per read over its blocks' descriptors and outcomes (ec_new_n_kernel reads the 48-byte EcWork of every block for three of its fields)
+__global__ __launch_bounds__(256) void ec_new_n_seg_kernel(uint64_t n_reads, const uint32_t *copy_n, const uint64_t *blk_off, const EcSeg *seg, const EcBlockOut *out, uint32_t *new_n)
+{
+    const uint64_t r = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_reads) return;
+    const uint64_t b0 = blk_off[r], b1 = blk_off[r + 1];
+    if (b0 == b1) { new_n[r] = copy_n[r]; return; }         // no block: what the walk kept (the whole chain)
+    uint32_t s = 0, prev_end = 0;
+    for (uint64_t i = b0; i < b1; ++i) {
+        const EcSeg d = seg[i];
+        s += ec_seg_front(d, prev_end) + ec_seg_body(d, out[i].status, out[i].np);
+        prev_end = d.end_fl >> 2;
+    }
+    new_n[r] = s;
+}
+
+// inclusive wave sum by DPP (rows of sixteen, then row_bcast 15 and 31); every lane of the wave must be active
+__device__ __forceinline__ uint32_t ecr_incl_sum(uint32_t v)
+{
+    v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int32_t) v, 0x111, 0xf, 0xf, false);
+    v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int32_t) v, 0x112, 0xf, 0xf, false);
+    v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int32_t) v, 0x114, 0xf, 0xf, false);
+    v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int32_t) v, 0x118, 0xf, 0xf, false);
+    v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int32_t) v, 0x142, 0xa, 0xf, false);
+    v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int32_t) v, 0x143, 0xc, 0xf, false);
+    return v;
+}
+
+// One wave per read, lane i holds chain entry i AND block i.  Two prefix sums over the blocks give every segment's place (all entries) and every path
+// interior's place among the path entries; a lane then finds the block its chain entry belongs to by comparing its index with the blocks' boundaries and
+// writes the entry if it stays, and the path interiors of all solved blocks of the read are copied together, 64 entries at a time.  Reads with more than 64
+// syncmers take ec_assemble_read_serial, as in ec_assemble_wave_kernel<1>, which this replaces (OATK_DEBUG_EC_ASSEMBLE_WALK=1 runs that one).
+__global__ __launch_bounds__(256) void ec_assemble_seg_kernel(EcAssembleArgs a)
+{
+    const uint64_t r0 = ((uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6)) * ECR_RPW;
+    const int lane = threadIdx.x & 63;
+    if (r0 >= a.rd.n_reads) return;
+#pragma unroll
+    for (int k = 0; k < ECR_RPW; ++k) {
+        const uint64_t r = r0 + k;
+        if (r >= a.rd.n_reads) break;
+        const uint64_t o = a.rd.scm_off[r], b0 = a.blk_off[r], w0 = a.new_off[r];
+        const int32_t n = ecr_s((int32_t) (a.rd.scm_off[r + 1] - o));
+        const uint64_t nb64 = a.blk_off[r + 1] - b0;
+        const int32_t nb = ecr_s(nb64 > 64? 65 : (int32_t) nb64);
+        const uint32_t room = (uint32_t) ecr_s((int32_t) (uint32_t) (a.new_off[r + 1] - w0));      // new_n[r]: nothing is written beyond it
+        const bool keep_all = ecr_s((int32_t) a.keep_all[r]) != 0;
+        if (n > 64 || nb > 64 || (nb == 0 && !keep_all)) {
+            if (lane == 0) ec_assemble_read_serial(a, r);
+            continue;
+        }
+        const bool in = lane < n;
+        const uint64_t km = in? a.rd.k_mer[o + lane] : 0;
+        const uint32_t mp = in? a.rd.m_pos[o + lane] : 0;
+        const uint64_t my_s = in? a.old_s_mer[o + lane] : 0;    // a syncmer's s-mer is the same at every occurrence (count.hpp: check_smer_kernel)
+        const uint64_t sid = (a.sid0 + r) << 32;
+        auto write = [&](uint32_t idx, uint64_t kk, uint32_t m, uint64_t sv) {          // entry idx of the corrected chain
+            if (idx >= room) return;
+            const uint64_t w = w0 + idx;
+            a.new_k_mer[w] = kk, a.new_m_pos[w] = m, a.new_s_mer[w] = sv;
+            a.key_id[w] = (uint32_t) (kk >> 1), a.val_occ[w] = sid | (uint64_t) idx << 1 | (m & 1u);                  // syncerr.c:796-805
+        };
+        if (nb == 0) {                                   // no good syncmer: the read keeps its arrays (syncerr.c:562-572)
+            if (in) write((uint32_t) lane, km, mp, my_s);
+            continue;
+        }
+        const bool isb = lane < nb;
+        EcSeg d;
+        d.beg = 0, d.end_fl = 0;
+        uint32_t status = EC_FAILURE, np = 0;
+        uint64_t path_off = 0;
+        if (isb) d = a.seg[b0 + lane], status = a.out[b0 + lane].status, np = a.out[b0 + lane].np, path_off = a.out[b0 + lane].path_off;
+        const uint32_t end = d.end_fl >> 2, prev = wave_prev(end), prev_end = lane == 0? 0u : prev;
+        const bool solved = isb && status == EC_SUCCESS;
+        const uint32_t front = isb? ec_seg_front(d, prev_end) : 0u, body = isb? ec_seg_body(d, status, np) : 0u, pc = solved? body : 0u;
+        const uint32_t at_incl = ecr_incl_sum(front + body), pt_incl = ecr_incl_sum(pc);
+        const uint32_t at = at_incl - (front + body), pt = pt_incl - pc;          // where block `lane`'s front starts; its path interior's place among the path entries
+        const uint32_t n_path = ecr_u32(pt_incl, 63);
+        // originals: entry `lane` lies in the stretch [prev_end(i), end(i)) of exactly one block i.  It stays if it is in front of the block (up to the anchor), or
+        // if the block is not corrected; its place is its distance from the stretch's start (front and body are adjacent in the chain, too)
+        {
+            const uint32_t meta = d.beg | (d.end_fl & EC_SEG_R) << 8 | (uint32_t) solved << 9;
+            const uint32_t base = at - prev_end;
+            uint32_t my_meta = 0, my_base = 0;
+            for (int32_t i = 0; i < nb; ++i) {
+                const uint32_t pe = ecr_u32(prev_end, i), mi = ecr_u32(meta, i), bi = ecr_u32(base, i);
+                if ((uint32_t) lane >= pe) my_meta = mi, my_base = bi;
+            }
+            const bool stays = !(my_meta >> 9 & 1u) || (!(my_meta >> 8 & 1u) && (uint32_t) lane <= (my_meta & 0xFFu));
+            if (in && stays) write(my_base + (uint32_t) lane, km, mp, my_s);
+        }
+        // path interiors: entry t of all of them belongs to the last block whose interiors start at or before t
+        for (uint32_t t0 = 0; t0 < n_path; t0 += 64) {
+            const uint32_t t = t0 + (uint32_t) lane;
+            int32_t bi = 0;
+            for (int32_t i = 0; i < nb; ++i) if (t >= ecr_u32(pt, i)) bi = i;
+            const uint32_t q = t - (uint32_t) __shfl((int32_t) pt, bi), dst = (uint32_t) __shfl((int32_t) (at + front), bi);
+            const int32_t bnp = __shfl((int32_t) np, bi);
+            const bool br = __shfl((int32_t) (d.end_fl & EC_SEG_R), bi) != 0;
+            const uint64_t poff = (uint64_t) (uint32_t) __shfl((int32_t) (uint32_t) (path_off >> 32), bi) << 32 | (uint32_t) __shfl((int32_t) (uint32_t) path_off, bi);
+            if (t < n_path) {
+                const uint64_t p = br? a.path_pool[poff + (uint32_t) (bnp - 1) - q] : a.path_pool[poff + 1 + q];
+                const uint64_t kk = (p & ~1ULL) | 1ULL;
+                write(dst + q, kk, br? 0xFFFFFFFFu ^ (uint32_t) (p & 1ULL) : 0xFFFFFFFEu | (uint32_t) (p & 1ULL), a.scm_s[kk >> 1]);
+            }
+        }
     }
 }
 
