@@ -78,8 +78,23 @@ enum {
     /* what the search cost, block by block (measurement aid; the layout may change): 12 u32 per error block -- beg_utg lo/hi, end_utg lo/hi, read,
      * beg_pos, length l, r, then 4 words of launch data -- and 12 u32 per block -- status, path entries, path offset lo/hi, flags, short, arcs tried
      * (DFS steps), dead ends counted (n_path, syncerr.c:147), wavefront steps, diagonals covered / 64, time on the wave that finished it (10 ns units), kernel variant */
-    OATK_BUF_EC_BLOCK_WORK, OATK_BUF_EC_BLOCK_OUT
+    OATK_BUF_EC_BLOCK_WORK, OATK_BUF_EC_BLOCK_OUT,
+    /* after oatk_hip_ec_corrected_reads: the corrected reads' sequences in hoco space, packed like HOCO_S (two bits per base, four bases to a byte, the first in
+     * the top bits); read i has EC_CSEQ_LEN[i] bases from byte EC_CSEQ_OFF[i] on, every read on a 16-byte boundary, pad bits and pad bytes zero */
+    OATK_BUF_EC_CSEQ_LEN,       /* u32[n_reads]                                                                                                           */
+    OATK_BUF_EC_CSEQ_OFF,       /* u64[n_reads+1] bytes                                                                                                   */
+    OATK_BUF_EC_CSEQ,           /* u8[EC_CSEQ_OFF[n_reads]]                                                                                               */
+    OATK_BUF_EC_BLOCK_QEND      /* u32[n_work]  after a correction with oatk_hip_ec_keep_seq: bases of the optimum consensus that replace the block, 0 = not replaced */
 };
+
+/* The corrected reads' sequences -- what read_error_correction writes to its FILE *fo (syncerr.c:544-558, :590-597, :614-624), in hoco space.
+ *   oatk_hip_ec_keep_seq(ctx, 1)        a switch, off by default, read when oatk_hip_ec / oatk_hip_ec_correct starts: the solver then leaves, for every block
+ *                                       that ends EC_SUCCESS or EC_AMBISNQ, q_end of the optimum alignment and the optimum consensus.  Every EC_* result and
+ *                                       the statistics are what they are without it.
+ *   oatk_hip_ec_corrected_reads(ctx, &n) builds EC_CSEQ_LEN / EC_CSEQ_OFF / EC_CSEQ from that; *n_bases (may be NULL) = bases of all corrected reads.
+ * OATK_E_STATE: the resident correction was made with the switch off, a scan has been made since, or the reads are sharded (oatk_hip_ec_set_global). */
+int oatk_hip_ec_keep_seq(oatk_hip_ctx *ctx, int on);
+int oatk_hip_ec_corrected_reads(oatk_hip_ctx *ctx, uint64_t *n_bases);
 
 /* oatk_hip_ec in two steps, for callers that need to act in between (sharded reads, below):
  *   oatk_hip_ec_mark     find_error_syncmers (syncerr.c:679) on the resident graph; EC_ERR_DEL and EC_VTX_SRC become readable

@@ -139,6 +139,10 @@ typedef struct {
  * scg_consensus and scg_destroy of run_syncasm.c:109-132 altogether; only the reads and the syncmer table are written back. */
 int oatk_read_error_correction(oatk_hip_ctx *ctx, oatk_sr_db_t *sr_db, oatk_syncmer_db_t *scm_db, oatk_asmg_t *asmg, double max_edist,
                                uint32_t err_mer_c, uint32_t max_err_c, uint32_t err_arc_c, double max_arc_f, uint64_t *stats12);
+/* the same with the reference's FILE *fo: when it is not NULL every read's corrected sequence in hoco space is written to it as ">%s\n%.*s\n" (syncerr.c:614-624)
+ * in sr_db order -- the order the reference writes with one thread -- from the device (oatk_hip_ec_keep_seq, oatk_hip_ec_corrected_reads: include/oatk_hip_ec.h) */
+int oatk_read_error_correction_fo(oatk_hip_ctx *ctx, oatk_sr_db_t *sr_db, oatk_syncmer_db_t *scm_db, oatk_asmg_t *asmg, double max_edist,
+                                  uint32_t err_mer_c, uint32_t max_err_c, uint32_t err_arc_c, double max_arc_f, FILE *fo, uint64_t *stats12);
 
 /* make_syncmer_graph(sr_db, scm_db, min_k_cov, min_a_cov_f) (syncasm.c:203-299, run_syncasm.c:138) on the device, from the batch resident
  * in ctx (after oatk_read_error_correction: the corrected reads): returns what the reference stores in scg->utg_asmg -- one vertex per

@@ -20,7 +20,7 @@ BUF = {name: i for i, name in enumerate([
 # include/oatk_hip_ec.h
 BUF.update({name: 100 + i for i, name in enumerate([
     "EC_N_SCM", "EC_SCM_OFF", "EC_KMER", "EC_MPOS", "EC_SMER", "EC_SCM_COV", "EC_SCM_DEL", "EC_SCM_OCC_OFF", "EC_SCM_OCC", "EC_ERR_DEL",
-    "EC_SCM_FWD", "EC_VTX_SRC", "EC_BLOCK_WORK", "EC_BLOCK_OUT"])})
+    "EC_SCM_FWD", "EC_VTX_SRC", "EC_BLOCK_WORK", "EC_BLOCK_OUT", "EC_CSEQ_LEN", "EC_CSEQ_OFF", "EC_CSEQ", "EC_BLOCK_QEND"])})
 # include/oatk_hip_ingest.h
 BUF.update({name: 160 + i for i, name in enumerate(["INGEST_SEQ", "INGEST_OFF", "INGEST_LEN", "INGEST_HDR"])})
 FMT_AUTO, FMT_FASTA, FMT_FASTQ = 0, 1, 2
@@ -54,6 +54,7 @@ EXPORTS = [
     "oatk_hip_asm_graph", "oatk_hip_asm_pairs", "oatk_hip_asm_graph_from_pairs", "oatk_hip_overlap_hist", "oatk_hip_overlap_pairs", "oatk_hip_overlap_hist_from_pairs", "oatk_hip_read_alignment", "oatk_hip_debug_align_two_pass",
     "oatk_hip_ra_utg_coverage", "oatk_hip_ra_arc_coverage", "oatk_hip_debug_racov_cap", "oatk_hip_ra_utg_coverage_sharded", "oatk_hip_ra_arc_coverage_sharded",
     "oatk_hip_ra_triplet_scores", "oatk_hip_ra_triplet_scores_sharded",
+    "oatk_hip_ec_keep_seq", "oatk_hip_ec_corrected_reads",
 ]
 
 # the N-handle mirror in liboatk_host.so (include/oatk_multi.h) of entry points listed above; EXPORTS itself is checked against liboatk_hip.so
@@ -222,6 +223,8 @@ def load():
         L.oatk_hip_debug_ed_ab.argtypes = [vp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
     L.oatk_hip_ec_mark.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double]
     L.oatk_hip_ec_correct.argtypes = [vp, C.c_double]
+    L.oatk_hip_ec_keep_seq.argtypes = [vp, C.c_int]
+    L.oatk_hip_ec_corrected_reads.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.oatk_hip_ec_set_global.argtypes = [vp, C.c_uint64, vp, vp, vp]
     L.oatk_hip_ec_pairs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.oatk_hip_ec_graph_from_pairs.argtypes = [vp, vp, vp, C.c_uint64]

@@ -5,6 +5,7 @@
 #include "ec_heavy.hpp"
 #include "ec_fused.hpp"
 #include "ecgraph.hpp"
+#include "ec_seq.hpp"
 #include <rocprim/device/device_run_length_encode.hpp>
 #include <rocprim/device/device_select.hpp>
 
@@ -33,6 +34,11 @@ struct EcState {
     bool global = false, marked = false;
     uint64_t n_global = 0, imp_used = 0;
     DevBuf g_l2g, g_kid, g_gcov, g_gs;
+    // corrected sequences (ec_seq.hpp)
+    bool keep_seq = false;              // oatk_hip_ec_keep_seq: the next correction records q_end and the optimum consensus of the blocks it replaces
+    bool seq_kept = false, cseq_done = false;      // the resident correction did; oatk_hip_ec_corrected_reads has run on it
+    DevBuf slot_w, slot_w64, slot_off, slots, qend, sblk, clen, cbytes, cbytes64, coff, cseq;
+    uint64_t cseq_bytes = 0;
 };
 
 static uint64_t ec_n_vtx(oatk_hip_ctx *ctx) { return ctx->ec && ctx->ec->global? ctx->ec->n_global : ctx->n_scm_total; }
@@ -49,7 +55,8 @@ static void ec_state_free(oatk_hip_ctx *ctx)
                      &e->g_keys, &e->g_keys2, &e->g_ukeys, &e->g_counts, &e->g_nruns, &e->g_nout, &e->g_nout64, &e->g_outoff, &e->g_akey,
                      &e->g_aval, &e->g_skey, &e->g_sval, &e->g_comp, &e->g_flags, &e->g_huge, &e->g_dist, &e->g_dist2, &e->g_cnt64, &e->g_runoff, &e->g_runls,
                      &e->g_big, &e->g_keep, &e->g_other, &e->g_lkeys, &e->g_ldist, &e->g_val2, &e->g_wgt2, &e->g_runcov, &e->g_head, &e->g_hpos, &e->g_iota, &e->g_segk, &e->g_segv,
-                     &e->g_l2g, &e->g_kid, &e->g_gcov, &e->g_gs};
+                     &e->g_l2g, &e->g_kid, &e->g_gcov, &e->g_gs,
+                     &e->slot_w, &e->slot_w64, &e->slot_off, &e->slots, &e->qend, &e->sblk, &e->clen, &e->cbytes, &e->cbytes64, &e->coff, &e->cseq};
     for (DevBuf *b : all) b->release();
     for (int i = 0; i < 5; ++i) { if (e->aux[i]) (void) hipStreamDestroy(e->aux[i]); if (e->aux_ev[i]) (void) hipEventDestroy(e->aux_ev[i]); }
     if (e->fork_ev) (void) hipEventDestroy(e->fork_ev);
@@ -83,6 +90,18 @@ static int ec_buffer(oatk_hip_ctx *ctx, int which, const void **d_ptr, uint64_t 
     if (!e || !e->done) { ctx->err = "unknown buffer id, or error-correction results requested before oatk_hip_ec"; return OATK_E_STATE; }
     if (which == OATK_BUF_EC_BLOCK_WORK) { *d_ptr = e->work.p, *bytes = e->n_work * sizeof(oatk::EcWork); return OATK_OK; }
     if (which == OATK_BUF_EC_BLOCK_OUT) { *d_ptr = e->out.p, *bytes = e->n_work * sizeof(oatk::EcBlockOut); return OATK_OK; }
+    if (which == OATK_BUF_EC_BLOCK_QEND) {
+        if (!e->seq_kept) { ctx->err = "EC_BLOCK_QEND: the resident correction was made without oatk_hip_ec_keep_seq"; return OATK_E_STATE; }
+        *d_ptr = e->qend.p, *bytes = e->n_work * 4;
+        return OATK_OK;
+    }
+    if (which >= OATK_BUF_EC_CSEQ_LEN && which <= OATK_BUF_EC_CSEQ) {
+        if (!e->seq_kept || !e->cseq_done) { ctx->err = "corrected sequences requested before oatk_hip_ec_corrected_reads"; return OATK_E_STATE; }
+        if (which == OATK_BUF_EC_CSEQ_LEN) *d_ptr = e->clen.p, *bytes = ctx->n_reads * 4;
+        else if (which == OATK_BUF_EC_CSEQ_OFF) *d_ptr = e->coff.p, *bytes = (ctx->n_reads + 1) * 8;
+        else *d_ptr = e->cseq.p, *bytes = e->cseq_bytes;
+        return OATK_OK;
+    }
     const uint64_t n = ctx->n_reads, ns = e->n_vtx, tot = e->new_tot;
     switch (which) {
         case OATK_BUF_EC_N_SCM: *d_ptr = e->new_n.p, *bytes = n * 4; break;
@@ -809,10 +828,12 @@ static uint64_t ec_os_words(int32_t cap_c) { return ((uint64_t) ecw_words(cap_c)
 
 static void ec_set_caps(EcwArgs &a, const EcTier &t) { a.cap_t = t.cap_t, a.cap_c = t.cap_c, a.cap_w = t.cap_w, a.cap_path = t.cap_path, a.cap_f = t.cap_f; }
 
-// one launcher per kernel family: `lds` bytes of LDS per wave (ec_wave_kernel) or per workgroup (the others)
+// one launcher per kernel family: `lds` bytes of LDS per wave (ec_wave_kernel) or per workgroup (the others).  A launch that records the optimum consensus
+// (a.seq_qend, oatk_hip_ec_keep_seq) runs the kernel's KEEP instantiation; every other launch runs the code it always ran.
 template <int MODE, int WPB> static void ec_wave_launch(uint64_t waves, uint64_t lds, hipStream_t st, const EcwArgs &a)
 {
-    hipLaunchKernelGGL((ec_wave_kernel<MODE, WPB>), dim3((unsigned) ((waves + WPB - 1) / WPB)), dim3(64 * WPB), (unsigned) (WPB * lds), st, a);
+    if (a.seq_qend) hipLaunchKernelGGL((ec_wave_kernel<MODE, WPB, true>), dim3((unsigned) ((waves + WPB - 1) / WPB)), dim3(64 * WPB), (unsigned) (WPB * lds), st, a);
+    else hipLaunchKernelGGL((ec_wave_kernel<MODE, WPB>), dim3((unsigned) ((waves + WPB - 1) / WPB)), dim3(64 * WPB), (unsigned) (WPB * lds), st, a);
 }
 static void ec_launch_lds_tier(const EcTier &t, uint64_t waves, hipStream_t st, const EcwArgs &a)
 {
@@ -826,11 +847,13 @@ static void ec_launch_lds_tier(const EcTier &t, uint64_t waves, hipStream_t st, 
 }
 template <int NW, int R> static void ec_heavy_launch(uint64_t wgs, uint64_t lds, hipStream_t st, const EcwArgs &a)
 {
-    hipLaunchKernelGGL((ec_heavy_kernel<NW, R>), dim3((unsigned) wgs), dim3(64 * NW), (unsigned) lds, st, a);
+    if (a.seq_qend) hipLaunchKernelGGL((ec_heavy_kernel<NW, R, true>), dim3((unsigned) wgs), dim3(64 * NW), (unsigned) lds, st, a);
+    else hipLaunchKernelGGL((ec_heavy_kernel<NW, R>), dim3((unsigned) wgs), dim3(64 * NW), (unsigned) lds, st, a);
 }
 template <int NW> static void ec_fused_launch(uint64_t wgs, uint64_t lds, hipStream_t st, const EcwArgs &a)
 {
-    hipLaunchKernelGGL((ec_fused_kernel<NW>), dim3((unsigned) wgs), dim3(64 * NW), (unsigned) lds, st, a);
+    if (a.seq_qend) hipLaunchKernelGGL((ec_fused_kernel<NW, true>), dim3((unsigned) wgs), dim3(64 * NW), (unsigned) lds, st, a);
+    else hipLaunchKernelGGL((ec_fused_kernel<NW>), dim3((unsigned) wgs), dim3(64 * NW), (unsigned) lds, st, a);
 }
 
 // the next of the call's HBM slab buffers: launches that may run side by side each take one of their own
@@ -1247,7 +1270,9 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     if (!ctx->ec || !ctx->ec->marked) { ctx->err = "oatk_hip_ec_correct needs oatk_hip_ec_mark"; return OATK_E_STATE; }
     CK(hipSetDevice(ctx->device));
     EcState *e = ctx->ec;
-    e->done = false;
+    e->done = false, e->cseq_done = false;
+    const bool keep_seq = e->keep_seq && !e->global;      // (sharded reads: corrected as ever; oatk_hip_ec_corrected_reads refuses them)
+    e->seq_kept = false;
     const EcKnobs kn = ec_knobs_read();
     EC_VIEWS();
     // the arcs that survive, squeezed, each with what the search needs about its target (ec.hpp: EcLiveArc)
@@ -1287,6 +1312,14 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     EENSURE(new_n, (nr + 1) * 4); EENSURE(copy_n, (nr + 1) * 4); EENSURE(seg, (n_work + 1) * sizeof(EcSeg)); EENSURE(keep_all, nr + 1);
     hipLaunchKernelGGL(ec_list_blocks_wave_kernel, rblocks, dim3(256), 0, ctx->stream, rd, lv, (const uint8_t *) e->scm_del.p, e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->copy_n.as<uint32_t>(),
                        e->seg.as<EcSeg>(), e->keep_all.as<uint8_t>());
+    // a fixed slot per block for its optimum consensus (oatk_hip_ec_keep_seq): no atomics, no overflow, and the same addresses whichever launch finishes a block
+    if (keep_seq) {
+        uint64_t slot_words = 0;
+        EENSURE(slot_w, (n_work + 1) * 4); EENSURE(qend, (n_work + 1) * 4);
+        if (n_work) hipLaunchKernelGGL(ec_slot_words_kernel, blocks(n_work), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), n_work, max_edist, e->slot_w.as<uint32_t>());
+        { int rc = ec_exclusive_scan_u32(ctx, e, e->slot_w, e->slot_w64, e->slot_off, n_work, &slot_words); if (rc) return rc; }
+        EENSURE(slots, (slot_words + 4) * 4);
+    }
     t_end(ctx, OATK_T_EC_MARK);
     t_begin(ctx, OATK_T_EC_SOLVE);
 
@@ -1307,6 +1340,10 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
         base.lv = lv, base.rd = rd, base.work = e->work.as<EcWork>(), base.n_work = n_work, base.max_edist = max_edist;
         base.out = e->out.as<EcBlockOut>(), base.path_pool = e->path_pool.as<uint64_t>(), base.pool_cap = pool_cap;
         base.pool_cursor = (unsigned long long *) e->cursor.p;       // [0] pool, then the lists' and work queues' counters; [63] blocks that outgrew the slabs
+        if (keep_seq) {
+            CK(hipMemsetAsync(e->qend.p, 0, (n_work + 1) * 4, ctx->stream));
+            base.seq_qend = e->qend.as<uint32_t>(), base.seq_slots = e->slots.as<uint32_t>(), base.seq_slot_off = e->slot_off.as<uint64_t>();
+        }
         if (kn.stages) fprintf(stderr, "[ec stages] the live graph %s: %s\n", graph_branches? "branches" : "does not branch", heavy? "classes with budgets, second stage" : "round 4's tiers");
         { int rc = heavy? ec_solve_classes(ctx, e, kn, base, max_hl, n_big) : ec_solve_tiers(ctx, e, kn, base, max_hl, n_big); if (rc) return rc; }
         unsigned long long fin = 0, used = 0;
@@ -1376,7 +1413,69 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     for (int i = 0; i < 11; ++i) e->stats_h[i] = st[i];
     e->stats_h[11] = n_big;
     if (chk != tot) { ctx->err = "error correction: coverage does not add up"; return OATK_E_STATE; }
-    e->done = true;
+    e->done = true, e->seq_kept = keep_seq;
+    return OATK_OK;
+}
+
+extern "C" int oatk_hip_ec_keep_seq(oatk_hip_ctx *ctx, int on)
+{
+    if (!ctx) return OATK_E_NODEV;
+    if (!ctx->ec) ctx->ec = new EcState();
+    ctx->ec->keep_seq = on != 0;
+    return OATK_OK;
+}
+
+// the corrected reads' sequences from what a correction with the switch on left resident (ec_seq.hpp): lengths, offsets, then the strings
+extern "C" int oatk_hip_ec_corrected_reads(oatk_hip_ctx *ctx, uint64_t *n_bases)
+{
+    using namespace oatk;
+    if (!ctx) return OATK_E_NODEV;
+    EcState *e = ctx->ec;
+    if (e && e->global) { ctx->err = "oatk_hip_ec_corrected_reads: sharded reads are not supported"; return OATK_E_STATE; }
+    if (!e || !e->done || !e->seq_kept || !ctx->scanned) { ctx->err = "oatk_hip_ec_corrected_reads needs a correction of the resident batch made with oatk_hip_ec_keep_seq"; return OATK_E_STATE; }
+    CK(hipSetDevice(ctx->device));
+    e->cseq_done = false;          // (a call that fails half-way leaves nothing readable)
+    EC_VIEWS();
+    (void) g;
+    const uint64_t n_work = e->n_work;
+    // OATK_DEBUG_EC_STAGES: the two passes' durations on stderr (tests/ec_seq_time.py)
+    const bool stages = getenv("OATK_DEBUG_EC_STAGES") != nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    if (stages) for (int i = 0; i < 3; ++i) CK(hipEventCreate(&ev[i]));
+    EENSURE(sblk, (n_work + nr + 1) * sizeof(EcSeqBlk)); EENSURE(clen, (nr + 1) * 4); EENSURE(cbytes, (nr + 1) * 4);
+    if (stages) CK(hipEventRecord(ev[0], ctx->stream));
+    if (nr) hipLaunchKernelGGL(ec_cseq_len_kernel, blocks(nr), dim3(256), 0, ctx->stream, rd, e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->out.as<EcBlockOut>(), e->qend.as<uint32_t>(),
+                               e->sblk.as<EcSeqBlk>(), e->clen.as<uint32_t>(), e->cbytes.as<uint32_t>());
+    uint64_t bytes = 0;
+    { int rc = ec_exclusive_scan_u32(ctx, e, e->cbytes, e->cbytes64, e->coff, nr, &bytes); if (rc) return rc; }
+    EENSURE(cseq, bytes + 16);
+    if (stages) CK(hipEventRecord(ev[1], ctx->stream));
+    EcSeqArgs sa;
+    sa.rd = rd, sa.blk_off = e->blk_off.as<uint64_t>(), sa.sb = e->sblk.as<EcSeqBlk>(), sa.slots = e->slots.as<uint32_t>(), sa.slot_off = e->slot_off.as<uint64_t>();
+    sa.coff = e->coff.as<uint64_t>(), sa.cseq = e->cseq.as<uint8_t>();
+    if (nr) hipLaunchKernelGGL(ec_cseq_write_kernel, dim3((unsigned) ((nr + 3) / 4)), dim3(256), 0, ctx->stream, sa);
+    if (stages) {
+        float ms_len = 0.f, ms_write = 0.f;
+        CK(hipEventRecord(ev[2], ctx->stream));
+        CK(hipEventSynchronize(ev[2]));
+        CK(hipEventElapsedTime(&ms_len, ev[0], ev[1]));
+        CK(hipEventElapsedTime(&ms_write, ev[1], ev[2]));
+        for (int i = 0; i < 3; ++i) (void) hipEventDestroy(ev[i]);
+        fprintf(stderr, "[ec stages] corrected reads: lengths + offsets %.3f ms, strings %.3f ms (%llu reads, %llu blocks, %llu bytes written)\n", ms_len, ms_write,
+                (unsigned long long) nr, (unsigned long long) n_work, (unsigned long long) bytes);
+    }
+    if (n_bases) {
+        // (bases, not bytes: the offsets count every read's pad)
+        std::vector<uint32_t> cl(nr);
+        if (nr) CK(hipMemcpyAsync(cl.data(), e->clen.p, nr * 4, hipMemcpyDeviceToHost, ctx->stream));
+        CK(hipStreamSynchronize(ctx->stream));
+        uint64_t s = 0;
+        for (uint64_t i = 0; i < nr; ++i) s += cl[i];
+        *n_bases = s;
+    }
+    CK(hipStreamSynchronize(ctx->stream));
+    CK(hipGetLastError());
+    e->cseq_bytes = bytes, e->cseq_done = true;
     return OATK_OK;
 }
 

@@ -401,18 +401,18 @@ void read_error_correction(oatk_sr_db_t *sr_db, oatk_scg_t *g, double max_edist,
     uint64_t st[12];
     hooks_off();                                                        /* the chains are about to change */
     if (!D.resident || !D.counted || sr_db != D.sr_db || !g || g->scm_db != D.scm_db) why = "no resident batch";
-    else if (fo) why = "the corrected reads are to be written out (debug build): the original does that";
+    else if (fo && D.multi) why = "the corrected reads are to be written out and the reads are spread over several handles: the original does that";
     if (!why) {
         oatk_host_set_threads(n_threads);
         int rc = D.multi? (placeholder? oatk_multi_read_error_correction(D.multi, sr_db, g->scm_db, max_edist, err_mer_c, max_err_c, err_arc_c, max_arc_f, st) : OATK_E_ARG)
-                        : oatk_read_error_correction(D.ctx, sr_db, g->scm_db, placeholder? 0 : g->utg_asmg, max_edist, err_mer_c, max_err_c, err_arc_c, max_arc_f, st);
+                        : oatk_read_error_correction_fo(D.ctx, sr_db, g->scm_db, placeholder? 0 : g->utg_asmg, max_edist, err_mer_c, max_err_c, err_arc_c, max_arc_f, fo, st);
         if (rc == OATK_E_SPLIT && placeholder && !D.multi) {
             /* the device refuses to ORDER this graph (duplicate arcs of a long tandem repeat, an arc with dozens of distances): the original
              * builds it, the correction itself still runs on the device against that graph */
             if (D.log) fprintf(stderr, "[M::oatk_dropin] read_error_correction: %s; graph from the original make_syncmer_graph + scg_consensus\n", why_not(rc));
             real = orig_make_syncmer_graph(sr_db, g->scm_db, 0, 0.);
             scg_consensus(sr_db, real, 1, 1, 0);
-            rc = oatk_read_error_correction(D.ctx, sr_db, g->scm_db, real->utg_asmg, max_edist, err_mer_c, max_err_c, err_arc_c, max_arc_f, st);
+            rc = oatk_read_error_correction_fo(D.ctx, sr_db, g->scm_db, real->utg_asmg, max_edist, err_mer_c, max_err_c, err_arc_c, max_arc_f, fo, st);      /* (the refusal came before anything was written) */
         }
         if (rc == OATK_OK) {
             ec_report(st, verbose);

@@ -322,9 +322,10 @@ __global__ __launch_bounds__(64 * NW) void ecf_wf_ed_kernel(const uint32_t *tw, 
 // The table test (round 6, always on): an arc that appends a long string is first asked whether it can be alive at all -- min over the band of (what the
 // parent's wavefront knows of its last row + the string's tables) beyond bw: dead by score, no step taken (tests/trace/ec_trace.c ECT_ROWS:
 // 92.8 % of such arcs' steps on the config-1 surrogate, no living arc).  The tables live in a region of HBM per workgroup (a.os_slabs, ecf_tab_words).
-template <int NW>
+// KEEP: as for ecw_solve_block (ec_wave.hpp).
+template <int NW, bool KEEP = false>
 __device__ bool ecf_solve_block(const EcLive &lv, const EcReads &rd, const EcWork &wk, const EcfShared &sh, double max_edist,
-                                uint32_t &status_out, uint32_t &np_out, uint32_t &tried_out, uint32_t &n_path_out, uint32_t &wf_steps_out, uint32_t &wf_diag_out)
+                                uint32_t &status_out, uint32_t &np_out, uint32_t &tried_out, uint32_t &n_path_out, uint32_t &wf_steps_out, uint32_t &wf_diag_out, uint32_t &olen_out)
 {
     constexpr int T = 64 * NW;
     const int t = (int) threadIdx.x, lane = t & 63;
@@ -631,12 +632,13 @@ __device__ bool ecf_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
             ++n_path;
         }
         // the optimum consensus is only ever compared with a LATER path's (a tie): when the search ends here nobody reads it
-        if (new_opt && (nfr > 0 || vpend)) {
+        if (new_opt && (KEEP || nfr > 0 || vpend)) {
             for (int32_t wi = t; wi < ((o_len + 15) >> 4); wi += T) sh.os[wi] = sh.cs[wi];
         }
         ECF_P2_T(12);
     }
     ech_barrier<NW>();
+    if (KEEP) olen_out = (uint32_t) o_len;
 #ifdef ECF_PROF2
     if (t == 0) { p2[14] = 1, p2[15] = wf_steps; const int row = NW == 2? 0 : (NW == 4? 1 : (NW == 8? 2 : (NW == 16? 3 : 4))); for (int i = 0; i < 28; ++i) atomicAdd(&ecf_prof2[row][i], (unsigned long long) p2[i]); }
 #endif
@@ -645,7 +647,7 @@ __device__ bool ecf_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
 }
 
 // One workgroup per block, blocks taken one at a time from the list.  EcwArgs as for ec_heavy_kernel.
-template <int NW>
+template <int NW, bool KEEP = false>
 __global__ __launch_bounds__(64 * NW) void ec_fused_kernel(EcwArgs a)
 {
     extern __shared__ uint32_t ecf_lds[];
@@ -690,12 +692,13 @@ __global__ __launch_bounds__(64 * NW) void ec_fused_kernel(EcwArgs a)
         if (ECW_RARE(wk.l < EC_MIN_ERR_SEQ_LEN)) {
             o.short_block = 1;                         // syncerr.c:502-504
         } else {
-            uint32_t st = 0, np = 0;
-            if (ECW_RARE(!(ecf_solve_block<NW>(a.lv, a.rd, wk, sh, a.max_edist, st, np, o.tried, o.n_path, o.wf_steps, o.wf_diag)))) {
+            uint32_t st = 0, np = 0, o_len = 0;
+            if (ECW_RARE(!(ecf_solve_block<NW, KEEP>(a.lv, a.rd, wk, sh, a.max_edist, st, np, o.tried, o.n_path, o.wf_steps, o.wf_diag, o_len)))) {
                 o.flags = 1;
                 if (t == 0) a.todo_out[atomicAdd(a.todo_cnt, 1ULL)] = (uint32_t) wi;
             } else {
                 o.status = st, o.np = np;
+                if (KEEP) ec_keep_seq(a, wi, st, o_len, sh.os, t, 64 * NW);
                 if (st == EC_SUCCESS && np) {
                     if (ECW_RARE(pool_at + np > pool_end)) {
                         const unsigned long long want = np > ECW_POOL_CHUNK? np : ECW_POOL_CHUNK;

@@ -236,9 +236,10 @@ __global__ __launch_bounds__(64 * NW) void ech_wf_ed_kernel(const uint32_t *tw, 
 }
 
 // Solve one block with the whole workgroup.  Returns false when the block outgrows the carve-up (it is then re-run by the slab tier of ec_wave.hpp).
-template <int NW, int R>
+// KEEP: as for ecw_solve_block (ec_wave.hpp).
+template <int NW, int R, bool KEEP = false>
 __device__ bool ech_solve_block(const EcLive &lv, const EcReads &rd, const EcWork &wk, const EchShared &sh, double max_edist,
-                                uint32_t &status_out, uint32_t &np_out, uint32_t &tried_out, uint32_t &n_path_out, uint32_t &wf_steps_out, uint32_t &wf_diag_out)
+                                uint32_t &status_out, uint32_t &np_out, uint32_t &tried_out, uint32_t &n_path_out, uint32_t &wf_steps_out, uint32_t &wf_diag_out, uint32_t &olen_out)
 {
     constexpr int T = 64 * NW;
     const int t = (int) threadIdx.x, lane = t & 63;
@@ -472,18 +473,19 @@ __device__ bool ech_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
             ++n_path;
         }
         // the optimum consensus is only ever compared with a LATER path's (a tie): when the search ends here nobody reads it
-        if (new_opt && (nfr > 0 || vpend)) {
+        if (new_opt && (KEEP || nfr > 0 || vpend)) {
             for (int32_t wi = t; wi < ((o_len + 15) >> 4); wi += T) sh.os[wi] = sh.cs[wi];
         }
     }
     ech_barrier<NW>();
+    if (KEEP) olen_out = (uint32_t) o_len;
     status_out = (uint32_t) status, np_out = (uint32_t) np, tried_out = tried, n_path_out = (uint32_t) n_path, wf_steps_out = wf_steps, wf_diag_out = (uint32_t) (wf_diag >> 6);
     return true;
 }
 
 // One workgroup per block, blocks taken one at a time from the list (a.todo, longest first where the host can tell).  EcwArgs as for ec_wave_kernel; a.slabs /
 // a.slab_bytes = the workgroups' HBM slabs, a.cap_f = the LDS frame arena, a.os_words = bytes of the slab's frame arena.
-template <int NW, int R>
+template <int NW, int R, bool KEEP = false>
 __global__ __launch_bounds__(64 * NW) void ec_heavy_kernel(EcwArgs a)
 {
     extern __shared__ uint32_t ech_lds[];
@@ -528,12 +530,13 @@ __global__ __launch_bounds__(64 * NW) void ec_heavy_kernel(EcwArgs a)
         if (ECW_RARE(wk.l < EC_MIN_ERR_SEQ_LEN)) {
             o.short_block = 1;                         // syncerr.c:502-504
         } else {
-            uint32_t st = 0, np = 0;
-            if (ECW_RARE(!(ech_solve_block<NW, R>(a.lv, a.rd, wk, sh, a.max_edist, st, np, o.tried, o.n_path, o.wf_steps, o.wf_diag)))) {
+            uint32_t st = 0, np = 0, o_len = 0;
+            if (ECW_RARE(!(ech_solve_block<NW, R, KEEP>(a.lv, a.rd, wk, sh, a.max_edist, st, np, o.tried, o.n_path, o.wf_steps, o.wf_diag, o_len)))) {
                 o.flags = 1;
                 if (t == 0) a.todo_out[atomicAdd(a.todo_cnt, 1ULL)] = (uint32_t) wi;
             } else {
                 o.status = st, o.np = np;
+                if (KEEP) ec_keep_seq(a, wi, st, o_len, sh.os, t, 64 * NW);
                 if (st == EC_SUCCESS && np) {
                     if (ECW_RARE(pool_at + np > pool_end)) {
                         const unsigned long long want = np > ECW_POOL_CHUNK? np : ECW_POOL_CHUNK;

@@ -367,8 +367,11 @@ __device__ __forceinline__ EcwArcRegs ecw_arc_load(const EcLiveArc *arc, uint32_
 }
 
 // Solve one block with the whole wave.  Returns false when the scratch is too small (the block is then re-run by a larger tier).
+// KEEP (oatk_hip_ec_keep_seq): the caller wants the optimum consensus -- its length comes back in olen_out and s.os holds it whenever an optimum exists,
+// also where the search ends with it.  Without KEEP this is the code it was: olen_out is not touched.
+template <bool KEEP = false>
 __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWork &wk, const EcwScratch &s, double max_edist,
-                                uint32_t &status_out, uint32_t &np_out, uint32_t &tried_out, uint32_t &n_path_out, uint32_t &wf_steps_out, uint32_t &wf_diag_out)
+                                uint32_t &status_out, uint32_t &np_out, uint32_t &tried_out, uint32_t &n_path_out, uint32_t &wf_steps_out, uint32_t &wf_diag_out, uint32_t &olen_out)
 {
     const int lane = threadIdx.x & 63;
     const int K = rd.K;
@@ -574,12 +577,13 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
             ++n_path;
         }
         // the optimum consensus is only ever compared with a LATER path's (a tie): when the search ends here -- the usual case, a block with one
-        // path -- nobody reads it and the copy is left out
-        if (new_opt && (nfr > 0 || vpend)) {
+        // path -- nobody reads it and the copy is left out (KEEP: the caller reads it)
+        if (new_opt && (KEEP || nfr > 0 || vpend)) {
             for (int32_t wi = lane; wi < ((o_len + 15) >> 4); wi += 64) s.os[wi] = s.cs[wi];
         }
     }
     ecw_sync();
+    if (KEEP) olen_out = (uint32_t) o_len;
     status_out = (uint32_t) status, np_out = (uint32_t) np, tried_out = tried, n_path_out = (uint32_t) n_path, wf_steps_out = wf_steps, wf_diag_out = (uint32_t) (wf_diag >> 6);
     return true;
 }
@@ -615,7 +619,32 @@ struct EcwArgs {
     int32_t skip_l;               // blocks longer than this were routed to a larger tier before the launch (ec_route_kernel): not this launch's business
     int32_t batch;                // blocks taken from the queue per atomic: ECW_BATCH where the blocks are millions and small, 1 where they are few and long
     int32_t arc_budget;           // first tier: arcs after which a block is left to the classes behind it (0: never)
+    // oatk_hip_ec_keep_seq (the KEEP instantiations of the solver kernels; null otherwise): what a corrected read's sequence needs of a block besides its path
+    uint32_t *seq_qend;           // [n_work] q_end of the optimum alignment = bases of the optimum consensus that replace the block (syncerr.c:247-248); 0 = not replaced
+    uint32_t *seq_slots;          // the optimum consensus itself, sixteen bases to a word as the solver holds it: block i at word seq_slot_off[i]
+    const uint64_t *seq_slot_off; // [n_work + 1] a fixed slot per block (ec_slot_words): addresses do not depend on which launch finishes what
 };
+
+// words of a block's slot: the optimum consensus ends where the alignment's query does, and q_end cannot pass tl + bw (the band); a block that is not solved has none
+__host__ __device__ inline uint32_t ec_slot_words(int32_t l, double max_edist)
+{
+    if (l < EC_MIN_ERR_SEQ_LEN) return 0u;
+    int32_t bw = (int32_t) ceil((double) l * max_edist);
+    if (bw < EC_MIN_ERR_BASE) bw = EC_MIN_ERR_BASE;
+    return (uint32_t) ((l + bw + 15) / 16);
+}
+// A block is done with an optimum that replaces its bases (EC_SUCCESS, EC_AMBISNQ: syncerr.c:545): every lane of the T that solved it copies its share of the
+// optimum consensus into the block's slot -- the words it wrote to `os` itself -- and one of them records the length
+__device__ __forceinline__ void ec_keep_seq(const EcwArgs &a, uint64_t wi, uint32_t status, uint32_t o_len, const uint32_t *os, int t, int T)
+{
+    if (status != EC_SUCCESS && status != EC_AMBISNQ) return;
+    const uint64_t s0 = a.seq_slot_off[wi];
+    uint32_t nw = (o_len + 15u) >> 4;
+    const uint32_t room = (uint32_t) (a.seq_slot_off[wi + 1] - s0);
+    if (nw > room) nw = room;                          // (cannot happen: q_end <= tl + bw)
+    for (uint32_t j = (uint32_t) t; j < nw; j += (uint32_t) T) a.seq_slots[s0 + j] = os[j];
+    if (t == 0) a.seq_qend[wi] = o_len;
+}
 
 // Blocks too long for the first tier's carve-up are known before anything runs (the length is in the work item): they go straight onto the
 // list of the first tier that holds them, and those tiers run BESIDE the first one instead of after it.  cap[t] = longest block of tier t
@@ -693,7 +722,7 @@ __host__ __device__ inline uint32_t ecw_scratch_words(int32_t cap_t, int32_t cap
 // reads in every step, 89 % of a long search's cycles -- in LDS, the paths and the DFS frames -- touched once per arc -- in an HBM slab.  A search
 // through a tandem array is hundreds of levels deep with a frame at every level: it outgrew every LDS carve-up and ran in the slabs at a tenth of
 // the speed, eight seconds for 40 k reads of the config-1 surrogate (profiles/r04e_solver_config1s.txt).
-template <int MODE, int WPB = 1>
+template <int MODE, int WPB = 1, bool KEEP = false>
 __global__ __launch_bounds__(64 * WPB) void ec_wave_kernel(EcwArgs a)
 {
     constexpr bool BIG = MODE == 1;
@@ -751,12 +780,13 @@ __global__ __launch_bounds__(64 * WPB) void ec_wave_kernel(EcwArgs a)
             if (ECW_RARE(wk.l < EC_MIN_ERR_SEQ_LEN)) {
                 o.short_block = 1;                     // syncerr.c:502-504
             } else {
-                uint32_t st = 0, np = 0;
-                if (ECW_RARE(!ecw_solve_block(a.lv, a.rd, wk, s, a.max_edist, st, np, o.tried, o.n_path, o.wf_steps, o.wf_diag))) {
+                uint32_t st = 0, np = 0, o_len = 0;
+                if (ECW_RARE(!ecw_solve_block<KEEP>(a.lv, a.rd, wk, s, a.max_edist, st, np, o.tried, o.n_path, o.wf_steps, o.wf_diag, o_len))) {
                     o.flags = 1;
                     if (lane == 0) a.todo_out[atomicAdd(a.todo_cnt, 1ULL)] = (uint32_t) wi;
                 } else {
                     o.status = st, o.np = np;
+                    if (KEEP) ec_keep_seq(a, wi, st, o_len, s.os, lane, 64);
                     if (st == EC_SUCCESS && np) {
                         if (ECW_RARE(pool_at + np > pool_end)) {
                             const unsigned long long want = np > ECW_POOL_CHUNK? np : ECW_POOL_CHUNK;

@@ -8,6 +8,7 @@
  *   - syncmer table: cov, del, m_pos; c and h released           (update_syncmer_db, syncerr.c:769-814)
  *   - graph: deleted error syncmers and their arcs              (find_error_syncmers with del_err = 1, syncerr.c:748-752)
  * With asmg == NULL the EC graph itself (run_syncasm.c:109-117) is built on the device as well and there is nothing to flatten.
+ * With a FILE *fo (oatk_read_error_correction_fo) every read's corrected sequence is written as the reference writes it (syncerr.c:614-624), in read order.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -103,11 +104,84 @@ void oatk_host_ec_write_back(oatk_sr_db_t *sr_db, oatk_syncmer_db_t *scm_db, con
     free(job.new_off);
 }
 
-int oatk_read_error_correction(oatk_hip_ctx *ctx, oatk_sr_db_t *sr_db, oatk_syncmer_db_t *scm_db, oatk_asmg_t *asmg, double max_edist,
-                               uint32_t err_mer_c, uint32_t max_err_c, uint32_t err_arc_c, double max_arc_f, uint64_t *stats12)
+/* ">name\nSEQ\n" of the reads [r0, r1) of a piece: packed strings (two bits per base, first base in the top bits) to ACGT, a slice of the reads per thread */
+typedef struct {
+    const oatk_sr_db_t *sr_db;
+    const uint8_t *packed;         /* the piece: read r at packed + (coff[r] - coff[r0]) */
+    const uint64_t *coff;
+    const uint32_t *clen;
+    const uint64_t *toff;          /* text offsets of the piece's reads, toff[r - r0] */
+    char *text;
+    uint64_t r0, r1;
+} ecs_job_t;
+
+static void ecs_worker(void *arg, int tid, int n_threads)
+{
+    static const char nt[4] = {'A', 'C', 'G', 'T'};
+    const ecs_job_t *j = (const ecs_job_t *) arg;
+    const uint64_t n = j->r1 - j->r0, ra = j->r0 + n * (uint64_t) tid / (uint64_t) n_threads, rb = j->r0 + n * (uint64_t) (tid + 1) / (uint64_t) n_threads;
+    uint64_t r;
+    for (r = ra; r < rb; ++r) {
+        const char *name = j->sr_db->a[r].sname? j->sr_db->a[r].sname : "(null)";      /* (what printf makes of a NULL %s) */
+        const size_t nl = strlen(name);
+        const uint8_t *s = j->packed + (j->coff[r] - j->coff[j->r0]);
+        const uint32_t l = j->clen[r];
+        char *t = j->text + j->toff[r - j->r0];
+        uint32_t p;
+        *t++ = '>';
+        memcpy(t, name, nl), t += nl;
+        *t++ = '\n';
+        for (p = 0; p + 4 <= l; p += 4) {
+            const uint8_t x = s[p >> 2];
+            t[p] = nt[x >> 6], t[p + 1] = nt[(x >> 4) & 3], t[p + 2] = nt[(x >> 2) & 3], t[p + 3] = nt[x & 3];
+        }
+        for (; p < l; ++p) t[p] = nt[(s[p >> 2] >> (((p & 3u) ^ 3u) << 1)) & 3];
+        t[l] = '\n';
+    }
+}
+
+/* every read's corrected sequence to fo, fetched in pieces through the context's staging buffer */
+static int ec_write_sequences(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, FILE *fo)
+{
+    const uint64_t PIECE = 64ull << 20;
+    const uint64_t nr = sr_db->n;
+    uint64_t b, r0, i, n_bases = 0;
+    int rc = oatk_hip_ec_corrected_reads(ctx, &n_bases);
+    if (rc) return rc;
+    uint32_t *clen = (uint32_t *) fetch(ctx, OATK_BUF_EC_CSEQ_LEN, &b, &rc); if (rc) return rc;
+    uint64_t *coff = (uint64_t *) fetch(ctx, OATK_BUF_EC_CSEQ_OFF, &b, &rc); if (rc) { free(clen); return rc; }
+    const void *d_cseq = 0;
+    rc = oatk_hip_buffer(ctx, OATK_BUF_EC_CSEQ, &d_cseq, &b);
+    if (!rc && b != coff[nr]) rc = OATK_E_STATE;
+    uint64_t *toff = (uint64_t *) xmalloc(8 * (nr + 1));
+    char *text = 0;
+    uint64_t text_cap = 0;
+    for (r0 = 0; !rc && r0 < nr; ) {
+        uint64_t r1 = r0 + 1;
+        while (r1 < nr && coff[r1 + 1] - coff[r0] <= PIECE) ++r1;
+        const uint64_t bytes = coff[r1] - coff[r0];
+        uint8_t *stage = bytes? (uint8_t *) oatk_hip_staging(ctx, bytes > PIECE? bytes : PIECE) : 0;
+        if (bytes && !stage) { rc = OATK_E_NOMEM; break; }
+        if (bytes && (rc = oatk_hip_d2h(ctx, stage, (const uint8_t *) d_cseq + coff[r0], bytes)) != 0) break;
+        for (i = r0, toff[0] = 0; i < r1; ++i) toff[i - r0 + 1] = toff[i - r0] + 1 + strlen(sr_db->a[i].sname? sr_db->a[i].sname : "(null)") + 1 + clen[i] + 1;
+        const uint64_t tb = toff[r1 - r0];
+        if (tb > text_cap) { free(text); text = (char *) xmalloc(tb), text_cap = tb; }
+        ecs_job_t job = {sr_db, stage, coff, clen, toff, text, r0, r1};
+        oatk_par_run(ecs_worker, &job);
+        if (fwrite(text, 1, tb, fo) != tb) { fprintf(stderr, "[E::%s] could not write the corrected reads\n", __func__); rc = OATK_E_ARG; }
+        r0 = r1;
+    }
+    free(text); free(toff); free(clen); free(coff);
+    return rc;
+}
+
+static int ec_impl(oatk_hip_ctx *ctx, oatk_sr_db_t *sr_db, oatk_syncmer_db_t *scm_db, oatk_asmg_t *asmg, double max_edist,
+                   uint32_t err_mer_c, uint32_t max_err_c, uint32_t err_arc_c, double max_arc_f, FILE *fo, uint64_t *stats12)
 {
     uint64_t i, b;
     int rc;
+    /* the solver records q_end and the optimum consensus of the blocks it replaces only for this call */
+    if ((rc = oatk_hip_ec_keep_seq(ctx, fo != 0)) != 0) return rc;
     uint64_t *arc_v = 0, *arc_w = 0;
     uint64_t nv = 0, na = 0;
     if (!asmg) {
@@ -116,6 +190,7 @@ int oatk_read_error_correction(oatk_hip_ctx *ctx, oatk_sr_db_t *sr_db, oatk_sync
         rc = err_mer_c > 0 && err_arc_c >= err_mer_c && max_err_c >= err_mer_c? oatk_hip_ec_graph_light(ctx, err_mer_c) : oatk_hip_ec_graph(ctx);
         if (rc) return rc;
         rc = oatk_hip_ec(ctx, 0, max_edist, err_mer_c, max_err_c, err_arc_c, max_arc_f);
+        (void) oatk_hip_ec_keep_seq(ctx, 0);
         if (rc) return rc;
     } else {
     nv = asmg->n_vtx, na = asmg->n_arc;
@@ -134,6 +209,7 @@ int oatk_read_error_correction(oatk_hip_ctx *ctx, oatk_sr_db_t *sr_db, oatk_sync
     g.n_vtx = nv, g.n_arc = na, g.idx_p = asmg->idx_p, g.idx_n = idx_n, g.arc_v = arc_v, g.arc_w = arc_w, g.arc_ls = arc_ls;
     g.arc_cov = arc_cov, g.arc_del = arc_del;
     rc = oatk_hip_ec(ctx, &g, max_edist, err_mer_c, max_err_c, err_arc_c, max_arc_f);
+    (void) oatk_hip_ec_keep_seq(ctx, 0);
     free(idx_n); free(arc_ls); free(arc_cov); free(arc_del);
     if (rc) { free(arc_v); free(arc_w); return rc; }
     }
@@ -152,6 +228,8 @@ int oatk_read_error_correction(oatk_hip_ctx *ctx, oatk_sr_db_t *sr_db, oatk_sync
     err_del = (uint8_t *) fetch(ctx, OATK_BUF_EC_ERR_DEL, &b, &rc); if (rc) goto done;
     occ_off = (uint64_t *) fetch(ctx, OATK_BUF_EC_SCM_OCC_OFF, &b, &rc); if (rc) goto done;
     occ = (uint64_t *) fetch(ctx, OATK_BUF_EC_SCM_OCC, &b, &rc); if (rc) goto done;
+    /* the sequences go out while the reads still carry what they were corrected from (the names are all they give) */
+    if (fo && (rc = ec_write_sequences(ctx, sr_db, fo)) != 0) goto done;
 
     /* graph: what find_error_syncmers(..., del_err = 1) leaves behind -- every arc touching a marked syncmer */
     if (asmg) {
@@ -165,4 +243,16 @@ done:
     free(arc_v); free(arc_w);
     free(new_n); free(new_k); free(new_m); free(new_s); free(cov); free(del); free(err_del); free(occ_off); free(occ);
     return rc;
+}
+
+int oatk_read_error_correction(oatk_hip_ctx *ctx, oatk_sr_db_t *sr_db, oatk_syncmer_db_t *scm_db, oatk_asmg_t *asmg, double max_edist,
+                               uint32_t err_mer_c, uint32_t max_err_c, uint32_t err_arc_c, double max_arc_f, uint64_t *stats12)
+{
+    return ec_impl(ctx, sr_db, scm_db, asmg, max_edist, err_mer_c, max_err_c, err_arc_c, max_arc_f, 0, stats12);
+}
+
+int oatk_read_error_correction_fo(oatk_hip_ctx *ctx, oatk_sr_db_t *sr_db, oatk_syncmer_db_t *scm_db, oatk_asmg_t *asmg, double max_edist,
+                                  uint32_t err_mer_c, uint32_t max_err_c, uint32_t err_arc_c, double max_arc_f, FILE *fo, uint64_t *stats12)
+{
+    return ec_impl(ctx, sr_db, scm_db, asmg, max_edist, err_mer_c, max_err_c, err_arc_c, max_arc_f, fo, stats12);
 }

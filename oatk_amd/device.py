@@ -19,6 +19,7 @@ _DTYPES = {
     "EC_N_SCM": np.uint32, "EC_SCM_OFF": np.uint64, "EC_KMER": np.uint64, "EC_MPOS": np.uint32, "EC_SMER": np.uint64,
     "EC_SCM_COV": np.uint32, "EC_SCM_DEL": np.uint8, "EC_SCM_OCC_OFF": np.uint64, "EC_SCM_OCC": np.uint64, "EC_ERR_DEL": np.uint8,
     "EC_SCM_FWD": np.uint32, "EC_VTX_SRC": np.uint64, "EC_BLOCK_WORK": np.uint32, "EC_BLOCK_OUT": np.uint32,
+    "EC_CSEQ_LEN": np.uint32, "EC_CSEQ_OFF": np.uint64, "EC_CSEQ": np.uint8, "EC_BLOCK_QEND": np.uint32,
     "INGEST_SEQ": np.uint8, "INGEST_OFF": np.uint64, "INGEST_LEN": np.uint32, "INGEST_HDR": np.uint64,
     "CONS_SEL": np.uint32, "CONS_SLOT": np.uint32, "CONS_RL": np.uint32, "CONS_MSEQ": np.uint32, "CONS_FIRST": np.uint64, "CONS_TOT": np.uint64,
     "EG_IDX_P": np.uint64, "EG_IDX_N": np.uint32, "EG_ARC_V": np.uint64, "EG_ARC_W": np.uint64, "EG_ARC_LS": np.uint32,
@@ -186,9 +187,11 @@ class HipSyncasm:
         else:
             self._check(self.L.oatk_hip_ec_graph(self.h), "oatk_hip_ec_graph")
 
-    def ec(self, max_edist, c, a, graph=None):
+    def ec(self, max_edist, c, a, graph=None, keep_seq=False):
         """read_error_correction(sr_db, g, max_edist, c, 10 c, c, a) (run_syncasm.c:124, syncerr.c:819); `graph` = dict of
-        host arrays shaped like oatk_ec_graph_t, or None for the graph ec_graph() left resident.  Returns stats[12]."""
+        host arrays shaped like oatk_ec_graph_t, or None for the graph ec_graph() left resident.  keep_seq: the solver also leaves what
+        corrected_reads() needs (oatk_hip_ec_keep_seq; the results are the same either way).  Returns stats[12]."""
+        self.ec_keep_seq(keep_seq)
         if graph is None:
             rc = self.L.oatk_hip_ec(self.h, None, max_edist, c, 10 * c, c, a)
         else:
@@ -275,6 +278,21 @@ class HipSyncasm:
         return st
 
     # the same in steps, and the calls for reads sharded over GPUs (device pointers as ints; oatk_amd/multi.py drives them)
+    def ec_keep_seq(self, on):
+        self._check(self.L.oatk_hip_ec_keep_seq(self.h, 1 if on else 0), "oatk_hip_ec_keep_seq")
+
+    def corrected_reads(self):
+        """every read's corrected sequence in hoco space, as read_error_correction writes them to its FILE *fo (syncerr.c:614-624), after a
+        correction with keep_seq: a list of bytes over ACGT in read order"""
+        n = C.c_uint64(0)
+        self._check(self.L.oatk_hip_ec_corrected_reads(self.h, C.byref(n)), "oatk_hip_ec_corrected_reads")
+        ln, off, packed = self.fetch("EC_CSEQ_LEN"), self.fetch("EC_CSEQ_OFF"), self.fetch("EC_CSEQ")
+        assert int(ln.sum(dtype=np.uint64)) == n.value
+        # four bases to a byte, the first in the top bits
+        codes = np.stack([(packed >> s) & 3 for s in (6, 4, 2, 0)], axis=1).reshape(-1)
+        text = np.frombuffer(b"ACGT", np.uint8)[codes]
+        return [text[4 * int(o):4 * int(o) + int(l)].tobytes() for o, l in zip(off[:-1], ln)]
+
     def ec_mark(self, c, a):
         self._check(self.L.oatk_hip_ec_mark(self.h, c, 10 * c, c, a), "oatk_hip_ec_mark")
 
