@@ -7,7 +7,7 @@
  *     sr_db_stat                   syncmer.c:867      -> oatk_sr_db_stat
  *     collect_syncmer_from_reads   syncmer.c:1397     -> oatk_collect_syncmer_from_reads
  *     make_syncmer_graph           syncasm.c:203      -> oatk_hip_ec_graph (the (0, 0.) call) / oatk_make_syncmer_asmg
- *     read_error_correction        syncerr.c:819      -> oatk_read_error_correction_fo   (its FILE *fo of corrected reads included, on one handle)
+ *     read_error_correction        syncerr.c:819      -> oatk_read_error_correction_fo   (its FILE *fo of corrected reads included; several handles: oatk_multi_read_error_correction_fo)
  *     scg_read_alignment           alignment.c:596    -> oatk_scg_read_alignment
  *     sr_destroy, sr_db_clean, sr_db_destroy, syncmer_db_clean, syncmer_db_destroy   syncmer.c:1047-1110   -> oatk_sr_destroy / oatk_sr_db_clean /
  *                                  oatk_syncmer_db_clean: owning these is what lets sr_read

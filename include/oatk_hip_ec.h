@@ -92,7 +92,13 @@ enum {
  *                                       that ends EC_SUCCESS or EC_AMBISNQ, q_end of the optimum alignment and the optimum consensus.  Every EC_* result and
  *                                       the statistics are what they are without it.
  *   oatk_hip_ec_corrected_reads(ctx, &n) builds EC_CSEQ_LEN / EC_CSEQ_OFF / EC_CSEQ from that; *n_bases (may be NULL) = bases of all corrected reads.
- * OATK_E_STATE: the resident correction was made with the switch off, a scan has been made since, or the reads are sharded (oatk_hip_ec_set_global). */
+ * Sharded reads (oatk_hip_ec_set_global, oatk_hip_ec_sharded of include/oatk_hip_multi.h): the same two calls.  A rank corrects its own reads, a replaced
+ * body is spelled from the optimum consensus whether the path's k-mers were the shard's own or imported (oatk_hip_ec_import_kmers), so the strings are
+ * rank-local: read 0 of EC_CSEQ_LEN / _OFF is the handle's FIRST read (global read sid0), and the handles' outputs in rank order are the reference's file.
+ * They stay readable across oatk_hip_gather_table, oatk_hip_asm_graph_sharded, oatk_hip_consensus_sharded and oatk_hip_read_alignment, until the next scan
+ * or correction.
+ * OATK_E_STATE: the resident correction was made with the switch off; a scan, a new table merge or oatk_hip_ec_set_global has happened since; or the handle's
+ * id space is not the one the correction was made in (a correction on local ids and a handle that is sharded now, or the reverse). */
 int oatk_hip_ec_keep_seq(oatk_hip_ctx *ctx, int on);
 int oatk_hip_ec_corrected_reads(oatk_hip_ctx *ctx, uint64_t *n_bases);
 

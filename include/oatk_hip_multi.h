@@ -79,7 +79,14 @@ int oatk_hip_multi_range(oatk_hip_ctx *ctx, uint64_t *first_id, uint64_t *n_owne
  * GLOBAL syncmer ids, and MG_EC_COV u32[n_owned] / MG_EC_DEL u8[n_owned] hold update_syncmer_db's table over all shards for this rank's range;
  * stats12 (may be NULL) receives the block statistics summed over the ranks, *n_imported (may be NULL) the k-mers this rank had to be sent.
  * With err_arc_c < err_mer_c (never from syncasm, run_syncasm.c:124) the light graph cannot serve: every pair of every shard travels and the
- * whole table is gathered on every rank -- correct, and as expensive as the number of shards makes it. */
+ * whole table is gathered on every rank -- correct, and as expensive as the number of shards makes it.
+ *
+ * The corrected reads' SEQUENCES (read_error_correction's FILE *fo; include/oatk_hip_ec.h): the call reads the switch oatk_hip_ec_keep_seq exactly as
+ * oatk_hip_ec does -- set it on the handle before, it holds until it is cleared.  Afterwards oatk_hip_ec_corrected_reads(ctx, &n) is a LOCAL call, not a
+ * collective: a rank may make it or not, in any order relative to its peers, before or after oatk_hip_gather_table, oatk_hip_asm_graph_sharded,
+ * oatk_hip_consensus_sharded and oatk_hip_read_alignment on the same handle, until its next scan, merge or correction.  The numbering is per rank:
+ * read 0 of EC_CSEQ_LEN / EC_CSEQ_OFF is the handle's first read (the read the scan was given as sid0); a rank without reads answers OATK_OK with zero
+ * reads.  The ranks' strings in rank order are the reference's file in read order. */
 int oatk_hip_ec_sharded(oatk_hip_ctx *ctx, oatk_comm *comm, double max_edist, uint32_t err_mer_c, uint32_t max_err_c, uint32_t err_arc_c,
                         double max_arc_f, uint64_t *stats12, uint64_t *n_imported);
 

@@ -46,6 +46,13 @@ oatk_syncmer_db_t *oatk_multi_collect_syncmer_from_reads(oatk_multi *m, oatk_sr_
 /* read_error_correction (syncerr.c:819) with the EC graph built on the devices (the asmg == NULL form of oatk_read_error_correction) */
 int oatk_multi_read_error_correction(oatk_multi *m, oatk_sr_db_t *sr_db, oatk_syncmer_db_t *scm_db, double max_edist, uint32_t err_mer_c, uint32_t max_err_c,
                                      uint32_t err_arc_c, double max_arc_f, uint64_t *stats12);
+/* the same with the reference's FILE *fo (oatk_read_error_correction_fo on one handle): ">name\nSEQ\n" of every read's corrected sequence in hoco space, in
+ * sr_db order -- handle after handle, each handle's reads from its own resident correction (oatk_hip_ec_corrected_reads is rank-local) -- byte for byte the
+ * reference's file.  oatk_hip_ec_keep_seq is set on every handle for this one call and cleared on every way out.  Order: correction, table gather, every
+ * handle's text written, and only then sr_db / scm_db rewritten: any failure (the file included) leaves them as they were.  fo == NULL: no strings are
+ * built anywhere, this is oatk_multi_read_error_correction. */
+int oatk_multi_read_error_correction_fo(oatk_multi *m, oatk_sr_db_t *sr_db, oatk_syncmer_db_t *scm_db, double max_edist, uint32_t err_mer_c, uint32_t max_err_c,
+                                        uint32_t err_arc_c, double max_arc_f, FILE *fo, uint64_t *stats12);
 /* make_syncmer_graph(sr_db, scm_db, min_k_cov, min_a_cov_f) of the corrected reads (run_syncasm.c:138) */
 oatk_asmg_t *oatk_multi_make_syncmer_asmg(oatk_multi *m, oatk_syncmer_db_t *scm_db, uint32_t min_k_cov, double min_a_cov_f, int *rc);
 /* the consensus sums and distance tables behind scg_consensus (include/oatk_syncasm.h: oatk_consensus_fetch / oatk_overlap_fetch); the tables cover

@@ -59,7 +59,7 @@ EXPORTS = [
 
 # the N-handle mirror in liboatk_host.so (include/oatk_multi.h) of entry points listed above; EXPORTS itself is checked against liboatk_hip.so
 HOST_EXPORTS = ["oatk_multi_scg_ra_utg_coverage", "oatk_multi_scg_ra_arc_coverage", "oatk_scg_multiplex_plan", "oatk_multi_scg_multiplex_plan",
-                "oatk_triplet_table_free"]
+                "oatk_triplet_table_free", "oatk_multi_read_error_correction_fo"]
 
 
 def load_host():
@@ -80,6 +80,7 @@ def load_host():
     H.oatk_multi_collect_syncmer_from_reads.restype = vp
     H.oatk_multi_collect_syncmer_from_reads.argtypes = [vp, vp, C.POINTER(C.c_int)]
     H.oatk_multi_read_error_correction.argtypes = [vp, vp, vp, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, vp]
+    H.oatk_multi_read_error_correction_fo.argtypes = [vp, vp, vp, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, vp, vp]      # (..., FILE *fo, stats12)
     H.oatk_multi_make_syncmer_asmg.restype = vp
     H.oatk_multi_make_syncmer_asmg.argtypes = [vp, vp, C.c_uint32, C.c_double, C.POINTER(C.c_int)]
     H.oatk_multi_scg_read_alignment.argtypes = [vp, vp, vp, vp, C.c_int, C.POINTER(C.c_uint64)]

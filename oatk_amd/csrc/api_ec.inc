@@ -37,6 +37,7 @@ struct EcState {
     // corrected sequences (ec_seq.hpp)
     bool keep_seq = false;              // oatk_hip_ec_keep_seq: the next correction records q_end and the optimum consensus of the blocks it replaces
     bool seq_kept = false, cseq_done = false;      // the resident correction did; oatk_hip_ec_corrected_reads has run on it
+    bool seq_global = false;            // the id space that correction was made in (sharded reads: global ids); the strings are built in no other
     DevBuf slot_w, slot_w64, slot_off, slots, qend, sblk, clen, cbytes, cbytes64, coff, cseq;
     uint64_t cseq_bytes = 0;
 };
@@ -1271,7 +1272,7 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     CK(hipSetDevice(ctx->device));
     EcState *e = ctx->ec;
     e->done = false, e->cseq_done = false;
-    const bool keep_seq = e->keep_seq && !e->global;      // (sharded reads: corrected as ever; oatk_hip_ec_corrected_reads refuses them)
+    const bool keep_seq = e->keep_seq;                     // (sharded reads too: a rank corrects its own reads, and the slots are per block of this handle)
     e->seq_kept = false;
     const EcKnobs kn = ec_knobs_read();
     EC_VIEWS();
@@ -1413,7 +1414,7 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     for (int i = 0; i < 11; ++i) e->stats_h[i] = st[i];
     e->stats_h[11] = n_big;
     if (chk != tot) { ctx->err = "error correction: coverage does not add up"; return OATK_E_STATE; }
-    e->done = true, e->seq_kept = keep_seq;
+    e->done = true, e->seq_kept = keep_seq, e->seq_global = e->global;
     return OATK_OK;
 }
 
@@ -1431,7 +1432,13 @@ extern "C" int oatk_hip_ec_corrected_reads(oatk_hip_ctx *ctx, uint64_t *n_bases)
     using namespace oatk;
     if (!ctx) return OATK_E_NODEV;
     EcState *e = ctx->ec;
-    if (e && e->global) { ctx->err = "oatk_hip_ec_corrected_reads: sharded reads are not supported"; return OATK_E_STATE; }
+    // (a change of id space drops the correction as a scan does -- oatk_hip_ec_set_global, api.hip: scan_reset_downstream --; named here because the blocks and slots
+    //  of the old space are still allocated and must never be read against the new one)
+    if (e && e->seq_kept && e->seq_global != e->global) {
+        ctx->err = e->global? "oatk_hip_ec_corrected_reads: the resident correction was made on one handle's ids and the handle is sharded now (correct again: oatk_hip_ec_sharded)"
+                            : "oatk_hip_ec_corrected_reads: the resident correction was made on sharded reads (global ids) and the handle is not sharded any more (correct again)";
+        return OATK_E_STATE;
+    }
     if (!e || !e->done || !e->seq_kept || !ctx->scanned) { ctx->err = "oatk_hip_ec_corrected_reads needs a correction of the resident batch made with oatk_hip_ec_keep_seq"; return OATK_E_STATE; }
     CK(hipSetDevice(ctx->device));
     e->cseq_done = false;          // (a call that fails half-way leaves nothing readable)

@@ -401,10 +401,9 @@ void read_error_correction(oatk_sr_db_t *sr_db, oatk_scg_t *g, double max_edist,
     uint64_t st[12];
     hooks_off();                                                        /* the chains are about to change */
     if (!D.resident || !D.counted || sr_db != D.sr_db || !g || g->scm_db != D.scm_db) why = "no resident batch";
-    else if (fo && D.multi) why = "the corrected reads are to be written out and the reads are spread over several handles: the original does that";
     if (!why) {
         oatk_host_set_threads(n_threads);
-        int rc = D.multi? (placeholder? oatk_multi_read_error_correction(D.multi, sr_db, g->scm_db, max_edist, err_mer_c, max_err_c, err_arc_c, max_arc_f, st) : OATK_E_ARG)
+        int rc = D.multi? (placeholder? oatk_multi_read_error_correction_fo(D.multi, sr_db, g->scm_db, max_edist, err_mer_c, max_err_c, err_arc_c, max_arc_f, fo, st) : OATK_E_ARG)
                         : oatk_read_error_correction_fo(D.ctx, sr_db, g->scm_db, placeholder? 0 : g->utg_asmg, max_edist, err_mer_c, max_err_c, err_arc_c, max_arc_f, fo, st);
         if (rc == OATK_E_SPLIT && placeholder && !D.multi) {
             /* the device refuses to ORDER this graph (duplicate arcs of a long tandem repeat, an arc with dozens of distances): the original

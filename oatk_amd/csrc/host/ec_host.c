@@ -104,9 +104,11 @@ void oatk_host_ec_write_back(oatk_sr_db_t *sr_db, oatk_syncmer_db_t *scm_db, con
     free(job.new_off);
 }
 
-/* ">name\nSEQ\n" of the reads [r0, r1) of a piece: packed strings (two bits per base, first base in the top bits) to ACGT, a slice of the reads per thread */
+/* ">name\nSEQ\n" of the reads [r0, r1) of a piece: packed strings (two bits per base, first base in the top bits) to ACGT, a slice of the reads per thread.
+ * r counts the HANDLE's reads: read r is sr_db->a[first + r] (first = 0 on one handle). */
 typedef struct {
     const oatk_sr_db_t *sr_db;
+    uint64_t first;
     const uint8_t *packed;         /* the piece: read r at packed + (coff[r] - coff[r0]) */
     const uint64_t *coff;
     const uint32_t *clen;
@@ -122,7 +124,7 @@ static void ecs_worker(void *arg, int tid, int n_threads)
     const uint64_t n = j->r1 - j->r0, ra = j->r0 + n * (uint64_t) tid / (uint64_t) n_threads, rb = j->r0 + n * (uint64_t) (tid + 1) / (uint64_t) n_threads;
     uint64_t r;
     for (r = ra; r < rb; ++r) {
-        const char *name = j->sr_db->a[r].sname? j->sr_db->a[r].sname : "(null)";      /* (what printf makes of a NULL %s) */
+        const char *name = j->sr_db->a[j->first + r].sname? j->sr_db->a[j->first + r].sname : "(null)";      /* (what printf makes of a NULL %s) */
         const size_t nl = strlen(name);
         const uint8_t *s = j->packed + (j->coff[r] - j->coff[j->r0]);
         const uint32_t l = j->clen[r];
@@ -140,15 +142,18 @@ static void ecs_worker(void *arg, int tid, int n_threads)
     }
 }
 
-/* every read's corrected sequence to fo, fetched in pieces through the context's staging buffer */
-static int ec_write_sequences(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, FILE *fo)
+/* the corrected sequences of the reads a handle holds -- sr_db->a[first .. first + count), the handle's reads 0 .. count -- to fo, fetched in pieces through the
+ * context's staging buffer (host_internal.h; one handle: first = 0, count = sr_db->n) */
+int oatk_host_ec_write_sequences(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, uint64_t first, uint64_t count, FILE *fo)
 {
     const uint64_t PIECE = 64ull << 20;
-    const uint64_t nr = sr_db->n;
+    const uint64_t nr = count;
     uint64_t b, r0, i, n_bases = 0;
+    if (first > sr_db->n || count > sr_db->n - first) return OATK_E_ARG;
     int rc = oatk_hip_ec_corrected_reads(ctx, &n_bases);
     if (rc) return rc;
     uint32_t *clen = (uint32_t *) fetch(ctx, OATK_BUF_EC_CSEQ_LEN, &b, &rc); if (rc) return rc;
+    if (b != 4 * nr) { free(clen); return OATK_E_STATE; }          /* (the handle holds other reads than the caller thinks) */
     uint64_t *coff = (uint64_t *) fetch(ctx, OATK_BUF_EC_CSEQ_OFF, &b, &rc); if (rc) { free(clen); return rc; }
     const void *d_cseq = 0;
     rc = oatk_hip_buffer(ctx, OATK_BUF_EC_CSEQ, &d_cseq, &b);
@@ -163,10 +168,10 @@ static int ec_write_sequences(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, FILE
         uint8_t *stage = bytes? (uint8_t *) oatk_hip_staging(ctx, bytes > PIECE? bytes : PIECE) : 0;
         if (bytes && !stage) { rc = OATK_E_NOMEM; break; }
         if (bytes && (rc = oatk_hip_d2h(ctx, stage, (const uint8_t *) d_cseq + coff[r0], bytes)) != 0) break;
-        for (i = r0, toff[0] = 0; i < r1; ++i) toff[i - r0 + 1] = toff[i - r0] + 1 + strlen(sr_db->a[i].sname? sr_db->a[i].sname : "(null)") + 1 + clen[i] + 1;
+        for (i = r0, toff[0] = 0; i < r1; ++i) toff[i - r0 + 1] = toff[i - r0] + 1 + strlen(sr_db->a[first + i].sname? sr_db->a[first + i].sname : "(null)") + 1 + clen[i] + 1;
         const uint64_t tb = toff[r1 - r0];
         if (tb > text_cap) { free(text); text = (char *) xmalloc(tb), text_cap = tb; }
-        ecs_job_t job = {sr_db, stage, coff, clen, toff, text, r0, r1};
+        ecs_job_t job = {sr_db, first, stage, coff, clen, toff, text, r0, r1};
         oatk_par_run(ecs_worker, &job);
         if (fwrite(text, 1, tb, fo) != tb) { fprintf(stderr, "[E::%s] could not write the corrected reads\n", __func__); rc = OATK_E_ARG; }
         r0 = r1;
@@ -229,7 +234,7 @@ static int ec_impl(oatk_hip_ctx *ctx, oatk_sr_db_t *sr_db, oatk_syncmer_db_t *sc
     occ_off = (uint64_t *) fetch(ctx, OATK_BUF_EC_SCM_OCC_OFF, &b, &rc); if (rc) goto done;
     occ = (uint64_t *) fetch(ctx, OATK_BUF_EC_SCM_OCC, &b, &rc); if (rc) goto done;
     /* the sequences go out while the reads still carry what they were corrected from (the names are all they give) */
-    if (fo && (rc = ec_write_sequences(ctx, sr_db, fo)) != 0) goto done;
+    if (fo && (rc = oatk_host_ec_write_sequences(ctx, sr_db, 0, sr_db->n, fo)) != 0) goto done;
 
     /* graph: what find_error_syncmers(..., del_err = 1) leaves behind -- every arc touching a marked syncmer */
     if (asmg) {

@@ -18,6 +18,9 @@ oatk_syncmer_db_t *oatk_host_build_syncmer_db(oatk_sr_db_t *sr_db, uint64_t n_sc
  * chains concatenated in read order, the refreshed table.  With arenas the chain arrays and `occ` are adopted (the pointers are cleared). */
 void oatk_host_ec_write_back(oatk_sr_db_t *sr_db, oatk_syncmer_db_t *scm_db, const uint32_t *new_n, uint64_t **new_k, uint32_t **new_m, uint64_t **new_s,
                              const uint32_t *cov, const uint8_t *del, const uint64_t *occ_off, uint64_t **occ);
+/* ">name\nSEQ\n" of the corrected sequences (read_error_correction's FILE *fo, syncerr.c:614-624) of the reads ctx holds, after a correction made with
+ * oatk_hip_ec_keep_seq: the handle's reads 0 .. count are sr_db->a[first .. first + count) (one handle: 0, sr_db->n).  Only the names are read from sr_db. */
+int oatk_host_ec_write_sequences(oatk_hip_ctx *ctx, const oatk_sr_db_t *sr_db, uint64_t first, uint64_t count, FILE *fo);
 /* asmg_t from the graph resident in ctx (OATK_BUF_AG_*), scm_db->a[i].del updated like syncasm.c:228 */
 oatk_asmg_t *oatk_host_asmg_from_resident(oatk_hip_ctx *ctx, oatk_syncmer_db_t *scm_db, uint64_t nv, uint64_t na, int *rc);
 oatk_consensus_t *oatk_host_consensus_from_resident(oatk_hip_ctx *ctx, int k, int *rc);

@@ -336,6 +336,16 @@ static int ec_rank(oatk_multi *m, int rank, void *arg)
 int oatk_multi_read_error_correction(oatk_multi *m, oatk_sr_db_t *sr_db, oatk_syncmer_db_t *scm_db, double max_edist, uint32_t err_mer_c, uint32_t max_err_c,
                                      uint32_t err_arc_c, double max_arc_f, uint64_t *stats12)
 {
+    return oatk_multi_read_error_correction_fo(m, sr_db, scm_db, max_edist, err_mer_c, max_err_c, err_arc_c, max_arc_f, 0, stats12);
+}
+
+/* With a file: the solvers of every handle record q_end and the optimum consensus of the blocks they replace, for this one call; after the correction and
+ * the gather every handle's reads go out in handle order = read order (a rank's strings are its own business: oatk_hip_ec_corrected_reads is local), and
+ * only then are the reads and the table rewritten. */
+int oatk_multi_read_error_correction_fo(oatk_multi *m, oatk_sr_db_t *sr_db, oatk_syncmer_db_t *scm_db, double max_edist, uint32_t err_mer_c, uint32_t max_err_c,
+                                        uint32_t err_arc_c, double max_arc_f, FILE *fo, uint64_t *stats12)
+{
+    if (!m) return OATK_E_NODEV;
     ec_arg_t *a = (ec_arg_t *) calloc(1, sizeof(ec_arg_t));
     int rc, r;
     table_t t;
@@ -344,7 +354,9 @@ int oatk_multi_read_error_correction(oatk_multi *m, oatk_sr_db_t *sr_db, oatk_sy
     memset(&t, 0, sizeof(t));
     a->max_edist = max_edist, a->max_arc_f = max_arc_f, a->err_mer_c = err_mer_c, a->max_err_c = max_err_c, a->err_arc_c = err_arc_c;
     if (!m->have_reads || m->first[m->n] != sr_db->n) { snprintf(m->err, sizeof(m->err), "the handles do not hold this database's reads"); rc = OATK_E_STATE; goto done; }
-    rc = run_ranks(m, ec_rank, a);
+    for (r = 0, rc = OATK_OK; r < m->n && !rc; ++r) { rc = oatk_hip_ec_keep_seq(m->ctx[r], fo != 0); note_err(m, r, rc); }
+    if (!rc) rc = run_ranks(m, ec_rank, a);
+    for (r = 0; r < m->n; ++r) (void) oatk_hip_ec_keep_seq(m->ctx[r], 0);       /* (read when the correction starts: it has, or never will) */
     if (rc) goto done;
     if (stats12) memcpy(stats12, a->st[0], sizeof(a->st[0]));       /* summed over the ranks, the same on each */
     /* everything is fetched before anything is rewritten: a failure here leaves the reads and the table as they were */
@@ -371,6 +383,14 @@ int oatk_multi_read_error_correction(oatk_multi *m, oatk_sr_db_t *sr_db, oatk_sy
         }
         if (!rc && at != t.n_occ) { snprintf(m->err, sizeof(m->err), "the refreshed table and the corrected chains disagree"); rc = OATK_E_STATE; }
     }
+    /* the sequences go out while the reads still carry what they were corrected from (the names are all they give), handle after handle */
+    for (r = 0; fo && r < m->n && !rc; ++r) {
+        const uint64_t nr = m->first[r + 1] - m->first[r];
+        if (nr == 0) continue;
+        rc = oatk_host_ec_write_sequences(m->ctx[r], sr_db, m->first[r], nr, fo);
+        if (rc) snprintf(m->err, sizeof(m->err), "handle %d: the corrected reads: %s", r, oatk_hip_last_error(m->ctx[r]));
+    }
+    if (fo && !rc && fflush(fo) != 0) { snprintf(m->err, sizeof(m->err), "could not write the corrected reads"); rc = OATK_E_ARG; }     /* (nothing is rewritten over a file that did not take them) */
     if (!rc) oatk_host_ec_write_back(sr_db, scm_db, new_n, &new_k, &new_m, &new_s, t.cov, t.del, t.occ_off, &t.occ);
 done:
     free(new_n); free(new_k); free(new_m); free(new_s);

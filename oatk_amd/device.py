@@ -124,7 +124,10 @@ class HipSyncasm:
         self._check(self.L.oatk_hip_multi_range(self.h, C.byref(a), C.byref(b), C.byref(g)), "oatk_hip_multi_range")
         return int(a.value), int(b.value), int(g.value)
 
-    def ec_sharded(self, comm, max_edist, c, a):
+    def ec_sharded(self, comm, max_edist, c, a, keep_seq=False):
+        """oatk_hip_ec_sharded: (block statistics summed over the ranks, k-mers this rank was sent).  keep_seq: as for ec() -- corrected_reads() then gives
+        THIS rank's reads, read 0 being the handle's first; it is a local call, any rank may make it or not"""
+        self.ec_keep_seq(keep_seq)
         st = np.zeros(12, np.uint64)
         ni = C.c_uint64()
         self._check(self.L.oatk_hip_ec_sharded(self.h, comm, max_edist, c, 10 * c, c, a, st.ctypes.data, C.byref(ni)), "oatk_hip_ec_sharded")
@@ -283,7 +286,8 @@ class HipSyncasm:
 
     def corrected_reads(self):
         """every read's corrected sequence in hoco space, as read_error_correction writes them to its FILE *fo (syncerr.c:614-624), after a
-        correction with keep_seq: a list of bytes over ACGT in read order"""
+        correction with keep_seq: a list of bytes over ACGT in read order.  On a sharded handle (ec_sharded, ShardedEc.run): the handle's own reads,
+        and the ranks' lists in rank order are the list of one handle holding all reads."""
         n = C.c_uint64(0)
         self._check(self.L.oatk_hip_ec_corrected_reads(self.h, C.byref(n)), "oatk_hip_ec_corrected_reads")
         ln, off, packed = self.fetch("EC_CSEQ_LEN"), self.fetch("EC_CSEQ_OFF"), self.fetch("EC_CSEQ")

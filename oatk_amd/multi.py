@@ -154,8 +154,10 @@ class ShardedEc:
         if self.device.type == "cuda":
             torch.cuda.current_stream(self.device).synchronize()
 
-    def run(self, max_edist, c, a):
+    def run(self, max_edist, c, a, keep_seq=False):
+        """keep_seq: the solver also leaves what hip.corrected_reads() needs (oatk_hip_ec_keep_seq) -- this rank's reads, no exchange"""
         hip, dist, dev = self.hip, self.dist, self.device
+        hip.ec_keep_seq(keep_seq)
         rank = dist.get_rank()
         G, S, cov, l2g = self.merger.merge()
         n_global = int(G.numel())
