@@ -13,7 +13,9 @@
  *   FASTQ   four lines per record: '@' header, sequence, '+' line, quality of the same length (the form every sequencer writes)
  *   KSEQ    anything kseq reads with headers at line starts: wrapped FASTQ, FASTA and FASTQ records in one stream (OATK_FMT_KSEQ below)
  * Read names are not kept on the device (sr_t.sname is only ever printed): OATK_BUF_INGEST_HDR gives the header-line offsets for a
- * caller that wants them.  gzip'ed input must be inflated by the caller (zlib is serial per stream, on any hardware).
+ * caller that wants them.  gzip'ed input: a DEFLATE stream is serial on any hardware, but a BGZF file (bgzip) is a hundred thousand independent
+ * streams of at most 64 KiB -- oatk_hip_inflate_bgzf below inflates those on the device, one wave per member, so that the compressed bytes cross the
+ * bus and the text first exists where oatk_hip_ingest wants it.  A plain gzip member (one stream) must still be inflated by the caller.
  */
 #ifndef OATK_HIP_INGEST_H
 #define OATK_HIP_INGEST_H
@@ -49,6 +51,35 @@ int oatk_hip_ingest_truncate(oatk_hip_ctx *ctx, uint64_t n_keep);
 int oatk_hip_ingest_text_buffer(oatk_hip_ctx *ctx, uint64_t n_bytes, uint8_t **d_text);
 /* oatk_hip_scan on the resident packed stream: reads are numbered sid0, sid0 + 1, ... in file order (syncmer.c:525) */
 int oatk_hip_scan_ingested(oatk_hip_ctx *ctx, uint64_t sid0, int k, int s);
+
+/* ---- BGZF members inflated on the device (oatk_amd/csrc/inflate.hpp) ----
+ * in_off / in_len: the raw deflate stream of the member inside d_comp (gzip header and 8-byte trailer excluded); out_off / out_len: its place in d_text
+ * (out_len is the trailer's ISIZE); crc: the trailer's CRC-32.  oatk_bgzf_index (include/oatk_inflate.h) makes such a table from the bytes of a file. */
+typedef struct { uint64_t in_off; uint32_t in_len, out_len; uint64_t out_off; uint32_t crc, pad; } oatk_bgzf_member_t;
+
+#define OATK_INF_OK 0             /* status of a member: its text is in place, as long as its trailer says and with the trailer's CRC-32 */
+#define OATK_INF_STREAM 1         /* not a DEFLATE stream this decoder takes: ends early, bytes behind the final block, a bad code set, a distance that reaches
+                                   * before the member's first byte, block type 3, LEN != ~NLEN ... (it may refuse what zlib accepts: an incomplete code set) */
+#define OATK_INF_LENGTH 2         /* the stream holds more or less text than out_len */
+#define OATK_INF_CRC 3            /* the text's CRC-32 is not the member's */
+
+/* Inflate n members on the context's stream.  The table is checked on the host first -- every member inside comp_bytes, in_len and out_len <= 65536, outputs
+ * ascending, disjoint and inside text_cap: OATK_E_ARG otherwise, nothing launched.  OATK_OK means the call ran, whatever *n_bad (members with a status other than 0;
+ * h_status, n bytes, may be NULL) says: what a bad member means is the caller's decision.  Nothing outside the members' own output ranges is written; the range of a
+ * member with status 1 or 2 is left as it was.  The call returns when the text, the statuses and the count are complete. */
+int oatk_hip_inflate_bgzf(oatk_hip_ctx *ctx, const uint8_t *d_comp, uint64_t comp_bytes, const oatk_bgzf_member_t *h_members, uint64_t n,
+                          uint8_t *d_text, uint64_t text_cap, uint64_t *n_bad, uint8_t *h_status);
+/* the same with the compressed bytes in host memory (one upload first) */
+int oatk_hip_inflate_bgzf_host(oatk_hip_ctx *ctx, const uint8_t *h_comp, uint64_t comp_bytes, const oatk_bgzf_member_t *h_members, uint64_t n,
+                               uint8_t *d_text, uint64_t text_cap, uint64_t *n_bad, uint8_t *h_status);
+/* the last byte of the text the context's latest oatk_hip_inflate_bgzf produced (0: none): kseq gives a file that ends without a newline one */
+int oatk_hip_inflate_last_byte(oatk_hip_ctx *ctx);
+
+/* The names of the records the context's latest oatk_hip_ingest found (after oatk_hip_ingest_truncate: of those kept), cut out of the text ON THE DEVICE -- for text
+ * that has no copy on the host, such as a window inflated there.  d_text / n_bytes: the text that ingest was given.  A name is what follows the header character up
+ * to the first space, tab, CR or LF, or the end of the text.  *h_off: n + 1 offsets into *h_packed, the names back to back without terminators; both lie in host
+ * memory owned by the context, valid until its next call. */
+int oatk_hip_ingest_names(oatk_hip_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const uint8_t **h_packed, const uint64_t **h_off, uint64_t *n_names);
 
 /* INGEST_SEQ u8[seq_bytes]  INGEST_OFF u64[n_reads]  INGEST_LEN u32[n_reads]  INGEST_HDR u64[n_reads] byte offset of each header line */
 enum { OATK_BUF_INGEST_SEQ = 160, OATK_BUF_INGEST_OFF, OATK_BUF_INGEST_LEN, OATK_BUF_INGEST_HDR };

@@ -55,11 +55,12 @@ EXPORTS = [
     "oatk_hip_ra_utg_coverage", "oatk_hip_ra_arc_coverage", "oatk_hip_debug_racov_cap", "oatk_hip_ra_utg_coverage_sharded", "oatk_hip_ra_arc_coverage_sharded",
     "oatk_hip_ra_triplet_scores", "oatk_hip_ra_triplet_scores_sharded",
     "oatk_hip_ec_keep_seq", "oatk_hip_ec_corrected_reads",
+    "oatk_hip_inflate_bgzf", "oatk_hip_inflate_bgzf_host", "oatk_hip_inflate_last_byte", "oatk_hip_ingest_names",
 ]
 
 # the N-handle mirror in liboatk_host.so (include/oatk_multi.h) of entry points listed above; EXPORTS itself is checked against liboatk_hip.so
 HOST_EXPORTS = ["oatk_multi_scg_ra_utg_coverage", "oatk_multi_scg_ra_arc_coverage", "oatk_scg_multiplex_plan", "oatk_multi_scg_multiplex_plan",
-                "oatk_triplet_table_free", "oatk_multi_read_error_correction_fo"]
+                "oatk_triplet_table_free", "oatk_multi_read_error_correction_fo", "oatk_bgzf_index", "oatk_host_set_device_inflate", "oatk_host_inflate_counts"]
 
 
 def load_host():
@@ -91,7 +92,13 @@ def load_host():
     H.oatk_triplet_table_free.restype = None
     H.oatk_triplet_table_free.argtypes = [C.POINTER(TripletTable)]
     H.oatk_host_debug_window.argtypes = [C.c_uint64]
+    H.oatk_bgzf_index.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]      # include/oatk_inflate.h
     return H
+
+
+# oatk_bgzf_member_t (include/oatk_hip_ingest.h) as a numpy record: the member table of oatk_hip_inflate_bgzf / oatk_bgzf_index
+BGZF_MEMBER = [("in_off", "<u8"), ("in_len", "<u4"), ("out_len", "<u4"), ("out_off", "<u8"), ("crc", "<u4"), ("pad", "<u4")]
+INF_OK, INF_STREAM, INF_LENGTH, INF_CRC = range(4)
 
 
 class TripletTable(C.Structure):
@@ -238,6 +245,11 @@ def load():
     L.oatk_hip_ingest.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.oatk_hip_ingest_host.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.oatk_hip_scan_ingested.argtypes = [vp, C.c_uint64, C.c_int, C.c_int]
+    L.oatk_hip_ingest_text_buffer.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
+    L.oatk_hip_inflate_bgzf.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    L.oatk_hip_inflate_bgzf_host.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    L.oatk_hip_inflate_last_byte.argtypes = [vp]
+    L.oatk_hip_ingest_names.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.oatk_hip_stat.argtypes = [vp, C.POINTER(StatRaw)]
     L.oatk_hip_stat_keys.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64), vp]
     L.oatk_hip_stat_from_keys.argtypes = [vp, vp, vp, C.c_uint64, vp, C.POINTER(StatRaw)]

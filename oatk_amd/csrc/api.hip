@@ -381,6 +381,7 @@ struct oatk_hip_ctx {
     struct EcState *ec = nullptr;   // error-correction buffers (api_ec.inc)
     struct ConsState *cons = nullptr;   // consensus buffers (api_cons.inc)
     struct IngState *ing = nullptr;     // record scan buffers (api_ingest.inc)
+    struct InfState *inf = nullptr;     // BGZF inflater buffers (api_inflate.inc)
     struct StatState *stat = nullptr;   // scan statistics buffers (api_stat.inc)
     struct AgState *ag = nullptr;       // assembly graph buffers (api_graph.inc)
     struct OvlState *ovl = nullptr;     // pair-distance tables (api_ovl.inc)
@@ -444,6 +445,7 @@ static void t_collect(oatk_hip_ctx *ctx, int first, int last)
 #include "api_ovl.inc"
 #include "api_align.inc"
 #include "api_ingest.inc"
+#include "api_inflate.inc"
 #include "api_stat.inc"
 #include "api_multi.inc"
 #include "api_multi_tail.inc"
@@ -505,6 +507,7 @@ void oatk_hip_destroy(oatk_hip_ctx *ctx)
     ec_state_free(ctx);
     cons_state_free(ctx);
     ing_state_free(ctx);
+    inf_state_free(ctx);
     stat_state_free(ctx);
     ag_state_free(ctx);
     ovl_state_free(ctx);

@@ -28,6 +28,7 @@
 #include <zlib.h>
 
 #include "oatk_hip.h"
+#include "oatk_inflate.h"
 #include "host_internal.h"
 
 #define GZ_MAX_THREADS 64
@@ -198,28 +199,79 @@ uint64_t oatk_gzsrc_size_in(const oatk_gzsrc_t *g) { return g->size; }
 int oatk_gzsrc_kind(const oatk_gzsrc_t *g) { return g->gzf? 3 : (g->bgzf? 2 : 1); }
 uint64_t oatk_gzsrc_members_on_many_threads(const oatk_gzsrc_t *g) { return g->n_par_opened; }
 
+/* The BGZF member at p, if one is there whole and its text fits what is left of `cap` behind `out` bytes: 1 and *B filled (its text goes to out).  0: the bytes at p
+ * are no BGZF member (the end of the file, a plain gzip member, a cut one, a member not of bgzip's making) or the next member does not fit.  The ONE reading of a
+ * member's header and trailer: bgzf_read below lists with it what its pool inflates, oatk_bgzf_index what the device inflates. */
+static int bgzf_member_at(const uint8_t *map, uint64_t size, uint64_t p, uint64_t out, uint64_t cap, bg_block_t *B)
+{
+    uint32_t bsize = 0;
+    if (p >= size) return 0;
+    const uint32_t hl = gzs_header(map + p, size - p, &bsize);
+    if (!hl || !bsize || p + bsize > size || bsize < hl + 8) return 0;
+    uint32_t isize;
+    memcpy(&isize, map + p + bsize - 4, 4);
+    if (isize > 0x10000) return 0;                   /* not what bgzip writes */
+    if (out + isize > cap) return 0;
+    B->in_off = p, B->in_len = bsize, B->hdr_len = hl, B->out_len = isize, B->out_off = out;
+    return 1;
+}
+
+/* the member table of the BGZF members from map[p0] on, for the device inflater: at most member_cap members, text_cap bytes of text and comp_cap compressed bytes;
+ * in_off is relative to p0 */
+static uint64_t bgzf_list(const uint8_t *map, uint64_t size, uint64_t p0, uint64_t text_cap, uint64_t comp_cap, uint64_t member_cap, oatk_bgzf_member_t *members,
+                          uint64_t *text_bytes, uint64_t *comp_bytes)
+{
+    uint64_t out = 0, p = p0, n = 0;
+    bg_block_t B;
+    while (n < member_cap && bgzf_member_at(map, size, p, out, text_cap, &B) && p + B.in_len - p0 <= comp_cap) {
+        oatk_bgzf_member_t *M = &members[n++];
+        M->in_off = B.in_off - p0 + B.hdr_len, M->in_len = B.in_len - B.hdr_len - 8, M->out_len = B.out_len, M->out_off = B.out_off, M->pad = 0;
+        memcpy(&M->crc, map + B.in_off + B.in_len - 8, 4);
+        out += B.out_len, p += B.in_len;
+    }
+    if (text_bytes) *text_bytes = out;
+    if (comp_bytes) *comp_bytes = p - p0;
+    return n;
+}
+
+/* include/oatk_inflate.h */
+int oatk_bgzf_index(const uint8_t *buf, uint64_t n_bytes, uint64_t text_cap, uint64_t member_cap, oatk_bgzf_member_t *members, uint64_t *n_members,
+                    uint64_t *text_bytes, uint64_t *comp_bytes)
+{
+    if ((!buf && n_bytes) || (!members && member_cap)) return OATK_E_ARG;
+    const uint64_t n = bgzf_list(buf, n_bytes, 0, text_cap, ~(uint64_t) 0, member_cap, members, text_bytes, comp_bytes);
+    if (n_members) *n_members = n;
+    return OATK_OK;
+}
+
+/* For a reader that inflates on the device (host/ingest_host.c): the BGZF members at the read position that oatk_gzsrc_read would inflate next into `text_cap` bytes,
+ * listed and not inflated; *span = their compressed bytes.  0: the read position is inside a member, at the end, or at something that is no BGZF member -- read on
+ * with oatk_gzsrc_read.  The position moves only with oatk_gzsrc_bgzf_skip, once the members' text is in place; without it oatk_gzsrc_read inflates the same members. */
+uint64_t oatk_gzsrc_bgzf_peek(oatk_gzsrc_t *g, uint64_t text_cap, uint64_t comp_cap, uint64_t member_cap, oatk_bgzf_member_t *members, uint64_t *text_bytes,
+                              uint64_t *comp_bytes, const uint8_t **span)
+{
+    if (!g || g->gzf || g->failed || g->eof || g->in_member || !g->map || g->pos >= g->size) return 0;
+    *span = g->map + g->pos;
+    return bgzf_list(g->map, g->size, g->pos, text_cap, comp_cap, member_cap, members, text_bytes, comp_bytes);
+}
+
+void oatk_gzsrc_bgzf_skip(oatk_gzsrc_t *g, uint64_t comp_bytes) { g->pos += comp_bytes; }
+
 /* the BGZF members from pos on that fit `cap` bytes of text, inflated on the pool; 0: the next member is not BGZF (or nothing fits) */
 static int64_t bgzf_read(oatk_gzsrc_t *g, uint8_t *dst, uint64_t cap)
 {
     uint64_t out = 0, p = g->pos;
+    bg_block_t nb1;
     g->n_blk = 0;
-    while (p < g->size) {
-        uint32_t bsize = 0;
-        const uint32_t hl = gzs_header(g->map + p, g->size - p, &bsize);
-        if (!hl || !bsize || p + bsize > g->size || bsize < hl + 8) break;
-        uint32_t isize;
-        memcpy(&isize, g->map + p + bsize - 4, 4);
-        if (isize > 0x10000) break;                  /* not what bgzip writes */
-        if (out + isize > cap) break;
+    while (bgzf_member_at(g->map, g->size, p, out, cap, &nb1)) {
         if (g->n_blk == g->m_blk) {
             g->m_blk = g->m_blk? 2 * g->m_blk : 4096;
             bg_block_t *nb = (bg_block_t *) realloc(g->blk, g->m_blk * sizeof(bg_block_t));
             if (!nb) return -1;
             g->blk = nb;
         }
-        bg_block_t *B = &g->blk[g->n_blk++];
-        B->in_off = p, B->in_len = bsize, B->hdr_len = hl, B->out_len = isize, B->out_off = out;
-        out += isize, p += bsize;
+        g->blk[g->n_blk++] = nb1;
+        out += nb1.out_len, p += nb1.in_len;
     }
     if (g->n_blk == 0) return 0;
     g->dst = dst;
@@ -336,4 +388,20 @@ int64_t oatk_gzsrc_read(oatk_gzsrc_t *g, uint8_t *dst, uint64_t cap)
         out += (uint64_t) n;
     }
     return (int64_t) out;
+}
+
+/* For a reader that inflates on the device: the text oatk_gzsrc_read would deliver, but no further than the end of the member at the read position (or being
+ * decoded).  oatk_gzsrc_read fills its buffer and so stops inside a member nearly every time; this stops at the member's end where it can, and the members behind
+ * it can be listed again (oatk_gzsrc_bgzf_peek).  Same judgement of a damaged file: both go through serial_read. */
+int64_t oatk_gzsrc_read_member(oatk_gzsrc_t *g, uint8_t *dst, uint64_t cap)
+{
+    if (!g || g->failed) return -1;
+    if (g->gzf) return oatk_gzsrc_read(g, dst, cap);
+    if (g->eof || cap == 0) return 0;
+    for (;;) {                                           /* (an empty member -- bgzip's end marker -- delivers nothing and is not the end: on to the next) */
+        if (!g->in_member && g->pos >= g->size) { g->eof = 1; return 0; }
+        const int64_t n = serial_read(g, dst, cap);
+        if (n < 0) { g->failed = 1; return -1; }
+        if (n > 0 || g->eof) return n;
+    }
 }

@@ -7,6 +7,7 @@
 #define OATK_HOST_INTERNAL_H
 
 #include "oatk_hip_racov.h"
+#include "oatk_inflate.h"
 #include "oatk_hip_stat.h"
 #include "oatk_syncasm.h"
 
@@ -62,6 +63,12 @@ uint64_t oatk_gzsrc_size_in(const oatk_gzsrc_t *g);
 uint64_t oatk_gzsrc_members_on_many_threads(const oatk_gzsrc_t *g);      /* (statistics, tests) */
 int oatk_gzsrc_kind(const oatk_gzsrc_t *g);          /* 1 plain member(s), 2 BGZF, 3 not a regular file (zlib's gzread) */
 void oatk_gzsrc_close(oatk_gzsrc_t *g);
+/* the BGZF members at the read position listed for the device inflater, and the position moved past them once their text is in place (gzsrc.c) */
+uint64_t oatk_gzsrc_bgzf_peek(oatk_gzsrc_t *g, uint64_t text_cap, uint64_t comp_cap, uint64_t member_cap, oatk_bgzf_member_t *members, uint64_t *text_bytes,
+                              uint64_t *comp_bytes, const uint8_t **span);
+void oatk_gzsrc_bgzf_skip(oatk_gzsrc_t *g, uint64_t comp_bytes);
+/* oatk_gzsrc_read that stops at the end of the member at hand, so that the members behind it can be listed again */
+int64_t oatk_gzsrc_read_member(oatk_gzsrc_t *g, uint8_t *dst, uint64_t cap);
 /* one member's deflate data inflated on many threads (host/gzpar.c) */
 typedef struct oatk_gzpar oatk_gzpar_t;
 oatk_gzpar_t *oatk_gzpar_open(const uint8_t *deflate, uint64_t n_in, int n_threads);

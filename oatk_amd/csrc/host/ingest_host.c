@@ -289,6 +289,26 @@ static void name_worker(void *arg, int tid, int n_threads)
 static uint64_t g_window = 0;
 void oatk_host_debug_window(uint64_t bytes) { g_window = bytes; }
 
+/* BGZF members of a streamed input inflated on the device (include/oatk_inflate.h): the switch, and what it has done */
+static int g_dev_inflate = -1;                                      /* -1: OATK_DEVICE_INFLATE has not been read yet */
+static uint64_t g_inf_counts[3];
+void oatk_host_set_device_inflate(int on) { __atomic_store_n(&g_dev_inflate, on? 1 : 0, __ATOMIC_RELAXED); }
+void oatk_host_inflate_counts(uint64_t out[3])
+{
+    int i;
+    for (i = 0; i < 3; ++i) out[i] = __atomic_load_n(&g_inf_counts[i], __ATOMIC_RELAXED);
+}
+static int dev_inflate_wanted(void)
+{
+    int v = __atomic_load_n(&g_dev_inflate, __ATOMIC_RELAXED);
+    if (v < 0) {
+        const char *e = getenv("OATK_DEVICE_INFLATE");
+        v = e && e[0] && !(e[0] == '0' && !e[1]);
+        __atomic_store_n(&g_dev_inflate, v, __ATOMIC_RELAXED);
+    }
+    return v;
+}
+
 /* what the stream keeps on one DEVICE: with the reads spread over several handles (include/oatk_multi.h) a window is uploaded to, parsed and scanned on
  * the device of the handle its reads will be assembled in */
 typedef struct {
@@ -318,6 +338,7 @@ typedef struct {
     uint64_t f0[2], f1[2], ftotal;
     int streamed;                  /* the input is pulled through sources (a gzip'ed file among them), window by window; the last window says so */
     int final[2];
+    int dev_win[2];                /* streamed input: the slot's window holds text that was inflated on the device -- the host has no whole copy of it */
 } stream_t;
 
 /* the handle a window's reads go to: by where the window starts in the input, so the ranks hold contiguous ranges of reads of about equal text */
@@ -467,6 +488,7 @@ typedef struct {
     uint64_t out_seg;              /* text delivered of the current file */
     uint8_t last;
     uint64_t f_before;             /* bytes of the files before the current one */
+    int by_member;                 /* a gzip'ed file is read no further than the end of the member at hand (the device inflates the whole members behind it) */
 } src_t;
 
 static uint64_t src_fpos(const src_t *q)
@@ -483,7 +505,7 @@ static int64_t src_read(src_t *q, uint8_t *dst, uint64_t cap)
         const seg_t *s = &q->seg[q->cur];
         int64_t n = 0;
         if (s->gz) {
-            n = oatk_gzsrc_read(s->gz, dst, cap);
+            n = q->by_member? oatk_gzsrc_read_member(s->gz, dst, cap) : oatk_gzsrc_read(s->gz, dst, cap);
             if (n < 0) { fprintf(stderr, "[E::%s] input file %d is damaged (gzip stream)\n", __func__, q->cur + 1); return -1; }
         } else if (s->fd >= 0) {
             const uint64_t left = s->size - q->in_seg, want = left < cap? left : cap;
@@ -508,6 +530,36 @@ static int64_t src_read(src_t *q, uint8_t *dst, uint64_t cap)
     return 0;
 }
 
+/* The BGZF members at the read position of the current file inflated ON THE DEVICE, into d_dst (room bytes): their compressed bytes are staged in h_stage (page-locked,
+ * room bytes: the listing stops at whichever fills first, so a run of stored members, a little larger compressed than inflated, is cut earlier), uploaded and inflated
+ * on the uploader's handle.  Returns the bytes of text now in place; 0 when there is nothing for the device here and nothing has moved:
+ *   - the read position is inside a member, at a plain one or at members without text (bgzip's end marker): the host path reads on from the same position;
+ *   - *waits: a BGZF member with text comes next that the room does not hold (its text, or its compressed bytes in the staging room): a window that holds text
+ *     already ends here, so that the member is the device's in the next one, and is not cut by the window's end and left to the host with all that follows;
+ *   - *redo: the device refused a member: the host path inflates the text of the members that were listed, *redo bytes, and it alone judges the file. */
+#define INF_MEMBER_CAP 65536
+static int64_t src_inflate_device(src_t *q, oatk_hip_ctx *up, uint8_t *h_stage, uint8_t *d_dst, uint64_t room, oatk_bgzf_member_t *members, uint64_t *redo, int *waits, int *rc)
+{
+    const seg_t *s = &q->seg[q->cur];
+    uint64_t text = 0, comp = 0, n_bad = 0;
+    const uint8_t *span = 0;
+    const uint64_t n = oatk_gzsrc_bgzf_peek(s->gz, room, room, INF_MEMBER_CAP, members, &text, &comp, &span);
+    *redo = 0, *waits = 0;
+    if (n == 0 || text == 0) {                                       /* (members without text are the host's: nothing to upload for them) */
+        uint64_t t1 = 0, c1 = 0;
+        if (n == 0 && oatk_gzsrc_bgzf_peek(s->gz, 0x10000, ~(uint64_t) 0, 1, members, &t1, &c1, &span) == 1 && t1) *waits = 1;
+        return 0;
+    }
+    memcpy(h_stage, span, (size_t) comp);
+    *rc = oatk_hip_inflate_bgzf_host(up, h_stage, comp, members, n, d_dst, text, &n_bad, 0);
+    if (*rc) return 0;
+    if (n_bad) { __atomic_fetch_add(&g_inf_counts[1], n, __ATOMIC_RELAXED); *redo = text; return 0; }
+    oatk_gzsrc_bgzf_skip(s->gz, comp);
+    q->last = (uint8_t) oatk_hip_inflate_last_byte(up), q->out_seg += text;
+    __atomic_fetch_add(&g_inf_counts[0], n, __ATOMIC_RELAXED);
+    return (int64_t) text;
+}
+
 static void *uploader_src(void *arg)
 {
     stream_t *st = (stream_t *) arg;
@@ -515,8 +567,11 @@ static void *uploader_src(void *arg)
     src_t q;
     uint64_t g0 = 0, w;
     int rc = OATK_OK, final = 0;
+    const int dev_inflate = dev_inflate_wanted();
+    oatk_bgzf_member_t *members = dev_inflate? (oatk_bgzf_member_t *) malloc(sizeof(oatk_bgzf_member_t) * INF_MEMBER_CAP) : 0;
     memset(&q, 0, sizeof(q));
     q.seg = st->seg, q.n_seg = st->n_seg, q.last = '\n';
+    if (dev_inflate && !members) rc = OATK_E_NOMEM;
     for (w = 0; !rc && !final; ++w) {
         const int s = (int) (w & 1);
         const uint64_t f0 = src_fpos(&q);
@@ -532,9 +587,20 @@ static void *uploader_src(void *arg)
         pthread_mutex_unlock(&st->mu);
         if (stop) break;
         uint64_t filled = 0;
+        int dev_win = 0;
         while (!rc && filled < st->win) {                            /* a piece is on the bus while the next one is inflated / read */
             const uint64_t want = st->win - filled < chunk? st->win - filled : chunk;
-            const int64_t n = src_read(&q, D->h_win[s] + filled, want);
+            uint64_t redo = 0;
+            int waits = 0;
+            if (dev_inflate && q.cur < q.n_seg && q.seg[q.cur].gz) {  /* whole BGZF members: the device's (the window's unused part of the host's copy is the staging room) */
+                const int64_t nd = src_inflate_device(&q, D->up, D->h_win[s] + filled, D->d_win[s] + filled, want, members, &redo, &waits, &rc);
+                if (rc) break;
+                if (nd > 0) { filled += (uint64_t) nd, dev_win = 1; continue; }
+                if (waits && filled) break;                          /* (a short window; the last one is not the only one that may be) */
+                q.by_member = !redo;                                 /* the host: the listed members again, or no further than the end of the member at hand */
+            }
+            const int64_t n = src_read(&q, D->h_win[s] + filled, redo? redo : want);
+            q.by_member = 0;
             if (n < 0) { rc = OATK_E_ARG; break; }
             if (n == 0) { final = 1; break; }
             rc = oatk_hip_h2d_async(D->up, D->d_win[s] + filled, D->h_win[s] + filled, (uint64_t) n);
@@ -543,11 +609,13 @@ static void *uploader_src(void *arg)
         if (!rc) rc = oatk_hip_sync(D->up);
         pthread_mutex_lock(&st->mu);
         if (rc) st->failed = rc;
-        else st->state[s] = 1, st->g0[s] = g0, st->g1[s] = g0 + filled, st->f0[s] = f0, st->f1[s] = src_fpos(&q), st->final[s] = final;
+        else st->state[s] = 1, st->g0[s] = g0, st->g1[s] = g0 + filled, st->f0[s] = f0, st->f1[s] = src_fpos(&q), st->final[s] = final, st->dev_win[s] = dev_win;
         pthread_cond_broadcast(&st->cv);
         pthread_mutex_unlock(&st->mu);
+        if (dev_win) __atomic_fetch_add(&g_inf_counts[2], 1, __ATOMIC_RELAXED);
         g0 += filled;
     }
+    free(members);
     if (rc) {
         pthread_mutex_lock(&st->mu);
         st->failed = rc;
@@ -572,6 +640,18 @@ static void hname_worker(void *arg, int tid, int n_threads)
         while (e < j->len && j->text[e] != ' ' && j->text[e] != '\t' && j->text[e] != '\n' && j->text[e] != '\r') ++e;
         j->names[i] = oatk_host_name_dup(j->text + p, (size_t) (e - p), &bump, j->owner);
     }
+}
+
+/* ... and out of names the device has cut and packed (oatk_hip_ingest_names): a window inflated there has no copy on the host */
+typedef struct { const uint8_t *packed; const uint64_t *off; uint64_t n; char **names; const void *owner; } pname_job_t;
+
+static void pname_worker(void *arg, int tid, int n_threads)
+{
+    pname_job_t *j = (pname_job_t *) arg;
+    const uint64_t a = j->n * (uint64_t) tid / (uint64_t) n_threads, b = j->n * (uint64_t) (tid + 1) / (uint64_t) n_threads;
+    oatk_name_bump_t bump = {0, 0};
+    uint64_t i;
+    for (i = a; i < b; ++i) j->names[i] = oatk_host_name_dup(j->packed + j->off[i], (size_t) (j->off[i + 1] - j->off[i]), &bump, j->owner);
 }
 
 /* the first character of the text that is not white space decides the format, as kseq and oatk_hip_ingest(AUTO) decide it */
@@ -668,6 +748,7 @@ static int sr_read_stream(oatk_hip_ctx **ctxs, int n_ctx, uint64_t *first, oatk_
         rc = st.failed;
         const uint64_t g0 = st.g0[s], g1 = st.g1[s], wf0 = st.f0[s], wf1 = st.f1[s];
         const int final = st.final[s];
+        const int dev_win = st.dev_win[s];                          /* text inflated on the device: what the host's copy is used for below comes from the device */
         pthread_mutex_unlock(&st.mu);
         if (rc) break;
         t_wait += now_s() - t0, t0 = now_s();
@@ -693,7 +774,20 @@ static int sr_read_stream(oatk_hip_ctx **ctxs, int n_ctx, uint64_t *first, oatk_
         const uint64_t len = carry + (g1 - g0);
         uint64_t n = 0, used = 0, b = 0;
         const uint8_t *h_text = 0;
-        if (streamed) {                                              /* the host's copy of the same text: the carried tail in front of the window */
+        if (streamed && dev_win) {
+            uint64_t at = 0;                                         /* the format: the few bytes the sniff needs, fetched */
+            while (fmt < 0 && at < len && !rc) {
+                uint8_t head[4096];
+                const uint64_t m = len - at < sizeof(head)? len - at : sizeof(head);
+                uint64_t i2;
+                rc = oatk_hip_d2h(D->piece[s], head, d_text + at, m);
+                for (i2 = 0; !rc && i2 < m && (head[i2] == '\n' || head[i2] == '\r' || head[i2] == ' ' || head[i2] == '\t'); ++i2) {}
+                if (!rc && i2 < m) fmt = head[i2] == '@'? OATK_FMT_FASTQ : OATK_FMT_FASTA;
+                at += m;
+            }
+            if (rc) break;
+            if (fmt < 0 && final) fmt = OATK_FMT_FASTA;
+        } else if (streamed) {                                       /* the host's copy of the same text: the carried tail in front of the window */
             if (carry) memcpy(D->h_win[s] - carry, h_carry, carry);
             h_text = D->h_win[s] - carry;
             if (fmt < 0) {
@@ -701,6 +795,8 @@ static int sr_read_stream(oatk_hip_ctx **ctxs, int n_ctx, uint64_t *first, oatk_
                 for (i2 = 0; i2 < len && (h_text[i2] == '\n' || h_text[i2] == '\r' || h_text[i2] == ' ' || h_text[i2] == '\t'); ++i2) {}
                 if (i2 < len || final) fmt = i2 < len && h_text[i2] == '@'? OATK_FMT_FASTQ : OATK_FMT_FASTA;
             }
+        }
+        if (streamed) {
             if (len == 0 || fmt < 0) {                               /* an empty last window, or nothing but white space so far (dropped, as kseq skips it) */
                 pthread_mutex_lock(&st.mu);
                 st.state[s] = 0;
@@ -739,7 +835,19 @@ static int sr_read_stream(oatk_hip_ctx **ctxs, int n_ctx, uint64_t *first, oatk_
             if (rc) break;
         }
         if (streamed) {                                             /* before the slot goes back: the names and the carried tail, from the host's copy */
-            if (sr_db && n) {
+            if (sr_db && n && dev_win) {                             /* cut and packed on the device, one copy */
+                const uint8_t *packed = 0;
+                const uint64_t *poff = 0;
+                uint64_t nn = 0;
+                early_names = (char **) calloc(n, sizeof(char *));
+                if (!early_names) { rc = OATK_E_NOMEM; break; }
+                rc = oatk_hip_ingest_names(D->piece[s], d_text, len, &packed, &poff, &nn);
+                if (!rc && nn != n) rc = OATK_E_STATE;
+                if (rc) break;
+                pname_job_t pj = {packed, poff, n, early_names, sr_db};
+                early_n = n;
+                oatk_par_run(pname_worker, &pj);
+            } else if (sr_db && n) {
                 const void *dh = 0;
                 uint64_t bb = 0;
                 hdr = (uint64_t *) malloc(8 * n), early_names = (char **) calloc(n, sizeof(char *));
@@ -752,7 +860,10 @@ static int sr_read_stream(oatk_hip_ctx **ctxs, int n_ctx, uint64_t *first, oatk_
                 oatk_par_run(hname_worker, &hj);
                 free(hdr), hdr = 0;
             }
-            if (!final && !capped && next_carry) memcpy(h_carry, h_text + used, next_carry);
+            if (!final && !capped && next_carry) {
+                if (dev_win) { rc = oatk_hip_d2h(D->piece[s], h_carry, d_text + used, next_carry); if (rc) break; }
+                else memcpy(h_carry, h_text + used, next_carry);
+            }
         }
         pthread_mutex_lock(&st.mu);                                 /* the window's text is spent: the uploader may have the slot back */
         st.state[s] = 0;
@@ -860,7 +971,8 @@ done:
         if (na) sr_db->a = na, sr_db->m = sr_db->n;
     }
     if (log) fprintf(stderr, "[M::oatk_sr_read_files] %.2f GB of text in %lu windows, %lu reads into %d handle(s): %.3f s (waiting for the uploader %.3f, record + syncmer scan %.3f, "
-                             "room for the batch %.3f, names %.3f, structs %.3f, append %.3f)\n", (double) text_done / 1e9, (unsigned long) w, (unsigned long) n_done, n_ctx, now_s() - t_begin, t_wait, t_dev, t_room, t_names, t_fill, t_app);
+                             "room for the batch %.3f, names %.3f, structs %.3f, append %.3f); inflated on the device so far: %lu members, %lu redone on the host, %lu windows\n", (double) text_done / 1e9, (unsigned long) w, (unsigned long) n_done, n_ctx, now_s() - t_begin, t_wait, t_dev, t_room, t_names, t_fill, t_app,
+                             (unsigned long) __atomic_load_n(&g_inf_counts[0], __ATOMIC_RELAXED), (unsigned long) __atomic_load_n(&g_inf_counts[1], __ATOMIC_RELAXED), (unsigned long) __atomic_load_n(&g_inf_counts[2], __ATOMIC_RELAXED));
     return rc;
 }
 

@@ -34,6 +34,44 @@ _DTYPES = {
 }
 
 
+_host = None
+
+
+def bgzf_index(data, text_cap=None, member_cap=None):
+    """oatk_bgzf_index (include/oatk_inflate.h): the BGZF members at the start of `data` (bytes / uint8 array), found header by header, nothing inflated.
+    Returns (members, text_bytes, comp_bytes): a record array of _lib.BGZF_MEMBER, the text the members hold and the compressed bytes they cover."""
+    global _host
+    if _host is None:
+        _host = _lib.load_host()
+    d = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+    cap = d.size // 26 + 1 if member_cap is None else int(member_cap)       # (no member is shorter than its 18-byte header and 8-byte trailer)
+    mem = np.zeros(max(cap, 1), dtype=_lib.BGZF_MEMBER)
+    n, tb, cb = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    rc = _host.oatk_bgzf_index(d.ctypes.data if d.size else None, d.size, (1 << 62) if text_cap is None else int(text_cap), cap, mem.ctypes.data,
+                               C.byref(n), C.byref(tb), C.byref(cb))
+    if rc != _lib.OK:
+        raise _lib.OatkHipError("oatk_bgzf_index failed (code %d)" % rc)
+    return mem[:int(n.value)].copy(), int(tb.value), int(cb.value)
+
+
+def set_device_inflate(on):
+    """oatk_host_set_device_inflate (include/oatk_inflate.h): the streamed reader inflates BGZF members on the device"""
+    global _host
+    if _host is None:
+        _host = _lib.load_host()
+    _host.oatk_host_set_device_inflate(1 if on else 0)
+
+
+def inflate_counts():
+    """oatk_host_inflate_counts: (members inflated on the device, members redone on the host, windows with device-inflated text) since the process began"""
+    global _host
+    if _host is None:
+        _host = _lib.load_host()
+    out = (C.c_uint64 * 3)()
+    _host.oatk_host_inflate_counts(out)
+    return tuple(int(x) for x in out)
+
+
 def pack_reads(reads):
     """list of bytes -> packed read stream (seq uint8, off uint64[n], len uint32[n]); reads start on 64-byte boundaries"""
     n = len(reads)
@@ -336,6 +374,46 @@ class HipSyncasm:
         n, used = C.c_uint64(), C.c_uint64()
         self._check(self.L.oatk_hip_ingest(self.h, d_text, n_bytes, fmt, 1 if final else 0, C.byref(n), C.byref(used)), "oatk_hip_ingest")
         return int(n.value), int(used.value)
+
+    # ---- BGZF members inflated on the device (include/oatk_hip_ingest.h: oatk_hip_inflate_bgzf) ----
+    def inflate_members(self, comp, members, d_text, text_cap):
+        """comp: the compressed bytes (host); members: a record array of _lib.BGZF_MEMBER; d_text: device pointer (int) with room for text_cap bytes.
+        Returns (n_bad, status uint8[n])"""
+        c = np.frombuffer(comp, dtype=np.uint8) if isinstance(comp, (bytes, bytearray, memoryview)) else np.ascontiguousarray(comp, dtype=np.uint8)
+        m = np.ascontiguousarray(members, dtype=_lib.BGZF_MEMBER)
+        st = np.zeros(max(len(m), 1), np.uint8)
+        bad = C.c_uint64()
+        self._check(self.L.oatk_hip_inflate_bgzf_host(self.h, c.ctypes.data if c.size else None, c.size, m.ctypes.data if len(m) else None, len(m),
+                                                      d_text, text_cap, C.byref(bad), st.ctypes.data), "oatk_hip_inflate_bgzf_host")
+        return int(bad.value), st[:len(m)]
+
+    def inflate_bgzf(self, data, status=False):
+        """data: the bytes of a BGZF file (or of whole members of one).  Returns the text as a uint8 array; it also stays resident in the context's text buffer
+        (self.inflated = (device pointer, bytes), e.g. for ingest_device).  A bad member raises OatkHipError naming the first one -- unless status=True, which
+        returns (text, status) and leaves the judgement to the caller (the range of a member with status 1 or 2 holds nothing meaningful)."""
+        members, n_text, n_comp = bgzf_index(data)
+        if n_comp != len(data):
+            raise _lib.OatkHipError("inflate_bgzf: the bytes at offset %d are not a whole BGZF member" % n_comp)
+        d_text = C.c_void_p()
+        self._check(self.L.oatk_hip_ingest_text_buffer(self.h, n_text, C.byref(d_text)), "oatk_hip_ingest_text_buffer")
+        n_bad, st = self.inflate_members(data, members, d_text.value, n_text)
+        self.inflated = (d_text.value, n_text)
+        if n_bad and not status:
+            i = int(np.flatnonzero(st)[0])
+            raise _lib.OatkHipError("inflate_bgzf: member %d (compressed offset %d, text offset %d) is bad: %s" % (
+                i, int(members["in_off"][i]), int(members["out_off"][i]), ["", "not a DEFLATE stream", "its length is not its trailer's", "its CRC-32 is not its trailer's"][int(st[i])]))
+        text = np.empty(n_text, np.uint8)
+        if n_text:
+            self._check(self.L.oatk_hip_d2h(self.h, text.ctypes.data, d_text.value, n_text), "oatk_hip_d2h")
+        return (text, st) if status else text
+
+    def ingest_names(self, d_text, n_bytes):
+        """the names of the records the latest ingest found in the text at d_text (the text it was given), cut on the device (oatk_hip_ingest_names)"""
+        pk, po, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self._check(self.L.oatk_hip_ingest_names(self.h, d_text, n_bytes, C.byref(pk), C.byref(po), C.byref(n)), "oatk_hip_ingest_names")
+        off = np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_uint64)), (n.value + 1,)).copy()
+        packed = C.string_at(pk.value, int(off[-1])) if off[-1] else b""
+        return [packed[int(a):int(b)] for a, b in zip(off[:-1], off[1:])]
 
     def scan_ingested(self, k, s, sid0=0):
         self._check(self.L.oatk_hip_scan_ingested(self.h, sid0, k, s), "oatk_hip_scan_ingested")

@@ -1,0 +1,153 @@
+"""BGZF members made by hand for the inflater's tests (tests/test_host_inflate_core_fuzz.py on the CPU, tests/test_gpu_inflate.py on the device): members of every
+shape from raw deflate streams of Python's zlib, and streams zlib never writes, bit by bit -- a first token that is a match, a distance one beyond the produced
+bytes, over-subscribed code lengths, block type 3, LEN != ~NLEN, and code-length repeat codes that run from the literal/length lengths into the distance lengths."""
+import struct
+import zlib
+
+import numpy as np
+
+
+def raw_deflate(text, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, flush_at=()):
+    """a raw deflate stream; flush_at: (position, flush mode) pairs that end a block inside the member"""
+    c = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
+    out, at = b"", 0
+    for pos, mode in flush_at:
+        out += c.compress(text[at:pos]) + c.flush(mode)
+        at = pos
+    return out + c.compress(text[at:]) + c.flush()
+
+
+def member(stream, text=None, crc=None, isize=None):
+    """a BGZF member around a raw deflate stream: bgzip's 18-byte header (BC field), the stream, CRC-32 and ISIZE"""
+    if crc is None:
+        crc = zlib.crc32(text)
+    if isize is None:
+        isize = len(text)
+    bsize = 18 + len(stream) + 8
+    assert bsize <= 65536, "not a BGZF member: %d bytes" % bsize
+    return b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", bsize - 1) + stream + struct.pack("<II", crc & 0xFFFFFFFF, isize)
+
+
+EOF_MARKER = member(b"\x03\x00", b"")
+assert len(EOF_MARKER) == 28
+
+
+def stored(text):
+    return raw_deflate(text, 0)
+
+
+class Bits:
+    """a deflate stream bit by bit: values LSB first, Huffman codes MSB first (RFC 1951 3.1.1)"""
+
+    def __init__(self):
+        self.v, self.n = 0, 0
+
+    def put(self, value, nbits):
+        self.v |= value << self.n
+        self.n += nbits
+        return self
+
+    def code(self, code, nbits):
+        for i in range(nbits - 1, -1, -1):
+            self.put((code >> i) & 1, 1)
+        return self
+
+    def align(self):
+        self.n = (self.n + 7) // 8 * 8
+        return self
+
+    def bytes(self):
+        return self.v.to_bytes((self.n + 7) // 8, "little")
+
+
+def canonical(lens):
+    """{symbol: (code, length)} of the canonical Huffman code with these lengths (RFC 1951 3.2.2)"""
+    out, code = {}, 0
+    for ln in range(1, 16):
+        for s in sorted(k for k, v in lens.items() if v == ln):
+            out[s] = (code, ln)
+            code += 1
+        code <<= 1
+    return out
+
+
+def _fixed_lit(b, sym):
+    if sym < 144:
+        return b.code(0x30 + sym, 8)
+    if sym < 256:
+        return b.code(0x190 + sym - 144, 9)
+    if sym < 280:
+        return b.code(sym - 256, 7)
+    return b.code(0xC0 + sym - 280, 8)
+
+
+def first_token_is_a_match():
+    """a fixed block whose first token is (length 3, distance 1): there is nothing to copy from"""
+    b = Bits().put(1, 1).put(1, 2)
+    _fixed_lit(b, 257).code(0, 5)
+    return _fixed_lit(b, 256).bytes()
+
+
+def distance_one_beyond():
+    """literals 'A' 'B', then (length 3, distance 3): one before the member's first byte"""
+    b = Bits().put(1, 1).put(1, 2)
+    _fixed_lit(_fixed_lit(b, 65), 66)
+    _fixed_lit(b, 257).code(2, 5)
+    return _fixed_lit(b, 256).bytes()
+
+
+def oversubscribed():
+    """a dynamic block whose nineteen code-length codes all have length 1"""
+    b = Bits().put(1, 1).put(2, 2).put(0, 5).put(0, 5).put(15, 4)
+    for _ in range(19):
+        b.put(1, 3)
+    return b.put(0, 32).bytes()
+
+
+def block_type_3():
+    return Bits().put(1, 1).put(3, 2).put(0, 13).bytes()
+
+
+def stored_len_mismatch(text=b"hello"):
+    return Bits().put(1, 1).put(0, 2).align().put(len(text), 16).put((~len(text) & 0xFFFF) ^ 0x0100, 16).bytes() + text
+
+
+def repeat_across_the_boundary():
+    """(stream, text): a dynamic block whose code lengths end ... [256] = 3, then repeat code 16 six times over [257] and the first five DISTANCE lengths, then
+    three times more -- zlib's deflate never writes this (it sends the two sets of lengths separately); other compressors do.  zlib's inflate reads it."""
+    ll = {65: 2, 67: 2, 71: 3, 84: 3, 256: 3, 257: 3}
+    dd = {i: 3 for i in range(8)}
+    cl = {0: 3, 2: 3, 3: 2, 16: 3, 17: 3, 18: 2}
+    clc, llc, ddc = canonical(cl), canonical(ll), canonical(dd)
+    b = Bits().put(1, 1).put(2, 2).put(258 - 257, 5).put(8 - 1, 5).put(16 - 4, 4)
+    for s in [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2]:
+        b.put(cl.get(s, 0), 3)
+
+    def sym(s, extra=None):
+        b.code(*clc[s])
+        if extra:
+            b.put(*extra)
+    sym(18, (65 - 11, 7)); sym(2); sym(0); sym(2); sym(17, (0, 3)); sym(3); sym(18, (12 - 11, 7)); sym(3)         # noqa: E702
+    sym(18, (138 - 11, 7)); sym(18, (33 - 11, 7)); sym(3)                                                        # noqa: E702  ... [256]
+    sym(16, (6 - 3, 2)); sym(16, (3 - 3, 2))                                                                     # noqa: E702  [257] and distance lengths 0..4; 5..7
+    for ch in b"ACGTTGCA":
+        b.code(*llc[ch])
+    b.code(*llc[257]).code(*ddc[3])            # length 3, distance 4: "TGC"
+    b.code(*llc[257]).code(*ddc[0])            # length 3, distance 1: "CCC"
+    b.code(*llc[256])
+    stream = b.bytes()
+    text = zlib.decompressobj(-15).decompress(stream)
+    assert text == b"ACGTTGCATGCCCC", text
+    return stream, text
+
+
+def table(members_and_texts):
+    """a file of members laid end to end -> (bytes, record array in the layout of oatk_bgzf_member_t): what oatk_bgzf_index makes of it, computed here"""
+    from oatk_amd import _lib
+    data, rows, out = b"", [], 0
+    for m in members_and_texts:
+        isize = struct.unpack("<I", m[-4:])[0]
+        rows.append((len(data) + 18, len(m) - 26, isize, out, struct.unpack("<I", m[-8:-4])[0], 0))
+        data += m
+        out += isize
+    return data, np.array(rows, dtype=_lib.BGZF_MEMBER)
