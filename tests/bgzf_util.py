@@ -1,6 +1,7 @@
 """BGZF members made by hand for the inflater's tests (tests/test_host_inflate_core_fuzz.py on the CPU, tests/test_gpu_inflate.py on the device): members of every
 shape from raw deflate streams of Python's zlib, and streams zlib never writes, bit by bit -- a first token that is a match, a distance one beyond the produced
 bytes, over-subscribed code lengths, block type 3, LEN != ~NLEN, and code-length repeat codes that run from the literal/length lengths into the distance lengths."""
+import bisect
 import struct
 import zlib
 
@@ -40,11 +41,19 @@ class Bits:
     """a deflate stream bit by bit: values LSB first, Huffman codes MSB first (RFC 1951 3.1.1)"""
 
     def __init__(self):
-        self.v, self.n = 0, 0
+        self.v, self.n, self.parts = 0, 0, []
 
     def put(self, value, nbits):
         self.v |= value << self.n
         self.n += nbits
+        return self.spill() if self.n >= 4096 else self
+
+    def spill(self):
+        """whole bytes leave the integer, so that a long stream costs what it holds and not its square"""
+        k = self.n >> 3
+        self.parts.append((self.v & ((1 << (k << 3)) - 1)).to_bytes(k, "little"))
+        self.v >>= k << 3
+        self.n &= 7
         return self
 
     def code(self, code, nbits):
@@ -57,7 +66,7 @@ class Bits:
         return self
 
     def bytes(self):
-        return self.v.to_bytes((self.n + 7) // 8, "little")
+        return b"".join(self.parts) + self.v.to_bytes((self.n + 7) // 8, "little")
 
 
 def canonical(lens):
@@ -79,6 +88,105 @@ def _fixed_lit(b, sym):
     if sym < 280:
         return b.code(sym - 256, 7)
     return b.code(0xC0 + sym - 280, 8)
+
+
+def _msb_first(code, nbits):
+    return int(format(code, "0%db" % nbits)[::-1], 2)
+
+
+def _fixed_tables():
+    """what a fixed-Huffman block writes for a literal, a length and a distance, each as (bits LSB first, how many): RFC 1951 3.2.5 and 3.2.6"""
+    sym = []
+    for s in range(288):
+        code, n = (0x30 + s, 8) if s < 144 else (0x190 + s - 144, 9) if s < 256 else (s - 256, 7) if s < 280 else (0xC0 + s - 280, 8)
+        sym.append((_msb_first(code, n), n))
+    length = {}
+    for c in range(257, 285):                                   # eight codes without extra bits, then four codes for each number of extra bits from 1 to 5
+        e = 0 if c < 265 else (c - 261) >> 2
+        base = c - 254 if c < 265 else 3 + ((4 + ((c - 261) & 3)) << e)
+        for x in range(1 << e):
+            v, n = sym[c]
+            length[base + x] = (v | x << n, n + e)
+    length[258] = sym[285]                                      # (code 284 with extra 31 would say 258 too; deflate writes 285)
+    assert sorted(length) == list(range(3, 259))
+    dist = []                                                   # per distance code: (first distance, code bits LSB first, extra bits)
+    for c in range(30):
+        e = 0 if c < 4 else (c >> 1) - 1
+        dist.append((c + 1 if c < 4 else 1 + ((2 + (c & 1)) << e), _msb_first(c, 5), e))
+    return sym, length, dist
+
+
+_FIXED_SYM, _FIXED_LEN, _FIXED_DIST = _fixed_tables()
+_FIXED_DIST_FIRST = [f for f, _, _ in _FIXED_DIST]
+
+
+def fixed_block(bits, tokens, final):
+    """a fixed-Huffman block appended to `bits`; tokens: an int is a literal, (length, distance) a match (3..258, 1..32768)"""
+    bits.put(1 if final else 0, 1).put(1, 2)
+    for t in tokens:
+        if isinstance(t, tuple):
+            ln, d = t
+            assert 3 <= ln <= 258 and 1 <= d <= 32768, t
+            bits.put(*_FIXED_LEN[ln])
+            first, code, e = _FIXED_DIST[bisect.bisect_right(_FIXED_DIST_FIRST, d) - 1]
+            bits.put(code | (d - first) << 5, 5 + e)
+        else:
+            bits.put(*_FIXED_SYM[t])
+    bits.put(*_FIXED_SYM[256])
+    return bits
+
+
+def stored_block(bits, data, final):
+    """a stored block appended to `bits`: the header, zeros up to the byte boundary, LEN, ~LEN, the bytes"""
+    assert len(data) <= 65535
+    bits.put(1 if final else 0, 1).put(0, 2).align().put(len(data), 16).put(~len(data) & 0xFFFF, 16).spill()
+    assert bits.n == 0
+    bits.parts.append(bytes(data))
+    return bits
+
+
+def write_blocks(blocks):
+    """[("fixed", tokens) | ("stored", bytes)] -> (raw deflate stream, the bit offset 0..7 at which each block's header starts); the last block is the final one"""
+    b, at = Bits(), []
+    for i, (kind, body) in enumerate(blocks):
+        at.append(b.n & 7)
+        (fixed_block if kind == "fixed" else stored_block)(b, body, i == len(blocks) - 1)
+    return b.bytes(), at
+
+
+def walk_blocks(blocks):
+    """the tokens as the decoder hands them out, one (index, kind, output offset, length, distance) each: kind "lit", "match" or "stored"; index counts tokens, so
+    index % 64 is a token's place in the kernel's batch (an empty stored block is no token)"""
+    i = o = 0
+    for kind, body in blocks:
+        if kind == "stored":
+            if len(body):
+                yield i, "stored", o, len(body), 0
+                i, o = i + 1, o + len(body)
+            continue
+        for t in body:
+            ln, d = t if isinstance(t, tuple) else (1, 0)
+            yield i, "match" if d else "lit", o, ln, d
+            i, o = i + 1, o + ln
+
+
+def lz_model(blocks):
+    """the text of a block list, by the definition of LZ77: one byte at a time, a match reading what was written a moment ago"""
+    out = bytearray()
+    for kind, body in blocks:
+        if kind == "stored":
+            for x in body:
+                out.append(x)
+            continue
+        for t in body:
+            if isinstance(t, tuple):
+                ln, d = t
+                assert d <= len(out), (t, len(out))
+                for _ in range(ln):
+                    out.append(out[-d])
+            else:
+                out.append(t)
+    return bytes(out)
 
 
 def first_token_is_a_match():

@@ -3,7 +3,10 @@ bgzip's header and trailer (tests/bgzf_util.py, tests/gpu_inflate_cases.py), so 
 members with overlapping copies, distance 32768, several blocks in a member, no distance codes, repeat codes across the literal/distance boundary; 1 to 300 members
 in a call; a FASTA file written as BGZF, inflated and parsed where it lies; and a fixed list of damaged members, each among good ones, with the text buffer filled
 with a sentinel beforehand: the bad member gets its status, the good ones their text, and nothing outside the members' own ranges changes.
-(tests/test_host_inflate_core_fuzz.py has put the same streams, and a few thousand damaged ones, to the decoder on the CPU under ASan first.)"""
+(tests/test_host_inflate_core_fuzz.py has put the same streams, and a few thousand damaged ones, to the decoder on the CPU under ASan first.)
+The shapes here are hand-picked: their overlapped copies have distances up to 8 and none of them mixes a stored run with Huffman blocks.  What the kernel alone
+does -- copies at every distance and length, the edges of the 64-token batch, stored runs among tokens, the 16-byte phases, the CRC's pieces, many bad members in
+one call -- is swept in tests/test_gpu_inflate_sweeps.py."""
 import gzip
 import zlib
 

@@ -2,8 +2,8 @@
 stand-alone program (tests/c/inflate_core_fuzz.cpp) and run against zlib: members made with every level and strategy (Z_FIXED, Z_HUFFMAN_ONLY, Z_RLE among them),
 stored members, flushes inside a member, texts of runs, short periods and random ACGT come out as zlib's text; damaged copies (bits flipped, bytes dropped, tails cut,
 wrong lengths) come out as an error or as zlib's bytes, never accepted with other bytes; input and output sit in heap blocks of exactly their sizes, so an access one
-byte outside them is a sanitizer report; every run ends within its bound.  The streams the GPU tests feed the kernel (tests/bgzf_util.py) are put to the core here
-first, the hand-made ones included."""
+byte outside them is a sanitizer report; every run ends within its bound.  The streams the GPU tests feed the kernel (tests/bgzf_util.py, tests/gpu_inflate_cases.py) are
+put to the core here first, the hand-made ones and the sweeps of tests/test_gpu_inflate_sweeps.py included."""
 import os
 import shutil
 import subprocess
@@ -69,10 +69,11 @@ def test_hand_made_streams(fuzzer, tmp_path):
 
 
 def test_members_of_the_gpu_tests_decode_without_a_rejection(fuzzer, tmp_path):
-    """every valid member tests/test_gpu_inflate.py builds is one the core takes: a rejection there would be the decoder's, not the kernel's"""
+    """every valid member tests/test_gpu_inflate.py and tests/test_gpu_inflate_sweeps.py build is one the core takes, with zlib's CRC over what its tokens make:
+    a rejection or a wrong byte there would be the decoder's, not the kernel's.  (All of them: the 527 members of the copy sweep too, 18 MB of text.)"""
     import gpu_inflate_cases as G
-    cases = [(s, len(t)) for _, s, t in G.member_shapes()]
-    got = ask(fuzzer, tmp_path, cases)
-    for (name, s, t), g in zip(G.member_shapes(), got):
+    members = list(G.member_shapes()) + [e for f in G.SWEEP_LISTS for e in f()]
+    got = ask(fuzzer, tmp_path, [(s, len(t)) for _, s, t in members])
+    for (name, s, t), g in zip(members, got):
         assert g[0] == 0 and g[2] == zlib.crc32(t), (name, g)
         assert zlib.decompressobj(-15).decompress(s) == t, name
