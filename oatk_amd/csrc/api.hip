@@ -10,9 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
-#include <execinfo.h>
 #include <sys/mman.h>
-#include <condition_variable>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -20,315 +18,13 @@
 #include <vector>
 
 #include "../../include/oatk_hip.h"
+#include "devmem.hpp"
 #include "common.hpp"
 #include "scan_hpc.hpp"
 #include "scan_syncmer.hpp"
 #include "scan_syncmer_fast.hpp"
 #include "kmer_hash.hpp"
 #include "count.hpp"
-
-namespace {
-
-// OATK_DEBUG_ALLOC_LOG=1: every call into the driver for device memory on stderr, with its size and what it took (development aid)
-static int dev_alloc_log()
-{
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("OATK_DEBUG_ALLOC_LOG"); on = e && e[0] && e[0] != '0'; }
-    return on;
-}
-static double dev_now() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double) t.tv_sec + 1e-9 * (double) t.tv_nsec; }
-
-// ---- Device memory in pieces (oatk_hip_mem_pool, include/oatk_hip.h) ----
-// What the driver does with device memory (tools/ubench/alloc_*.hip, profiles/r08l_alloc_rates.txt): memory nobody has had since the GPU was reset is cleared when it
-// is handed out -- 30 ms per GB INSIDE hipMalloc / hipMemCreate --, memory a process gives back is cleared behind its back at ~33 GB/s, and the next call that wants
-// memory (of any size, from any process) waits until that is done.  A process that takes 50 GB for its batch at once therefore stands still for up to 1.5 s on a
-// fresh GPU, and one that gives a slab back and takes another stands still for the clearing of the first.  With a pool switched on the larger buffers of this process
-// are address ranges backed by 64 MB pieces (hipMemAddressReserve / hipMemCreate / hipMemMap): a buffer grows by mapping more pieces where it is (no copy, no
-// slack for growth), a buffer that is released hands its pieces to the next one (nothing goes back to the driver before the process ends), and a thread of the
-// pool's own takes pieces from the driver AHEAD of the need -- beside the host's work on the reads, which is what a reader that fills structs is bound by.
-constexpr size_t DM_CHUNK = 64ull << 20;          // a piece
-static size_t dm_min()                             // buffers below this stay hipMalloc's (32 MB; OATK_DEBUG_POOL_MIN: tests put small buffers into pieces too)
-{
-    static size_t v = 0;
-    if (!v) { const char *e = getenv("OATK_DEBUG_POOL_MIN"); v = e && atoll(e) > 0? (size_t) atoll(e) : (32ull << 20); }
-    return v;
-}
-struct ChunkPool {
-    int device = -1;
-    bool on = false;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<hipMemGenericAllocationHandle_t> ready;       // pieces nobody has mapped ...
-    std::vector<char> used;                                   // ... and whether a buffer has had them (what the driver hands out is zero, and so is what a buffer gets: vm_grow)
-    size_t created = 0, target = 0;                           // pieces taken from the driver so far; what the thread works towards
-    bool warming = false, stop = false, failed = false;
-    std::thread th;
-    hipMemAllocationProp prop;
-    hipMemAccessDesc acc;
-    double t_wait = 0;                                        // seconds callers stood waiting for a piece
-
-    bool create(hipMemGenericAllocationHandle_t *h)
-    {
-        const double t0 = dev_alloc_log()? dev_now() : 0;
-        const hipError_t e = hipMemCreate(h, DM_CHUNK, &prop, 0);
-        if (dev_alloc_log() && (e != hipSuccess || dev_now() - t0 > 0.01)) fprintf(stderr, "[oatk alloc] %.3f hipMemCreate %zu MB: %.4f s%s\n", dev_now(), DM_CHUNK >> 20, dev_now() - t0, e == hipSuccess? "" : " FAILED");
-        if (e != hipSuccess) (void) hipGetLastError();
-        return e == hipSuccess;
-    }
-    void run()
-    {
-        (void) hipSetDevice(device);
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                if (stop || created >= target) { warming = false; cv.notify_all(); return; }
-            }
-            hipMemGenericAllocationHandle_t h;
-            const bool ok = create(&h);
-            std::unique_lock<std::mutex> lk(mu);
-            if (!ok) { failed = true, warming = false; cv.notify_all(); return; }
-            ready.push_back(h), used.push_back(0), ++created;
-            cv.notify_all();
-        }
-    }
-    void warm(size_t bytes)
-    {
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess && bytes > fr / 10 * 7) bytes = fr / 10 * 7;        // (never more than most of what is free now)
-        std::unique_lock<std::mutex> lk(mu);
-        const size_t want = created + bytes / DM_CHUNK;                        // on top of what the process holds already
-        if (want > target) target = want;
-        if (!warming && !failed && created < target) {
-            if (th.joinable()) th.join();
-            warming = true;
-            th = std::thread([this] { run(); });
-        }
-    }
-    bool take(hipMemGenericAllocationHandle_t *h, bool *was_used)
-    {
-        *was_used = false;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            const double t0 = dev_now();
-            for (;;) {
-                if (!ready.empty()) { *h = ready.back(), *was_used = used.back() != 0; ready.pop_back(), used.pop_back(); t_wait += dev_now() - t0; return true; }
-                if (warming && !failed && created < target) { cv.wait(lk); continue; }     // the thread is at it: two callers inside the driver would only take turns
-                break;
-            }
-            t_wait += dev_now() - t0;
-        }
-        if (!create(h)) return false;
-        std::unique_lock<std::mutex> lk(mu);
-        ++created;
-        return true;
-    }
-    void give(hipMemGenericAllocationHandle_t h)
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        ready.push_back(h), used.push_back(1);
-    }
-    // what nobody has mapped goes back to the driver (a hipMalloc failed: the pool must not be the reason)
-    size_t trim()
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        const size_t n = ready.size();
-        for (auto h : ready) (void) hipMemRelease(h);
-        ready.clear(), used.clear();
-        created -= n, target = created;
-        return n;
-    }
-    void end()                                                 // at exit, before the runtime's own handlers: no thread of ours inside the driver when they run
-    {
-        { std::unique_lock<std::mutex> lk(mu); stop = true; cv.notify_all(); }
-        if (th.joinable()) th.join();
-    }
-};
-static ChunkPool *g_pool[64];                                  // by device; made by oatk_hip_mem_pool, never destroyed
-static std::mutex g_pool_mu;
-static void pools_end() { for (ChunkPool *p : g_pool) if (p) p->end(); }
-static ChunkPool *pool_of_current_device()
-{
-    int d = -1;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return nullptr;
-    ChunkPool *p = g_pool[d];
-    return p && p->on? p : nullptr;
-}
-// (development aid) OATK_DEBUG_POOL_SEQ="lo:hi": only the lo-th .. (hi-1)-th decisions of a buffer to live in pieces are taken; the others stay hipMalloc's
-static ChunkPool *pool_for_new_buffer()
-{
-    ChunkPool *p = pool_of_current_device();
-    if (!p) return nullptr;
-    static long lo = -1, hi = -1, seq = 0;
-    if (lo < 0) { const char *e = getenv("OATK_DEBUG_POOL_SEQ"); lo = 0, hi = 1L << 60; if (e) sscanf(e, "%ld:%ld", &lo, &hi); }
-    const long k = seq++;
-    if (dev_alloc_log()) {
-        void *bt[6];
-        const int nb = backtrace(bt, 6);
-        char **sy = backtrace_symbols(bt, nb);
-        fprintf(stderr, "[oatk alloc] decision %ld%s  <- %s <- %s <- %s\n", k, k >= lo && k < hi? "" : " (hipMalloc)", nb > 2? sy[2] : "", nb > 3? sy[3] : "", nb > 4? sy[4] : "");
-        free(sy);
-    }
-    return k >= lo && k < hi? p : nullptr;
-}
-
-static hipError_t dev_malloc(void **p, size_t bytes)
-{
-    const double t0 = dev_alloc_log()? dev_now() : 0;
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {
-        ChunkPool *pl = pool_of_current_device();
-        if (pl && pl->trim()) { (void) hipGetLastError(); e = hipMalloc(p, bytes); }
-    }
-    if (dev_alloc_log()) fprintf(stderr, "[oatk alloc] %.3f hipMalloc %10.3f MB: %.4f s%s\n", dev_now(), (double) bytes / 1e6, dev_now() - t0, e == hipSuccess? "" : " FAILED");
-    {   // OATK_DEBUG_POISON=1 (tests): new memory is 0xA5 all over instead of the driver's zeros -- whatever relies on zeros it did not write shows
-        static int poison = -1;
-        if (poison < 0) { const char *ev = getenv("OATK_DEBUG_POISON"); poison = ev && ev[0] == '1'; }
-        if (poison && e == hipSuccess) { (void) hipMemset(*p, 0xA5, bytes); (void) hipDeviceSynchronize(); }
-    }
-    return e;
-}
-static void dev_free(void *p, size_t bytes)
-{
-    const double t0 = dev_alloc_log()? dev_now() : 0;
-    (void) hipFree(p);
-    if (dev_alloc_log()) fprintf(stderr, "[oatk alloc] %.3f hipFree   %10.3f MB: %.4f s\n", dev_now(), (double) bytes / 1e6, dev_now() - t0);
-}
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    // the form in pieces: p is an address range of `va` bytes, its first ch.size() * DM_CHUNK bytes backed
-    size_t va = 0;
-    ChunkPool *pool = nullptr;
-    bool decided = false;                     // whether this buffer lives in pieces was settled (at its first request of the threshold's size)
-    std::vector<hipMemGenericAllocationHandle_t> ch;
-
-    static size_t up(size_t b) { return (b + DM_CHUNK - 1) / DM_CHUNK * DM_CHUNK; }
-    // an address range of at least `bytes`; what is mapped moves along (no copy).  false: nothing changed
-    bool vm_range(size_t bytes, hipStream_t st)
-    {
-        if (bytes <= va) return true;
-        const size_t nva = up(bytes < (1ull << 30)? 4 * bytes + (256ull << 20) : bytes + bytes / 2 + (2ull << 30));     // room to grow in place
-        void *np = nullptr;
-        { const hipError_t er = hipMemAddressReserve(&np, nva, 2 << 20, nullptr, 0);
-          if (er != hipSuccess) { if (dev_alloc_log()) fprintf(stderr, "[oatk alloc] hipMemAddressReserve of %.1f MB FAILED: %s\n", (double) nva / 1e6, hipGetErrorString(er)); (void) hipGetLastError(); return false; } }
-        if (!ch.empty()) {
-            (void) hipStreamSynchronize(st);
-            (void) hipDeviceSynchronize();
-            for (size_t i = 0; i < ch.size(); ++i) {
-                (void) hipMemUnmap((char *) p + i * DM_CHUNK, DM_CHUNK);
-                if (hipMemMap((char *) np + i * DM_CHUNK, DM_CHUNK, 0, ch[i], 0) != hipSuccess) return false;       // (cannot happen on a range just reserved)
-            }
-            if (hipMemSetAccess(np, ch.size() * DM_CHUNK, &pool->acc, 1) != hipSuccess) return false;
-        }
-        // An address range, once reserved, is never given back while the process lives -- not the one the pieces have just moved out of, not a released buffer's.
-        // With hipMemAddressFree in either place a range reserved LATER (at the same addresses, presumably) showed other contents than were written to it: the
-        // correction's results changed in 8 - 14 of 158 cases of tests/test_gpu_ec.py + levdist + light_graph + overlap run over pieces, every run, and in none with the
-        // ranges kept (ROCm 7.0.2; translations of the old mapping that outlive it is the guess, not looked into further).  Address space is what this costs: a buffer's
-        // range is a few times its size, a process of the CLI has some hundreds of such buffers in its life -- a terabyte of a 47-bit space at the outside.
-        if (dev_alloc_log()) fprintf(stderr, "[oatk alloc] %.3f address range %10.3f MB (%zu pieces moved)\n", dev_now(), (double) nva / 1e6, ch.size());
-        p = np, va = nva;
-        return true;
-    }
-    bool vm_grow(size_t bytes, hipStream_t st)
-    {
-        const size_t want = up(bytes);
-        if (!vm_range(want, st)) return false;
-        const size_t have = ch.size() * DM_CHUNK;
-        const double t0 = dev_alloc_log()? dev_now() : 0;
-        bool any_used = false;
-        while (ch.size() * DM_CHUNK < want) {
-            hipMemGenericAllocationHandle_t h;
-            bool was_used;
-            if (!pool->take(&h, &was_used)) { if (dev_alloc_log()) fprintf(stderr, "[oatk alloc] no piece to be had\n"); break; }
-            { const hipError_t er = hipMemMap((char *) p + ch.size() * DM_CHUNK, DM_CHUNK, 0, h, 0);
-              if (er != hipSuccess) { if (dev_alloc_log()) fprintf(stderr, "[oatk alloc] hipMemMap FAILED: %s\n", hipGetErrorString(er)); (void) hipGetLastError(); pool->give(h); break; } }
-            ch.push_back(h);
-            any_used |= was_used;
-        }
-        const size_t now_b = ch.size() * DM_CHUNK;
-        if (now_b > have) { const hipError_t er = hipMemSetAccess((char *) p + have, now_b - have, &pool->acc, 1);
-                            if (er != hipSuccess) { if (dev_alloc_log()) fprintf(stderr, "[oatk alloc] hipMemSetAccess FAILED: %s\n", hipGetErrorString(er)); (void) hipGetLastError(); return false; } }
-        // memory from hipMalloc is zero, always (the driver clears what it hands out): pieces that served another buffer are made so (5 TB/s: 13 us a piece)
-        // -- and waited for: the buffer's first user may be a kernel on another stream than `st`
-        if (any_used && now_b > have && (hipMemsetAsync((char *) p + have, 0, now_b - have, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) return false;
-        if (dev_alloc_log()) fprintf(stderr, "[oatk alloc] %.3f pieces    %10.3f MB -> %10.3f MB: %.4f s\n", dev_now(), (double) have / 1e6, (double) now_b / 1e6, dev_now() - t0);
-        cap = now_b;
-        return now_b >= want;
-    }
-    bool ensure(size_t bytes, hipStream_t st, bool zero_new = false)
-    {
-        if (bytes <= cap) return true;
-        if (!va && !decided) pool = bytes >= dm_min()? pool_for_new_buffer() : nullptr, decided = bytes >= dm_min();
-        if (pool && p && !va) { (void) hipStreamSynchronize(st); dev_free(p, cap); p = nullptr; cap = 0; }      // (a small hipMalloc'ed buffer that has outgrown the threshold)
-        if (pool) {
-            if (vm_grow(bytes + bytes / 16, st)) {
-                if (zero_new) (void) hipMemsetAsync(p, 0, cap, st);
-                return true;
-            }
-            if (!ch.empty()) return false;          // (out of memory with pieces in place)
-            pool = nullptr, p = nullptr, cap = 0, va = 0;      // no range or no piece to start with: this buffer is hipMalloc's (a range that was reserved stays reserved)
-        }
-        if (p) { (void) hipStreamSynchronize(st); dev_free(p, cap); p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        if (dev_malloc(&p, want) != hipSuccess) { p = nullptr; return false; }
-        cap = want;
-        if (zero_new) (void) hipMemsetAsync(p, 0, want, st);
-        return true;
-    }
-    // grow without losing the first `used` bytes (appending to a resident batch)
-    bool grow_keep(size_t bytes, size_t used, hipStream_t st)
-    {
-        if (bytes <= cap) return true;
-        if (!va && !decided) pool = bytes >= dm_min()? pool_for_new_buffer() : nullptr, decided = bytes >= dm_min();
-        if (pool && p && !va) {                                     // from a hipMalloc'ed buffer to pieces: the one copy of this buffer's life
-            void *old = p;
-            const size_t old_cap = cap;
-            p = nullptr, cap = 0;
-            if (!vm_grow(bytes, st)) { release(); p = old, cap = old_cap, pool = nullptr; }
-            else {
-                if (used && hipMemcpyAsync(p, old, used, hipMemcpyDeviceToDevice, st) != hipSuccess) return false;
-                (void) hipStreamSynchronize(st);
-                dev_free(old, old_cap);
-                return true;
-            }
-        }
-        if (pool) return vm_grow(bytes, st);
-        void *np = nullptr;
-        size_t want = bytes + bytes / 4 + 256;
-        if (dev_malloc(&np, want) != hipSuccess) return false;
-        if (p && used && hipMemcpyAsync(np, p, used, hipMemcpyDeviceToDevice, st) != hipSuccess) { dev_free(np, want); return false; }
-        (void) hipStreamSynchronize(st);
-        if (p) dev_free(p, cap);
-        p = np, cap = want;
-        return true;
-    }
-    // room for `bytes` LATER: in pieces that is an address range and nothing else (the pieces come as the buffer fills); otherwise the memory itself, now
-    bool reserve(size_t bytes, size_t used, hipStream_t st)
-    {
-        if (bytes <= cap) return true;
-        if (!va && !p && !decided) pool = bytes >= dm_min()? pool_for_new_buffer() : nullptr, decided = bytes >= dm_min();
-        if (pool && (va || !p)) return vm_range(up(bytes), st);
-        return grow_keep(bytes, used, st);
-    }
-    void release()
-    {
-        if (va) {
-            (void) hipDeviceSynchronize();
-            for (size_t i = 0; i < ch.size(); ++i) { (void) hipMemUnmap((char *) p + i * DM_CHUNK, DM_CHUNK); pool->give(ch[i]); }
-            ch.clear();
-            // (the address range is NOT given back: see vm_range)
-            if (dev_alloc_log()) fprintf(stderr, "[oatk alloc] %.3f pieces    %10.3f MB back to the pool\n", dev_now(), (double) cap / 1e6);
-            p = nullptr, cap = 0, va = 0, decided = false;
-            return;
-        }
-        if (p) dev_free(p, cap);
-        p = nullptr; cap = 0, decided = false;
-    }
-    template <class T> T *as() const { return (T *) p; }
-};
-
-}  // namespace
 
 struct oatk_hip_ctx {
     int device = 0;
@@ -496,14 +192,6 @@ void oatk_hip_destroy(oatk_hip_ctx *ctx)
     if (!ctx) return;
     (void) hipSetDevice(ctx->device);
     (void) hipStreamSynchronize(ctx->stream);
-    DevBuf *all[] = {&ctx->in_seq, &ctx->in_off, &ctx->in_len, &ctx->hoco_l, &ctx->n_scm, &ctx->n_nn, &ctx->n_lrl, &ctx->ho_rl,
-                     &ctx->hoco_s, &ctx->nbits, &ctx->nn_key, &ctx->lrl_key, &ctx->lrl_val, &ctx->nn_key2, &ctx->lrl_key2,
-                     &ctx->lrl_val2, &ctx->raw_lo, &ctx->raw_smer, &ctx->raw_mpos, &ctx->shard_cnt, &ctx->counters, &ctx->n_scm64,
-                     &ctx->scm_off, &ctx->pos_hash, &ctx->pos_lo, &ctx->pos_smer, &ctx->pos_mpos, &ctx->pos_kid, &ctx->key_hash,
-                     &ctx->key_sorted, &ctx->iota, &ctx->perm, &ctx->head, &ctx->head_idx, &ctx->newclus, &ctx->clus_id, &ctx->kloc, &ctx->smer_sorted, &ctx->slot_rec, &ctx->scm_loc,
-                     &ctx->bad_head, &ctx->tag, &ctx->tmp_perm, &ctx->flags, &ctx->scm_h, &ctx->scm_s, &ctx->scm_cov,
-                     &ctx->scm_occ_off, &ctx->scm_occ, &ctx->tmp};
-    for (DevBuf *b : all) b->release();
     ec_state_free(ctx);
     cons_state_free(ctx);
     ing_state_free(ctx);
@@ -520,7 +208,7 @@ void oatk_hip_destroy(oatk_hip_ctx *ctx)
     }
     staging_free(ctx);
     (void) hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;                   // (the handle's own buffers go here: ~DevBuf)
 }
 
 int oatk_hip_mem_pool(oatk_hip_ctx *ctx, uint64_t warm_bytes)

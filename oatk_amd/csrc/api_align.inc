@@ -21,15 +21,7 @@ struct RaState {
 
 static void ra_state_free(oatk_hip_ctx *ctx)
 {
-    if (!ctx->ra) return;
-    RaState *g = ctx->ra;
-    DevBuf *all[] = {&g->su_off, &g->su_uid, &g->su_pos, &g->utg_n, &g->idx_p, &g->idx_n, &g->arc_w, &g->arc_ln, &g->arc_del, &g->old_ra,
-                     &g->slab, &g->cnt_aln, &g->cnt_frg, &g->skipped, &g->tmp64, &g->aln_off, &g->frg_off, &g->stats, &g->skip_list, &g->big_list,
-                     &g->o_sid, &g->o_off, &g->o_s, &g->o_uid, &g->o_ubeg, &g->o_uend, &g->o_sbeg, &g->o_send,
-                     &g->p_sid, &g->p_off, &g->p_s, &g->p_uid, &g->p_ubeg, &g->p_uend, &g->p_sbeg, &g->p_send, &g->pool_a, &g->pool_f, &g->pool_used};
-    for (DevBuf *b : all) b->release();
-    g->bg0.release(), g->bgH.release(), g->bgF.release();
-    delete g;
+    delete ctx->ra;          // (its buffers free themselves: ~DevBuf)
     ctx->ra = nullptr;
 }
 

@@ -11,11 +11,7 @@ struct ConsState {
 
 static void cons_state_free(oatk_hip_ctx *ctx)
 {
-    if (!ctx->cons) return;
-    ConsState *c = ctx->cons;
-    DevBuf *all[] = {&c->flag, &c->flag64, &c->slot_of, &c->sel, &c->slot, &c->rl, &c->tot, &c->m_seq, &c->first, &c->nch, &c->ch_off};
-    for (DevBuf *b : all) b->release();
-    delete c;
+    delete ctx->cons;          // (its buffers free themselves: ~DevBuf)
     ctx->cons = nullptr;
 }
 

@@ -49,16 +49,6 @@ static void ec_state_free(oatk_hip_ctx *ctx)
 {
     if (!ctx->ec) return;
     EcState *e = ctx->ec;
-    DevBuf *all[] = {&e->idx_p, &e->idx_n, &e->arc_v, &e->arc_w, &e->arc_ls, &e->arc_cov, &e->arc_del, &e->conv, &e->scm_del, &e->err_del,
-                     &e->vtx_hs_off, &e->vtx_mpos, &e->copy_n, &e->seg, &e->keep_all, &e->n_blocks, &e->n_blocks64, &e->blk_off, &e->work, &e->out, &e->path_pool, &e->cursor,
-                     &e->todo, &e->todo2, &e->slabs, &e->big_slabs, &e->os_slabs, &e->hyb_slabs[0], &e->hyb_slabs[1], &e->hyb_slabs[2], &e->hyb_slabs[3], &e->hyb_slabs[4], &e->hyb_slabs[5], &e->hyb_slabs[6], &e->hyb_slabs[7], &e->hyb_slabs[8], &e->hyb_slabs[9], &e->hyb_slabs[10], &e->hyb_slabs[11], &e->hyb_slabs[12], &e->hyb_slabs[13], &e->hyb_slabs[14], &e->hyb_slabs[15], &e->new_n, &e->new_n64, &e->new_off, &e->new_k, &e->new_m, &e->new_s, &e->stats,
-                     &e->live32, &e->live64, &e->live_off, &e->larc, &e->lidx_p, &e->lidx_n, &e->cov, &e->fwd, &e->key_id, &e->key_sorted, &e->val_occ, &e->occ, &e->occ_off, &e->cov64,
-                     &e->g_keys, &e->g_keys2, &e->g_ukeys, &e->g_counts, &e->g_nruns, &e->g_nout, &e->g_nout64, &e->g_outoff, &e->g_akey,
-                     &e->g_aval, &e->g_skey, &e->g_sval, &e->g_comp, &e->g_flags, &e->g_huge, &e->g_dist, &e->g_dist2, &e->g_cnt64, &e->g_runoff, &e->g_runls,
-                     &e->g_big, &e->g_keep, &e->g_other, &e->g_lkeys, &e->g_ldist, &e->g_val2, &e->g_wgt2, &e->g_runcov, &e->g_head, &e->g_hpos, &e->g_iota, &e->g_segk, &e->g_segv,
-                     &e->g_l2g, &e->g_kid, &e->g_gcov, &e->g_gs,
-                     &e->slot_w, &e->slot_w64, &e->slot_off, &e->slots, &e->qend, &e->sblk, &e->clen, &e->cbytes, &e->cbytes64, &e->coff, &e->cseq};
-    for (DevBuf *b : all) b->release();
     for (int i = 0; i < 5; ++i) { if (e->aux[i]) (void) hipStreamDestroy(e->aux[i]); if (e->aux_ev[i]) (void) hipEventDestroy(e->aux_ev[i]); }
     if (e->fork_ev) (void) hipEventDestroy(e->fork_ev);
     delete e;
@@ -193,7 +183,6 @@ static int debug_ed_impl(oatk_hip_ctx *ctx, uint64_t n_jobs, const uint8_t *t_co
     const std::vector<uint32_t> tw = pack(t_codes, t_off, tw_off, n_jobs), qw = pack(q_codes, q_off, qw_off, n_jobs);
     const uint64_t n_steps = step_off[n_jobs];
     DevBuf d_tw, d_qw, d_two, d_qwo, d_tl, d_bw, d_sq, d_so, d_k, d_ko, d_out, d_slab;
-    DevBuf *all[] = {&d_tw, &d_qw, &d_two, &d_qwo, &d_tl, &d_bw, &d_sq, &d_so, &d_k, &d_ko, &d_out, &d_slab};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (kernel_ms) { *kernel_ms = 0.f; (void) hipEventCreate(&ev0); (void) hipEventCreate(&ev1); }
     int32_t max_t = 0;
@@ -251,7 +240,6 @@ static int debug_ed_impl(oatk_hip_ctx *ctx, uint64_t n_jobs, const uint8_t *t_co
     if (ev0 && ev1 && !rc) (void) hipEventElapsedTime(kernel_ms, ev0, ev1);
     if (ev0) (void) hipEventDestroy(ev0);
     if (ev1) (void) hipEventDestroy(ev1);
-    for (DevBuf *b : all) b->release();
     if (rc == OATK_E_NODEV) ctx->err = std::string("oatk_hip_debug_wf_ed: ") + hipGetErrorString(he);
     if (rc == OATK_E_NOMEM) ctx->err = "oatk_hip_debug_wf_ed: hipMalloc failed";
     return rc;
@@ -298,7 +286,6 @@ extern "C" int oatk_hip_debug_tables(oatk_hip_ctx *ctx, uint64_t n_jobs, const u
     };
     const std::vector<uint32_t> tw = pack(t_codes, t_off, tw_off, n_jobs), qw = pack(s_codes, s_off, qw_off, n_jobs);
     DevBuf d_tw, d_qw, d_two, d_qwo, d_tl, d_ql, d_oo, d_out;
-    DevBuf *all[] = {&d_tw, &d_qw, &d_two, &d_qwo, &d_tl, &d_ql, &d_oo, &d_out};
     int rc = OATK_OK;
     hipError_t he = hipSuccess;
     auto up = [&](DevBuf &b, const void *src, size_t bytes) {
@@ -326,7 +313,6 @@ extern "C" int oatk_hip_debug_tables(oatk_hip_ctx *ctx, uint64_t n_jobs, const u
         if (!rc && (he = hipGetLastError()) != hipSuccess) rc = OATK_E_NODEV;
     }
     (void) hipStreamSynchronize(ctx->stream);
-    for (DevBuf *b : all) b->release();
     if (rc == OATK_E_NODEV) ctx->err = std::string("oatk_hip_debug_tables: ") + hipGetErrorString(he);
     if (rc == OATK_E_NOMEM) ctx->err = "oatk_hip_debug_tables: hipMalloc failed";
     return rc;

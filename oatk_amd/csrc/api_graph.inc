@@ -14,13 +14,7 @@ struct AgState {
 
 static void ag_state_free(oatk_hip_ctx *ctx)
 {
-    if (!ctx->ag) return;
-    AgState *g = ctx->ag;
-    DevBuf *all[] = {&g->keys, &g->keys2, &g->ukeys, &g->counts, &g->nruns, &g->nout, &g->nout64, &g->outoff, &g->akey, &g->aval, &g->skey, &g->sval,
-                     &g->del, &g->keep, &g->keep64, &g->vidx, &g->vtx_scm, &g->vtx_cov, &g->idx_p, &g->idx_n, &g->arc_v, &g->arc_w, &g->arc_ls,
-                     &g->arc_cov, &g->arc_comp, &g->arc_del, &g->flags, &g->opens, &g->opens64, &g->open_rank, &g->comp_idx, &g->link, &g->wgt2};
-    for (DevBuf *b : all) b->release();
-    delete g;
+    delete ctx->ag;          // (its buffers free themselves: ~DevBuf)
     ctx->ag = nullptr;
 }
 

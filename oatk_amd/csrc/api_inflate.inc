@@ -11,11 +11,7 @@ struct InfState {
 
 static void inf_state_free(oatk_hip_ctx *ctx)
 {
-    if (!ctx->inf) return;
-    InfState *g = ctx->inf;
-    DevBuf *all[] = {&g->members, &g->status, &g->res, &g->x2n, &g->comp, &g->name_len, &g->name_off, &g->name_out};
-    for (DevBuf *b : all) b->release();
-    delete g;
+    delete ctx->inf;          // (its buffers free themselves: ~DevBuf)
     ctx->inf = nullptr;
 }
 

@@ -10,12 +10,7 @@ struct IngState {
 
 static void ing_state_free(oatk_hip_ctx *ctx)
 {
-    if (!ctx->ing) return;
-    IngState *g = ctx->ing;
-    DevBuf *all[] = {&g->text, &g->cnt, &g->cnt64, &g->blk_off, &g->nl_pos, &g->is_hdr, &g->seq_len, &g->hdr_rank, &g->seq_before, &g->hdr_line,
-                     &g->len, &g->padded, &g->off, &g->hdr_off, &g->seq, &g->flags, &g->info};
-    for (DevBuf *b : all) b->release();
-    delete g;
+    delete ctx->ing;          // (its buffers free themselves: ~DevBuf)
     ctx->ing = nullptr;
 }
 

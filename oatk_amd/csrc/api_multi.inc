@@ -133,17 +133,7 @@ struct MultiState {
 
 static void multi_state_free(oatk_hip_ctx *ctx)
 {
-    if (!ctx->multi) return;
-    MultiState *m = ctx->multi;
-    DevBuf *all[] = {&m->recv_h, &m->recv_s, &m->recv_cov, &m->srt_h, &m->srt_i, &m->iota, &m->flag, &m->grp, &m->grp_of, &m->own_h, &m->own_s, &m->own_cov, &m->reply,
-                     &m->back, &m->l2g, &m->lcov, &m->plan_d, &m->num, &m->bad, &m->need_j, &m->need8, &m->pos_of_j, &m->rep, &m->clhead, &m->req_j, &m->req_k, &m->asked, &m->lid,
-                     &m->seq_out, &m->seq_in, &m->gcov, &m->S, &m->cand, &m->cand_cov, &m->cand_s, &m->cand_mine, &m->ccov_mine,
-                     &m->cs_mine, &m->opack, &m->sel_tmp, &m->keys_all, &m->dist_all, &m->need, &m->need_all, &m->need_srt, &m->uni, &m->owner, &m->mine, &m->kout,
-                     &m->krev, &m->ids_all, &m->rev_all, &m->km_all, &m->lack, &m->ids_i, &m->rev_i, &m->km_i, &m->ec_cov, &m->ec_fwd, &m->ec_del, &m->st64, &m->loc_c,
-                     &m->loc_f, &m->rcv_c, &m->rcv_f, &m->pc};
-    for (DevBuf *b : all) b->release();
-    for (DevBuf &b : m->x) b.release();
-    delete m;
+    delete ctx->multi;          // (its buffers free themselves: ~DevBuf)
     ctx->multi = nullptr;
 }
 

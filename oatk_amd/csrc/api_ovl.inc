@@ -10,12 +10,7 @@ struct OvlState {
 
 static void ovl_state_free(oatk_hip_ctx *ctx)
 {
-    if (!ctx->ovl) return;
-    OvlState *g = ctx->ovl;
-    DevBuf *all[] = {&g->keys, &g->dist, &g->keys2, &g->dist2, &g->val2, &g->ukeys, &g->counts, &g->nruns, &g->cnt64, &g->runoff, &g->nout, &g->nout64,
-                     &g->outoff, &g->o_dist, &g->o_cnt, &g->o_tail, &g->flags, &g->spill};
-    for (DevBuf *b : all) b->release();
-    delete g;
+    delete ctx->ovl;          // (its buffers free themselves: ~DevBuf)
     ctx->ovl = nullptr;
 }
 

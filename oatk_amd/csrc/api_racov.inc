@@ -17,17 +17,7 @@ struct RcState {
 
 static void rc_state_free(oatk_hip_ctx *ctx)
 {
-    RcState *g = ctx->rc;
-    if (!g) return;
-    DevBuf *all[] = {&g->su_off, &g->su_uid, &g->su_pos, &g->scm_cov, &g->utg_off, &g->utg_a, &g->utg_n, &g->idx_p, &g->idx_n, &g->arc_v, &g->arc_w, &g->arc_link,
-                     &g->arc_comp, &g->arc_del, &g->a_sid, &g->a_off, &g->a_s, &g->f_uid, &g->f_ub, &g->f_ue, &g->f_sb, &g->f_se, &g->c_off, &g->c_kmer,
-                     &g->flag, &g->pos, &g->rd_beg, &g->need_c, &g->need_l, &g->need_u, &g->cell_off, &g->lcs_off, &g->u_off, &g->cells, &g->lcs, &g->rec_lb,
-                     &g->rec_ln, &g->st_frg, &g->st_lcsb, &g->st_uid, &g->st_beg, &g->st_len, &g->ma_n, &g->ma_u, &g->nb, &g->cnt, &g->vals, &g->vals2,
-                     &g->avg, &g->covs, &g->covt, &g->key, &g->val, &g->key2, &g->val2, &g->seg_beg, &g->seg_end, &g->diff, &g->err, &g->tmp,
-                     &g->blk_a, &g->em_w, &g->em_e, &g->em_fl, &g->em_ef, &g->em_fpos, &g->ev_key, &g->ev_key2, &g->ev_val, &g->ev_val2, &g->ev_bits, &g->ev_score, &g->lv, &g->arc_out, &g->carry,
-                     &g->t_grp, &g->t_pslot, &g->t_score, &g->t_have, &g->t_first, &g->t_last};
-    for (DevBuf *b : all) b->release();
-    delete g;
+    delete ctx->rc;          // (its buffers free themselves: ~DevBuf)
     ctx->rc = nullptr;
 }
 

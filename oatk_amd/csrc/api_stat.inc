@@ -108,11 +108,7 @@ struct StatState {
 
 static void stat_state_free(oatk_hip_ctx *ctx)
 {
-    if (!ctx->stat) return;
-    StatState *t = ctx->stat;
-    DevBuf *all[] = {&t->key, &t->sorted, &t->uniq, &t->counts, &t->nruns, &t->hist, &t->acc};
-    for (DevBuf *b : all) b->release();
-    delete t;
+    delete ctx->stat;          // (its buffers free themselves: ~DevBuf)
     ctx->stat = nullptr;
 }
 

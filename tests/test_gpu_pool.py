@@ -2,7 +2,7 @@
 once more in a process of their own with the pool switched on for every handle (OATK_TEST_POOL) and its threshold lowered so that EVERY buffer is an address range
 backed by 64 MB pieces (OATK_DEBUG_POOL_MIN) -- scan, assembled batches (buffers that grow and keep what they hold), count, EC graph, correction, assembly graph,
 reader: every comparison those files make with the oracle, the golden vectors and the compiled reference.  The allocation log proves the pieces were what ran.
-(This is the test that found that an address range given back with hipMemAddressFree must not be: csrc/api.hip, DevBuf::vm_range.)"""
+(This is the test that found that an address range given back with hipMemAddressFree must not be: csrc/devmem.hpp, DevBuf::vm_range.)"""
 import os
 import re
 import subprocess
