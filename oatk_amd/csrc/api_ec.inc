@@ -22,6 +22,7 @@ struct EcState {
     uint64_t n_vtx = 0, new_tot = 0;
     uint64_t stats_h[12] = {0};
     uint64_t n_work = 0;
+    uint32_t staged_over = 0;           // where the block walk's overflow flag is copied to: a copy queued on the stream may land after the call that queued it has returned on an error
     bool done = false;
     // graph built on the device (ecgraph.hpp)
     DevBuf g_keys, g_keys2, g_ukeys, g_counts, g_nruns, g_nout, g_nout64, g_outoff, g_akey, g_aval, g_skey, g_sval, g_comp, g_flags, g_huge;
@@ -736,6 +737,8 @@ struct EcKnobs {
     int32_t heavy_fl = 0;         // OATK_DEBUG_EC_HEAVY_FL: bytes of the classes' LDS frame arena (tests: 64 sends every frame to HBM)
     int32_t waves = 32;           // OATK_DEBUG_EC_WAVES: first-tier waves per CU (tools/solverbench.py)
     bool assemble_walk = false;   // OATK_DEBUG_EC_ASSEMBLE_WALK=1: the corrected chains by a third walk (ec_new_n_kernel, ec_assemble_wave_kernel<1>) instead of from the blocks' descriptors (A/B, tests)
+    bool list_walk = false;       // OATK_DEBUG_EC_LIST_WALK=1: the blocks listed by a second walk behind the scan (ec_count_blocks_wave_kernel, ec_list_blocks_wave_kernel) instead of from the
+                                  // descriptors the one walk stages (ec_stage_blocks_wave_kernel, ec_fill_work_kernel) (A/B, tests)
 };
 static EcKnobs ec_knobs_read()
 {
@@ -749,6 +752,7 @@ static EcKnobs ec_knobs_read()
     k.heavy_cap2 = num("OATK_DEBUG_EC_HEAVY_CAP2", 1, 0), k.heavy_fl = num("OATK_DEBUG_EC_HEAVY_FL", 64, 0) & ~7;
     k.waves = num("OATK_DEBUG_EC_WAVES", 1, 32);
     { const char *e = getenv("OATK_DEBUG_EC_ASSEMBLE_WALK"); k.assemble_walk = e && e[0] == '1'; }
+    { const char *e = getenv("OATK_DEBUG_EC_LIST_WALK"); k.list_walk = e && e[0] == '1'; }
     return k;
 }
 
@@ -1268,7 +1272,7 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     {
         uint64_t n_live = 0;
         EENSURE(g_flags, 64);
-        CK(hipMemsetAsync(e->g_flags.as<uint32_t>() + 8, 0, 8, ctx->stream));          // [8] a live vertex without its k-mer here, [9] the live graph branches
+        CK(hipMemsetAsync(e->g_flags.as<uint32_t>() + 8, 0, 12, ctx->stream));         // [8] a live vertex without its k-mer here, [9] the live graph branches, [10] a block beyond a read's staging entries
         EENSURE(live32, (na + 1) * 4); EENSURE(lidx_p, (2 * nv + 1) * 4); EENSURE(lidx_n, (2 * nv + 1) * 4);
         if (na) hipLaunchKernelGGL(ec_live_flag_kernel, blocks(na), dim3(256), 0, ctx->stream, na, (const uint8_t *) e->arc_del.p, e->live32.as<uint32_t>());
         { int rc = ec_exclusive_scan_u32(ctx, e, e->live32, e->live64, e->live_off, na, &n_live); if (rc) return rc; }
@@ -1291,14 +1295,29 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     // ---- blocks ----
     EENSURE(n_blocks, (nr + 1) * 4);
     const dim3 rblocks((unsigned) ((nr + ECR_READS_PER_BLOCK - 1) / ECR_READS_PER_BLOCK > 0? (nr + ECR_READS_PER_BLOCK - 1) / ECR_READS_PER_BLOCK : 1));      // a wave per read
-    hipLaunchKernelGGL(ec_count_blocks_wave_kernel, rblocks, dim3(256), 0, ctx->stream, rd, (const uint8_t *) e->scm_del.p, e->n_blocks.as<uint32_t>());
+    EENSURE(new_n, (nr + 1) * 4); EENSURE(copy_n, (nr + 1) * 4); EENSURE(keep_all, nr + 1);
+    // One walk over the chains: it counts a read's blocks and stages their descriptors, n + 1 entries per read of n syncmers (ec.hpp: ec_stage_blocks_wave_kernel).
+    // The staging array is val_occ, which nothing holds before the chains are assembled and which is of this size once they are (a buffer of its own would be
+    // another 8 bytes per chain entry, 0.4 GB at 2 M reads).  Its last reader is ec_fill_work_kernel below; the assembly ("corrected chains") is its next writer.
+    const uint64_t stage_cap = nocc + nr + 1;
+    e->staged_over = 0;
+    if (kn.list_walk) hipLaunchKernelGGL(ec_count_blocks_wave_kernel, rblocks, dim3(256), 0, ctx->stream, rd, (const uint8_t *) e->scm_del.p, e->n_blocks.as<uint32_t>());
+    else {
+        static_assert(sizeof(EcSeg) == 8, "a staging entry is one val_occ entry");
+        EENSURE(val_occ, stage_cap * sizeof(EcSeg));
+        hipLaunchKernelGGL(ec_stage_blocks_wave_kernel, rblocks, dim3(256), 0, ctx->stream, rd, (const uint8_t *) e->scm_del.p, e->n_blocks.as<uint32_t>(), e->copy_n.as<uint32_t>(),
+                           e->keep_all.as<uint8_t>(), e->val_occ.as<EcSeg>(), stage_cap, e->g_flags.as<uint32_t>() + 10);
+        CK(hipMemcpyAsync(&e->staged_over, e->g_flags.as<uint32_t>() + 10, 4, hipMemcpyDeviceToHost, ctx->stream));       // (waited for with the scan's total)
+    }
     uint64_t n_work = 0;
     { int rc = ec_exclusive_scan_u32(ctx, e, e->n_blocks, e->n_blocks64, e->blk_off, nr, &n_work); if (rc) return rc; }
+    if (e->staged_over) { ctx->err = "error correction: a read has more error blocks than syncmers + 1 (the block walk's staging array)"; return OATK_E_STATE; }
     EENSURE(work, (n_work + 1) * sizeof(EcWork)); EENSURE(out, (n_work + 1) * sizeof(EcBlockOut));
     e->n_work = n_work;
-    EENSURE(new_n, (nr + 1) * 4); EENSURE(copy_n, (nr + 1) * 4); EENSURE(seg, (n_work + 1) * sizeof(EcSeg)); EENSURE(keep_all, nr + 1);
-    hipLaunchKernelGGL(ec_list_blocks_wave_kernel, rblocks, dim3(256), 0, ctx->stream, rd, lv, (const uint8_t *) e->scm_del.p, e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->copy_n.as<uint32_t>(),
-                       e->seg.as<EcSeg>(), e->keep_all.as<uint8_t>());
+    EENSURE(seg, (n_work + 1) * sizeof(EcSeg));
+    if (kn.list_walk) hipLaunchKernelGGL(ec_list_blocks_wave_kernel, rblocks, dim3(256), 0, ctx->stream, rd, lv, (const uint8_t *) e->scm_del.p, e->blk_off.as<uint64_t>(), e->work.as<EcWork>(),
+                                         e->copy_n.as<uint32_t>(), e->seg.as<EcSeg>(), e->keep_all.as<uint8_t>());
+    else hipLaunchKernelGGL(ec_fill_work_kernel, blocks(nr), dim3(256), 0, ctx->stream, rd, lv, e->blk_off.as<uint64_t>(), (const EcSeg *) e->val_occ.as<EcSeg>(), e->work.as<EcWork>(), e->seg.as<EcSeg>());
     // a fixed slot per block for its optimum consensus (oatk_hip_ec_keep_seq): no atomics, no overflow, and the same addresses whichever launch finishes a block
     if (keep_seq) {
         uint64_t slot_words = 0;
@@ -1362,6 +1381,7 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     { int rc = ec_exclusive_scan_u32(ctx, e, e->new_n, e->new_n64, e->new_off, nr, &tot); if (rc) return rc; }
     e->new_tot = tot;
     EENSURE(new_k, (tot + 1) * 8); EENSURE(new_m, (tot + 1) * 4); EENSURE(new_s, (tot + 1) * 8);
+    // (val_occ held the block walk's staging entries until ec_fill_work_kernel had read them, "blocks" above: nothing may write it between the two)
     EENSURE(key_id, (tot + 1) * 4); EENSURE(key_sorted, (tot + 1) * 4); EENSURE(val_occ, (tot + 1) * 8); EENSURE(occ, (tot + 1) * 8);
     aa.new_off = e->new_off.as<uint64_t>(), aa.new_k_mer = e->new_k.as<uint64_t>(), aa.new_m_pos = e->new_m.as<uint32_t>(), aa.new_s_mer = e->new_s.as<uint64_t>();
     aa.key_id = e->key_id.as<uint32_t>(), aa.val_occ = e->val_occ.as<uint64_t>(), aa.sid0 = ctx->sid0;

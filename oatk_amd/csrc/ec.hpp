@@ -469,6 +469,104 @@ __global__ __launch_bounds__(256) void ec_list_blocks_wave_kernel(EcReads rd, Ec
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The blocks listed in ONE walk (r16).  The count walk cannot write a block where it belongs -- blk_off[r] is a scan away -- but it knows everything the list
+// walk found out: copy_n and keep_all need nothing from the scan, and a block is the 8 bytes of its EcSeg (the chain indices of its anchors and two flags;
+// every other field of its EcWork is a function of the chain entries at those two indices).  So the walk leaves the descriptors in a staging array at a
+// place known beforehand, and a kernel without a walk in it builds the work items behind the scan (ec_fill_work_kernel).
+//
+// Staging: read r owns the n + 1 entries from scm_off[r] + r on, n = its chain's length.  That is enough: a round of the walk yields at most one block and
+// moves `beg` on (-1, then end + 1 >= 1, then at least two further each round) until it exceeds n -- at most n + 1 rounds.  A block beyond that, or beyond
+// the array, is not written and raises *overflow, and the call fails.
+// ---------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ec_stage_blocks_wave_kernel(EcReads rd, const uint8_t *scm_del, uint32_t *n_blocks, uint32_t *copy_n, uint8_t *keep_all, EcSeg *stage,
+                                                                   uint64_t stage_cap, uint32_t *overflow)
+{
+    const uint64_t r0 = ((uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6)) * ECR_RPW;
+    const int lane = threadIdx.x & 63;
+    if (r0 >= rd.n_reads) return;
+    EcrRead q[ECR_RPW];
+    ecr_load(rd, scm_del, r0, lane, q);
+#pragma unroll
+    for (int k = 0; k < ECR_RPW; ++k) {
+        const EcrRead &x = q[k];
+        if (x.n < 0) continue;
+        const int32_t n = x.n;
+        const uint64_t s0 = x.o + x.r;                   // the read's first staging entry
+        auto put = [&](int i, const EcBlock &b) {
+            if (i <= n && s0 + (uint64_t) i < stage_cap) stage[s0 + (uint64_t) i] = ec_seg_of(b, n); else *overflow = 1u;
+        };
+        // what the assembly copies between the blocks whatever becomes of them; a read without a good syncmer keeps its chain (syncerr.c:562-572)
+        uint32_t cp = 0;
+        auto on_copy = [&](int32_t first, int32_t last) { if (last > first) cp += (uint32_t) (last - first); };
+        if (n > 64) {
+            if (lane == 0) {
+                const int nbs = ec_blocks(scm_del, rd.k_mer + x.o, rd.m_pos + x.o, n, x.hoco_l, rd.K, put, on_copy);
+                n_blocks[x.r] = nbs < 0? 0u : (uint32_t) nbs;
+                copy_n[x.r] = nbs < 0? (uint32_t) n : cp;
+                keep_all[x.r] = nbs < 0;
+            }
+            continue;
+        }
+        // lane i keeps block i and writes it after the walk (n <= 64: at most 65 blocks, and lane 0 writes the 65th on the spot)
+        EcBlock mine;
+        mine.beg_utg = 0, mine.end_utg = 0, mine.beg_pos = 0, mine.l = 0, mine.beg = 0, mine.end = 0, mine.r = 0;
+        int nb = 0;
+        const int res = ec_blocks_wave(lane, n, x.km, x.mp, x.del, x.hoco_l, rd.K,
+                                       [&](int i, const EcBlock &b) { ++nb; if (i < 64) { if (lane == i) mine = b; } else if (lane == 0) put(i, b); }, on_copy);
+        if (lane < nb) put(lane, mine);
+        if (lane == 0) n_blocks[x.r] = (uint32_t) nb, copy_n[x.r] = res < 0? (uint32_t) n : cp, keep_all[x.r] = res < 0;
+    }
+}
+
+// What ec_list_blocks_wave_kernel's `put` took from the walk's EcBlock, read back from the chain entries at the block's two indices (ec_blocks: the three cases).
+// o, n: the read's chain; d: the block's staged descriptor.
+__device__ __forceinline__ EcWork ec_work_of(const EcReads &rd, const EcLive &lv, uint64_t r, uint64_t o, int32_t n, const EcSeg &d)
+{
+    const int32_t beg = (int32_t) d.beg, end = (int32_t) (d.end_fl >> 2);       // end: min(EcBlock::end, n)
+    const uint64_t kb = rd.k_mer[o + d.beg];
+    const uint32_t mb = rd.m_pos[o + d.beg];
+    EcWork y;
+    y.read = (uint32_t) r, y.hs16 = (uint32_t) (rd.off[r] >> 6);
+    if (d.end_fl & EC_SEG_R) {
+        y.beg_utg = (kb & ~1ULL) | (uint64_t) !(mb & 1u);
+        y.beg_pos = 0, y.end_utg = EC_NONE, y.l = (int32_t) (mb >> 1), y.r = 1;
+        y.pad = d.beg;
+    } else {
+        y.beg_utg = (kb & ~1ULL) | (mb & 1u);
+        y.beg_pos = (mb >> 1) + (uint32_t) rd.K;
+        if (d.end_fl & EC_SEG_OPEN) y.end_utg = EC_NONE, y.l = (int32_t) rd.hoco_l[r] - (int32_t) y.beg_pos;
+        else {
+            const uint64_t ke = rd.k_mer[o + (uint32_t) end];
+            const uint32_t me = rd.m_pos[o + (uint32_t) end];
+            y.end_utg = (ke & ~1ULL) | (me & 1u), y.l = (int32_t) (me >> 1) - (int32_t) y.beg_pos;
+        }
+        y.r = 0;
+        y.pad = beg + 1 < n && end > beg + 1? (uint32_t) (end - beg - 1) : 0u;
+    }
+    y.lp = lv.idx_p[y.beg_utg], y.ln = lv.idx_n[y.beg_utg];
+    return y;
+}
+
+// The work items and the descriptors at their places: a workgroup per 256 reads, its lanes side by side over their blocks -- the 257 offsets sit in LDS and a lane
+// finds its block's read by bisection -- so the 48-byte items leave in order and every lane has a block.  (A lane per read looping over its blocks, 3.9 on
+// average, was built and measured beside it: the `ec_mark` timer 2.26 ms against 1.80 at config 3, profiles/r16a_fill_layout.txt)
+__global__ __launch_bounds__(256) void ec_fill_work_kernel(EcReads rd, EcLive lv, const uint64_t *blk_off, const EcSeg *stage, EcWork *work, EcSeg *seg)
+{
+    __shared__ uint64_t offs[257];
+    const uint64_t r0 = (uint64_t) blockIdx.x * 256;
+    for (uint32_t t = threadIdx.x; t < 257; t += 256) offs[t] = blk_off[r0 + t < rd.n_reads? r0 + t : rd.n_reads];
+    __syncthreads();
+    for (uint64_t j = offs[0] + threadIdx.x; j < offs[256]; j += 256) {
+        uint32_t lo = 0, hi = 256;                       // the last read with offs[.] <= j
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (offs[mid] <= j) lo = mid; else hi = mid; }
+        const uint64_t r = r0 + lo, o = rd.scm_off[r];
+        const EcSeg d = stage[o + r + (j - offs[lo])];
+        work[j] = ec_work_of(rd, lv, r, o, (int32_t) (rd.scm_off[r + 1] - o), d);
+        seg[j] = d;
+    }
+}
+
 // the corrected chains' lengths from the blocks' outcomes (r04; until then a third walk over the chains, ec_assemble_wave_kernel<0>): what the read keeps between
 // its blocks, plus per block the optimum path's interior (syncerr.c:513-532) or the originals it keeps
 __global__ __launch_bounds__(256) void ec_new_n_kernel(uint64_t n_reads, const uint32_t *copy_n, const uint64_t *blk_off, const EcWork *work, const EcBlockOut *out, uint32_t *new_n)

@@ -271,7 +271,11 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
     int32_t rep_start = 0x7FFFFFFF;             // first chunk hashed in repeat mode (valid while rep_mode)
     uint32_t quiet = 0, tpar = 0;
     const int32_t wave_first = __builtin_amdgcn_readfirstlane((int) (wid * OATK_WAVE * C));
-    for (uint32_t I0 = 0; I0 < hl; I0 += T, next_tile_addr(), tpar ^= 1u) {
+    // A wave takes the tiles in which it has a position inside the read: the later waves of a read's last tile lie wholly behind hoco_l in about half the
+    // reads, and leave the loop a tile early (r16; until then they rolled eight hashes per lane along with every one predicated off, then decided nothing in
+    // the edge form of P3).  What such a wave still owes the workgroup follows the loop.
+    uint32_t I0 = 0;
+    for (; I0 + (uint32_t) wave_first < hl; I0 += T, next_tile_addr(), tpar ^= 1u) {
         if (rep_next != rep_mode) { rep_mode = rep_next; rep_start = rep_mode? (int32_t) (I0 / C) : 0x7FFFFFFF; }
         // ---- P1: s-mer hashes of this lane's chunk, chunk minimum, wave prefix/suffix minima ----
         const int32_t i0 = (int32_t) (I0 + tid * C);
@@ -293,8 +297,12 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
             uint64_t cm = UINT64_MAX;                   // the chunk minimum in full (repeat mode only)
             uint32_t cmin = 0xFFFFFFFFu;                // its top word: what the filter looks at
             // (the test is made for the WAVE: a wave with one lane at either end of the read would otherwise run both branches, eight
-            //  hashes each -- two waves per read, 5 % of the kernel)
-            if (wb + 1 >= S && (uint32_t) (wb + OATK_WAVE * C) <= hl) {
+            //  hashes each -- two waves per read, 5 % of the kernel.  r16, S = 31: the two waves that hold a read's start and its end take the fixed-field
+            //  form as well, with the hashes of positions where no s-mer ends -- i + 1 < S, i >= hoco_l -- set to MAX afterwards: two compares and a select
+            //  per position instead of the rolling form's twelve instructions more.  The bases such a position is hashed from lie in front of the read or
+            //  in the slack behind it and are anything; its hash is thrown away.)
+            const bool inside = wb + 1 >= S && (uint32_t) (wb + OATK_WAVE * C) <= hl;     // no position of the wave lies in front of the first s-mer's end or behind the read
+            if (S31 || inside) {
                 if (S31) {
                     // The s-mer that ends at position i0 + b is a FIXED bit field of the 96-bit window [a_hi : a_lo : vbh] (bases i0 - 32 .. i0 + 15): bits
                     // [91 - 2b : 30 - 2b]; its reverse complement is the field [65 + 2b : 4 + 2b] of the window's reverse complement [r2 : r1 : r0].  Two
@@ -305,7 +313,7 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
                         return ~(((r >> 1) & 0x55555555u) | ((r & 0x55555555u) << 1));
                     };
                     const uint32_t r0 = rc16(a_hi), r1 = rc16(a_lo), r2 = rc16(vbh);
-                    auto hash_chunk = [&](auto keep) __attribute__((always_inline)) {
+                    auto hash_chunk = [&](auto keep, auto ends) __attribute__((always_inline)) {
 #pragma unroll
                         for (int b = 0; b < C; ++b) {
                             // both strands LEFT-aligned in 64 bits, two bits of the neighbouring base below them: they never decide the comparison (an odd-length
@@ -314,15 +322,24 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
                             uint64_t rv = (uint64_t) __builtin_amdgcn_alignbit(r2, r1, 2 + 2 * b) << 32 | __builtin_amdgcn_alignbit(r1, r0, 2 + 2 * b);
                             asm("" : "+v"(fw), "+v"(rv));        // (the halves are read back out of the register pairs: without this the compiler keeps each half twice, a v_mov per word)
                             const uint64_t cn = fw < rv? fw : rv;
-                            const uint64_t mv4 = hash64_s31_left(cn);   // four times the hash: the order is the hash's, the top word a shift away
+                            uint64_t mv4 = hash64_s31_left(cn);   // four times the hash: the order is the hash's, the top word a shift away
                             y[b] = (uint32_t) (mv4 >> 34);
+                            if (decltype(ends)::value) {          // the wave holds the read's start or its end: MAX where no s-mer ends
+                                const bool ok = i0 + b + 1 >= S && (uint32_t) (i0 + b) < hl;
+                                y[b] = ok? y[b] : 0xFFFFFFFFu;
+                                if (decltype(keep)::value) mv4 = ok? mv4 : UINT64_MAX;
+                            }
                             cmin = y[b] < cmin? y[b] : cmin;
                             if (decltype(keep)::value) cm = mv4 < cm? mv4 : cm;
                         }
-                        if (decltype(keep)::value) cm >>= 2;
+                        if (decltype(keep)::value) cm = decltype(ends)::value && cm == UINT64_MAX? cm : cm >> 2;      // (four times a hash is never MAX)
                     };
                     // (two copies of the loop, chosen by a scalar branch: as one loop with a per-position select the compiler keeps the 64-bit chain for every position)
-                    if (__builtin_amdgcn_readfirstlane((int) rep_mode)) hash_chunk(std::true_type()); else hash_chunk(std::false_type());
+                    if (inside) {
+                        if (__builtin_amdgcn_readfirstlane((int) rep_mode)) hash_chunk(std::true_type(), std::false_type()); else hash_chunk(std::false_type(), std::false_type());
+                    } else {
+                        if (__builtin_amdgcn_readfirstlane((int) rep_mode)) hash_chunk(std::true_type(), std::true_type()); else hash_chunk(std::false_type(), std::true_type());
+                    }
                 } else {
                     const uint64_t X = ((uint64_t) a_hi << 32 | a_lo) << (2 * (32 - S));       // the S bases that end at i0 - 1, at the top
                     uint64_t fw = X >> (64 - 2 * S), rv = revcomp32(X) & mask;
@@ -337,7 +354,7 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
                         cm = mv < cm? mv : cm;      // (S != 31: the chain is always kept; this form of the kernel is not the one the headline workload runs)
                     }
                 }
-            } else {                                    // first / last chunk of the read
+            } else {                                    // first / last chunk of the read (S != 31)
                 const uint64_t X = ((uint64_t) a_hi << 32 | a_lo) << (2 * (32 - S));       // the S bases that end at i0 - 1, at the top
                 uint64_t fw = X >> (64 - 2 * S), rv = revcomp32(X) & mask;
 #pragma unroll
@@ -407,7 +424,9 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
         uint32_t backF_keep = 0, fwd0_keep = 0, fwd1_keep = 0;
         uint32_t kinds = 0;                             // 2 bits per position of the chunk: 0 none, 1 Close, 2 Open
         uint32_t tiemask = 0;
-        {
+        // (not in a wave where no k-mer ends -- E + 1 <= wb + 512 < K for every position E of it: the first wave of a read, the first two on the 4096-slot
+        //  ring.  The edge form below found `fits` false at all eight positions there, after the loads and the filter: nothing decided, nothing tied.  r16)
+        if (!(wb + OATK_WAVE * C < K)) {
             // minimum of the chunk minima over chunks [lo, hi], hi - lo = D - 1: suffix of lo's block, prefix of hi's block and,
             // when the two are not adjacent, the one whole block between them.  Chunks before the read map to ring slots that
             // still hold the initial MAX, which is exactly "no constraint".
@@ -573,6 +592,18 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
         if (lane == 0) w_cnt[par][wid] = wtot;
         pend_kinds = kinds, pend_rank = incl - ns, pend_i0 = i0, pend_wtot = wtot, pend_par = par, pend_any = 1u;
         par ^= 1u;
+    }
+    if (I0 < hl) {
+        // The wave left before the read's last tile: it passes that tile's two barriers and flush() -- whose own barriers stand behind conditions that must come
+        // out the same in every wave, so pend_any stays set -- and leaves a count of zero.  Its ring slots keep what an older tile left there, and nothing reads
+        // them: the other waves' ranges and windows, fill_c_min and the tie path all look BACKWARDS from positions in front of this wave, and no tile follows.
+        // (A read of one tile whose later waves never enter the loop: pend_any is still 0 in EVERY wave when they call flush() here, as it is in the loop's first
+        //  round, so flush() returns at once in all of them.)
+        __syncthreads();
+        __syncthreads();
+        flush();
+        if (lane == 0) w_cnt[par][wid] = 0;
+        pend_kinds = 0, pend_rank = 0, pend_wtot = 0, pend_par = par, pend_any = 1u;
     }
     __syncthreads();
     flush();
