@@ -8,11 +8,14 @@
 #include "ec_seq.hpp"
 #include <rocprim/device/device_run_length_encode.hpp>
 #include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
 
 struct EcState {
     DevBuf idx_p, idx_n, arc_v, arc_w, arc_ls, arc_cov, arc_del, conv;   // graph (device copy)
     DevBuf scm_del, err_del, vtx_hs_off, vtx_mpos;
     DevBuf copy_n, seg, keep_all, n_blocks, n_blocks64, blk_off, work, out, path_pool, cursor, todo, todo2, slabs, big_slabs, os_slabs;
+    DevBuf qkey, qidx, qtmp[4];   // the solver's queues in source order (ec_queue_sort): keys and sorted lists of a call one behind the other; a side stream's sort has its own temporary
+    uint64_t n_live = 0, q_used = 0, qk_used = 0;      // live arcs of the resident marking (the width of a queue key); words of qidx / qkey the call's lists take so far
     DevBuf hyb_slabs[16];         // the hybrid tier's HBM slabs, one buffer per launch of a call (launches may run side by side), sized by the blocks the launch has
     hipStream_t aux[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};       // the larger solver tiers run beside the first one ([4]: of the lowest priority level)
     hipEvent_t aux_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, fork_ev = nullptr;
@@ -737,6 +740,9 @@ struct EcKnobs {
     int32_t heavy_fl = 0;         // OATK_DEBUG_EC_HEAVY_FL: bytes of the classes' LDS frame arena (tests: 64 sends every frame to HBM)
     int32_t waves = 32;           // OATK_DEBUG_EC_WAVES: first-tier waves per CU (tools/solverbench.py)
     bool assemble_walk = false;   // OATK_DEBUG_EC_ASSEMBLE_WALK=1: the corrected chains by a third walk (ec_new_n_kernel, ec_assemble_wave_kernel<1>) instead of from the blocks' descriptors (A/B, tests)
+    int memo = 2;                 // OATK_DEBUG_EC_MEMO=0: every level of every block gathers its k-mer again (ec_wave.hpp: EcwMemo); =1: levels are reused, no block starts at its
+                                  // sink; unset: both (A/B, tests)
+    bool queue_sort = true;       // OATK_DEBUG_EC_QUEUE_SORT=0: the wave solver's queues in read order (A/B, tests)
     bool list_walk = false;       // OATK_DEBUG_EC_LIST_WALK=1: the blocks listed by a second walk behind the scan (ec_count_blocks_wave_kernel, ec_list_blocks_wave_kernel) instead of from the
                                   // descriptors the one walk stages (ec_stage_blocks_wave_kernel, ec_fill_work_kernel) (A/B, tests)
 };
@@ -753,6 +759,8 @@ static EcKnobs ec_knobs_read()
     k.waves = num("OATK_DEBUG_EC_WAVES", 1, 32);
     { const char *e = getenv("OATK_DEBUG_EC_ASSEMBLE_WALK"); k.assemble_walk = e && e[0] == '1'; }
     { const char *e = getenv("OATK_DEBUG_EC_LIST_WALK"); k.list_walk = e && e[0] == '1'; }
+    { const char *e = getenv("OATK_DEBUG_EC_MEMO"); k.memo = e && (e[0] == '0' || e[0] == '1') && !e[1]? e[0] - '0' : 2; }
+    { const char *e = getenv("OATK_DEBUG_EC_QUEUE_SORT"); k.queue_sort = !(e && e[0] == '0' && !e[1]); }
     return k;
 }
 
@@ -893,6 +901,64 @@ static int ec_sort_longest_first(oatk_hip_ctx *ctx, EcState *e, uint32_t *list, 
     ENSURE(tmp, tb);
     CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, k_in, k_out, list, v_out, n, 0, 32, ctx->stream));
     CK(hipMemcpyAsync(list, v_out, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    return OATK_OK;
+}
+
+// A queue of the wave solver in source order: blocks of one source, and among them of one sink, next to each other, so that a wave's batch is mostly one walk
+// (ec_wave.hpp: EcwMemo).  The key is the source's first live arc -- one per source that has an arc -- then the sink.  Only neighbours matter, not the order, so
+// the key is as narrow as the batch allows: the bits its live arcs need, and of the sink the low bits that fill the key up to the next whole 8-bit pass of the
+// sort beyond eight (at config 3: 14 + 10 bits, three passes over 32-bit keys; the vertex ids themselves need 24 bits and would make it 64-bit keys and five
+// passes, 0.75 ms -- profiles/r17a).  Two sinks of one source that agree in those bits are interleaved in read order, which costs their blocks the start at the
+// sink and nothing else; the sort keeps read order among equal keys.  list == nullptr: every work item.  The sorted list is *sorted, in qidx behind the call's
+// earlier ones (the caller has made room: ec_queue_room); `st` and `tmp`: the stream the launch is on and a temporary nobody else on another stream uses.
+static int ec_queue_room(oatk_hip_ctx *ctx, EcState *e, uint64_t n_work)
+{
+    e->q_used = e->qk_used = 0;
+    EENSURE(qkey, (4 * (n_work + 1) + 64) * 4); EENSURE(qidx, 2 * (n_work + 1) * 4);
+    return OATK_OK;
+}
+static int ec_queue_sort(oatk_hip_ctx *ctx, EcState *e, const uint32_t *list, uint64_t n, hipStream_t st, DevBuf &tmp, const uint32_t **sorted)
+{
+    auto bits = [](uint64_t v) { int b = 1; while (b < 64 && (v >> b)) ++b; return b; };
+    const uint64_t end_max = 2 * e->g_n_vtx;                 // (an open block's EC_NONE: one value for all of them)
+    const uint32_t lp_max = (uint32_t) e->n_live;
+    const int lb = bits(lp_max), total = lb + 8 >= 32? 32 : (lb + 8 + 7) & ~7;
+    const int eb = bits(end_max) < total - lb? bits(end_max) : total - lb;
+    if (e->q_used + n > e->qidx.cap / 4 || e->qk_used + 2 * (n + 1) > e->qkey.cap / 4) { ctx->err = "EC solver: more sorted queues than room for them (internal)"; return OATK_E_STATE; }
+    uint32_t *v_out = e->qidx.as<uint32_t>() + e->q_used, *k_in = e->qkey.as<uint32_t>() + e->qk_used, *k_out = k_in + (n + 1);
+    e->q_used += n, e->qk_used += 2 * (n + 1);
+    hipLaunchKernelGGL(ec_queue_keys_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, e->work.as<EcWork>(), list, n, lp_max, end_max, eb, k_in);
+    size_t tb = 0;
+    if (list) {
+        CK(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, list, v_out, n, 0, (unsigned) (eb + lb), st));
+        if (!tmp.ensure(tb, st)) { ctx->err = "hipMalloc failed (EC queue sort)"; return OATK_E_NOMEM; }
+        CK(rocprim::radix_sort_pairs(tmp.p, tb, k_in, k_out, list, v_out, n, 0, (unsigned) (eb + lb), st));
+    } else {
+        rocprim::counting_iterator<uint32_t> iota(0);
+        CK(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, iota, v_out, n, 0, (unsigned) (eb + lb), st));
+        if (!tmp.ensure(tb, st)) { ctx->err = "hipMalloc failed (EC queue sort)"; return OATK_E_NOMEM; }
+        CK(rocprim::radix_sort_pairs(tmp.p, tb, k_in, k_out, iota, v_out, n, 0, (unsigned) (eb + lb), st));
+    }
+    *sorted = v_out;
+    return OATK_OK;
+}
+// blocks a wave of a larger tier takes from its queue at a time: consecutive blocks of a sorted list share a wave only in a batch, and a few hundred long blocks
+// must still have a wave each (r04e)
+static int32_t ec_routed_batch(uint64_t n_todo, uint64_t waves)
+{
+    const uint64_t b = waves? n_todo / (16 * waves) : 1;
+    return (int32_t) (b < 1? 1 : (b > ECW_BATCH? ECW_BATCH : b));
+}
+// OATK_DEBUG_EC_STAGES: what the launches of ec_wave_kernel reused (EcwArgs::memo_stat: two counters per launch behind the cursor's 64)
+struct EcMemoLog { int tier; unsigned long long n; int32_t batch; int slot; };
+static int ec_memo_report(oatk_hip_ctx *ctx, EcState *e, const std::vector<EcMemoLog> &log)
+{
+    if (log.empty()) return OATK_OK;
+    unsigned long long c[128];
+    CK(hipMemcpyAsync(c, (unsigned long long *) e->cursor.p + 64, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    for (const EcMemoLog &l : log)
+        fprintf(stderr, "[ec stages] wave solver, tier %d, %llu blocks: batch %d, %llu levels reused, %llu blocks started at their sink\n", l.tier, l.n, (int) l.batch, c[2 * l.slot], c[2 * l.slot + 1]);
     return OATK_OK;
 }
 
@@ -1116,10 +1182,17 @@ static int ec_solve_classes(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, co
         CK(hipEventRecord(e->aux_ev[used_aux], st));
         ++used_aux;
     }
+    std::vector<EcMemoLog> mlog;
     if (T0.usable && n_work) {
         EcwArgs a = base;
         ec_set_caps(a, T0);
         a.todo = nullptr, a.n_todo = 0, a.next = cur + qslot++, a.skip_l = T0.cap_t, a.batch = ECW_BATCH;
+        if (kn.queue_sort && n_work > 1) {          // (where the graph branches a walk ends at the first frame, and the kernel reuses nothing behind it)
+            { int rc = ec_queue_room(ctx, e, n_work); if (rc) return rc; }
+            { int rc = ec_queue_sort(ctx, e, nullptr, n_work, ctx->stream, ctx->tmp, &a.todo); if (rc) return rc; }
+            a.n_todo = n_work;
+        }
+        if (kn.stages) a.memo_stat = cur + 64 + 2 * mlog.size(), mlog.push_back(EcMemoLog{0, (unsigned long long) n_work, a.batch, (int) mlog.size()});
         // (a small block inside a repeat tries tens of thousands of arcs on a handful of diagonals -- 70 ms of ONE wave on the config-1 surrogate with everything else waiting
         //  for this launch: past the arc budget it is left to the classes and, past their step budget, to the second stage)
         a.arc_budget = EC_ARC_BUDGET;
@@ -1133,6 +1206,7 @@ static int ec_solve_classes(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, co
     // 2. the first tier's left-overs (deep searches: the longest chains of the batch) as soon as it is done; then everything launched so far; then the second stage
     CK(hipMemcpyAsync(cnts, cur, sizeof(cnts), hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
+    if (kn.stages) { int rc = ec_memo_report(ctx, e, mlog); if (rc) return rc; }
     if (cnts[1] > routed[1]) { int rc = launch_class(1, list[1] + routed[1], cnts[1] - routed[1], ctx->stream); if (rc) return rc; }
     n_big = cnts[1] + routed[2] + routed[3] + routed[4];
     for (int i = 0; i < used_aux; ++i) CK(hipStreamWaitEvent(ctx->stream, e->aux_ev[i], 0));
@@ -1167,6 +1241,8 @@ static int ec_solve_tiers(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, cons
     EENSURE(todo, 3 * (n_work + 1) * 4); EENSURE(todo2, (n_work + 1) * 4);
     uint32_t *list[4] = {nullptr, e->todo.as<uint32_t>(), e->todo.as<uint32_t>() + (n_work + 1), e->todo.as<uint32_t>() + 2 * (n_work + 1)};
     int qslot = 4, hyb_k = 0;
+    std::vector<EcMemoLog> mlog;
+    if (kn.queue_sort) { int rc = ec_queue_room(ctx, e, n_work); if (rc) return rc; }
     auto next_usable = [&](int t) { int u = t + 1; while (u < LAST && !T[u].usable) ++u; return u; };
     auto launch = [&](int tier, const uint32_t *todo, uint64_t n_todo, hipStream_t st, bool routed, uint64_t max_waves = 0) -> int {
         if (qslot >= 60) { ctx->err = "EC solver: more rounds of left-overs than queue counters (internal)"; return OATK_E_STATE; }
@@ -1178,7 +1254,7 @@ static int ec_solve_tiers(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, cons
         ec_set_caps(a, t);
         a.todo = todo, a.n_todo = n_todo, a.next = queue;
         a.skip_l = routed && tier == 0? t.cap_t : 0x7FFFFFFF;
-        a.batch = tier == 0? ECW_BATCH : 1;                        // (241 long blocks in batches of sixteen were sixteen waves' work: r04e)
+        a.batch = ECW_BATCH;                                       // (a larger tier: by its blocks and waves, below)
         // a block outgrows an LDS tier by the depth of its search or by its frames (its length was checked before): the hybrid tier, without such limits, takes it
         const int nx = tier < LAST - 1 && T[LAST - 1].usable? LAST - 1 : next_usable(tier);
         a.todo_out = list[nx], a.todo_cnt = cur + nx;
@@ -1188,10 +1264,26 @@ static int ec_solve_tiers(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, cons
         a.os_slabs = e->os_slabs.as<uint32_t>() + os_next;
         os_next += waves * a.os_words;
         const uint64_t n_items = todo? n_todo : n_work;
+        if (tier > 0) {                                            // (241 long blocks in batches of sixteen were sixteen waves' work: r04e)
+            uint64_t w1 = waves < n_items? waves : n_items;
+            if (max_waves && w1 > max_waves) w1 = max_waves;
+            a.batch = ec_routed_batch(n_items, w1);
+        }
+        // the queue in source order: every block for the first tier, a routed list for a larger one where its waves take batches (a wave forgets between batches:
+        // a list taken block by block gains nothing).  Sorted on the launch's own stream: the first tier does not wait for a side stream's list, and its own sort,
+        // of every block, ends after a side stream's, of some: the larger tiers must be on the CUs before the first tier fills them (below).  Sorted in front of
+        // the routing instead, the first tier got there first and the second ran behind it: 21.3 ms against 12.7 (profiles/r17a_ab_bench.txt)
+        if (kn.queue_sort && (todo? routed : true) && n_items > 1 && a.batch > 1) {
+            DevBuf *tmp = &ctx->tmp;
+            for (int i = 0; i < 4; ++i) if (st == e->aux[i]) tmp = &e->qtmp[i];
+            { int rc = ec_queue_sort(ctx, e, todo, n_items, st, *tmp, &a.todo); if (rc) return rc; }
+            a.n_todo = n_items;
+        }
         const uint64_t groups = (n_items + (uint64_t) a.batch - 1) / (uint64_t) a.batch;
         if (waves > groups) waves = groups;
         if (max_waves && waves > max_waves) waves = max_waves;
         if (!waves) return OATK_OK;
+        if (kn.stages && mlog.size() < 64) a.memo_stat = cur + 64 + 2 * mlog.size(), mlog.push_back(EcMemoLog{tier, (unsigned long long) n_items, a.batch, (int) mlog.size()});
         if (t.hybrid) {
             void *p = nullptr;
             int rc = ec_slab_buf(ctx, e, hyb_k, (waves + ECW_WPB) * t.slab + 64, st, "the hybrid tier", "slabs", &p); if (rc) return rc;
@@ -1248,6 +1340,7 @@ static int ec_solve_tiers(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, cons
         if (!any && waited_aux) break;
         if (!waited_aux) { for (int i = 0; i < used_aux; ++i) CK(hipStreamWaitEvent(ctx->stream, e->aux_ev[i], 0)); waited_aux = true; }
     }
+    if (kn.stages) { int rc = ec_memo_report(ctx, e, mlog); if (rc) return rc; }
     return OATK_OK;
 }
 
@@ -1278,6 +1371,7 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
         { int rc = ec_exclusive_scan_u32(ctx, e, e->live32, e->live64, e->live_off, na, &n_live); if (rc) return rc; }
         if (n_live >= 0xFFFFFFFFULL) { ctx->err = "error correction: more than 2^32 live arcs"; return OATK_E_ARG; }
         EENSURE(larc, (n_live + 1) * sizeof(EcLiveArc));
+        e->n_live = n_live;
         hipLaunchKernelGGL(ec_live_idx_kernel, blocks(2 * nv), dim3(256), 0, ctx->stream, 2 * nv, e->idx_p.as<uint64_t>(), e->idx_n.as<uint32_t>(),
                            e->live_off.as<uint64_t>(), e->lidx_p.as<uint32_t>(), e->lidx_n.as<uint32_t>(), e->g_flags.as<uint32_t>() + 9);
         if (na) hipLaunchKernelGGL(ec_live_arc_kernel, blocks(na), dim3(256), 0, ctx->stream, na, (const uint8_t *) e->arc_del.p, e->live_off.as<uint64_t>(),
@@ -1336,15 +1430,16 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     // classes with budgets and the second stage run: the config-1 surrogate has 304, and its searches are what they were built for (0.23 s against 3.2).
     const bool heavy = kn.heavy < 0? graph_branches : kn.heavy != 0;
     uint64_t pool_cap = 2 * nocc + (uint64_t) 16384 * ECW_POOL_CHUNK + 4096;
-    EENSURE(cursor, 512); EENSURE(stats, 16 * 8);
+    EENSURE(cursor, 512 + 128 * 8); EENSURE(stats, 16 * 8);              // (behind the 64 counters: two per launch of the wave solver, OATK_DEBUG_EC_STAGES)
     uint64_t n_big = 0;
     uint32_t max_hl = 0;                 // the longest read of the batch, once the slab tier has needed it
     for (;;) {
         EENSURE(path_pool, pool_cap * 8);
-        CK(hipMemsetAsync(e->cursor.p, 0, 512, ctx->stream));
+        CK(hipMemsetAsync(e->cursor.p, 0, 512 + 128 * 8, ctx->stream));
         EcwArgs base = {};               // what every launch shares; each sets the rest of its own
         base.lv = lv, base.rd = rd, base.work = e->work.as<EcWork>(), base.n_work = n_work, base.max_edist = max_edist;
         base.out = e->out.as<EcBlockOut>(), base.path_pool = e->path_pool.as<uint64_t>(), base.pool_cap = pool_cap;
+        base.memo = kn.memo;
         base.pool_cursor = (unsigned long long *) e->cursor.p;       // [0] pool, then the lists' and work queues' counters; [63] blocks that outgrew the slabs
         if (keep_seq) {
             CK(hipMemsetAsync(e->qend.p, 0, (n_work + 1) * 4, ctx->stream));

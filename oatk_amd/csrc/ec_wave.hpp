@@ -366,11 +366,29 @@ __device__ __forceinline__ EcwArcRegs ecw_arc_load(const EcLiveArc *arc, uint32_
     return r;
 }
 
+// What a wave keeps from one block of a batch to the next (the queue is sorted by source, then by sink: ec_queue_keys_kernel).  A search is a walk until
+// the first vertex with two arcs out, the walk is a function of the source alone, and so are the bases it appends: while no frame exists, level d of every
+// block of one source writes the same words to the same place of `cs`, and a later append only writes at or beyond its own c_len (its first word keeps
+// the fields below).  `depth` leading levels of `src`'s walk are in cs; a block of that source adds their lengths up and leaves the k-mers where they are.
+// ff_*: the block before reached its sink `ff_end` at level ff_d over levels that decided nothing (the interior rule below); a block of the same source
+// and sink for which that rule's two length tests hold at both ends of the stretch -- they are monotone in the level -- starts at the sink's level.
+// c_path[1 .. ff_d] are the walk's vertices as well and stay.  Reset at the start of every batch: what is reused depends on the queue's order alone.
+struct EcwMemo {
+    uint64_t src, ff_end;         // EC_NONE: cs holds no walk
+    int32_t depth;
+    int32_t ff_d;                 // 0: no sink known
+    uint32_t ff_arc;              // the arc into the sink
+    int32_t ff_cl0, ff_clp;       // c_len after level 0, and before level ff_d
+    int32_t mode;                 // 0: off (OATK_DEBUG_EC_MEMO=0), 1: levels only, 2: levels and the start at the sink
+    uint32_t n_reuse, n_ff;       // levels not appended again, blocks started at their sink (OATK_DEBUG_EC_STAGES)
+    __device__ __forceinline__ void reset() { src = ff_end = EC_NONE, depth = 0, ff_d = 0, ff_arc = 0, ff_cl0 = ff_clp = 0; }
+};
+
 // Solve one block with the whole wave.  Returns false when the scratch is too small (the block is then re-run by a larger tier).
 // KEEP (oatk_hip_ec_keep_seq): the caller wants the optimum consensus -- its length comes back in olen_out and s.os holds it whenever an optimum exists,
 // also where the search ends with it.  Without KEEP this is the code it was: olen_out is not touched.
 template <bool KEEP = false>
-__device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWork &wk, const EcwScratch &s, double max_edist,
+__device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWork &wk, const EcwScratch &s, double max_edist, EcwMemo &mm,
                                 uint32_t &status_out, uint32_t &np_out, uint32_t &tried_out, uint32_t &n_path_out, uint32_t &wf_steps_out, uint32_t &wf_diag_out, uint32_t &olen_out)
 {
     const int lane = threadIdx.x & 63;
@@ -379,11 +397,23 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
     int32_t bw = (int32_t) ceil((double) tl * max_edist);
     if (bw < EC_MIN_ERR_BASE) bw = EC_MIN_ERR_BASE;
     if (ECW_RARE(tl > s.cap_t || 2 * bw + 8 > s.cap_w)) return false;
-    // the first arc out of the source is fetched while the target is gathered
+    // whose walk cs holds (EcwMemo): m_live while this block is on it and has built no frame
+    bool m_live = false;
+    if (mm.mode) {
+        if (ECW_LIKELY(wk.ln == 1)) {
+            if (wk.beg_utg != mm.src) mm.reset(), mm.src = wk.beg_utg;
+            m_live = true;
+        } else mm.reset();
+    }
+    const bool ff = mm.mode > 1 && m_live && mm.ff_d > 0 && wk.end_utg == mm.ff_end && mm.depth >= mm.ff_d && mm.ff_cl0 >= bw + 3 && mm.ff_clp - K <= tl + bw;
+    bool ff_walk = mm.mode > 1 && m_live && wk.end_utg != EC_NONE;      // every level so far was an interior one
+    int32_t cl0 = ff? mm.ff_cl0 : 0;
+    // the first arc the search takes -- out of the source, or into the sink -- is fetched while the target is gathered
+    const uint32_t arc0 = ff? mm.ff_arc : wk.lp;
     EcwArcRegs pre;
     pre.a = make_uint4(0, 0, 0, 0), pre.b = make_uint2(0, 0);
     uint32_t pre_idx = 0xFFFFFFFFu;
-    if (wk.ln) pre = ecw_arc_load(lv.arc, wk.lp), pre_idx = wk.lp;
+    if (wk.ln) pre = ecw_arc_load(lv.arc, arc0), pre_idx = arc0;
     // target: the read segment, reverse-complemented for a leading block (get_kmer_dna_seq, syncmer.c:1237)
     const uint8_t *hs = rd.hoco_s + ((uint64_t) wk.hs16 << 4);
     // (a wave's 64 windows are 1024 bases and two blocks in three are shorter than that: the common case is one window per lane, and the
@@ -443,10 +473,15 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
         top = fsz;
         fsz += need;
         ++nfr;
+        m_live = false;
         return true;
     };
-    if (ECW_LIKELY(wk.ln == 1)) vpend = true, v_arc = wk.lp, v_depth = 0;
+    if (ECW_LIKELY(wk.ln == 1)) vpend = true, v_arc = arc0, v_depth = 0;
     else if (!push_frame(wk.lp, wk.ln, 0)) return false;
+    if (ff) {                                         // the levels before the sink's: what they would have left behind
+        v_depth = mm.ff_d, tried = (uint32_t) mm.ff_d, c_len = mm.ff_clp;
+        ++mm.n_ff;
+    }
 
     while (nfr > 0 || vpend) {
         ecw_sync();
@@ -486,7 +521,11 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
         // the arc most likely to be tried next: the first one out of w (in flight during the gather and the alignment)
         pre_idx = 0xFFFFFFFFu;
         if (ECW_LIKELY(w_ln)) pre = ecw_arc_load(lv.arc, w_lp), pre_idx = w_lp;
-        {   // append the part of w's k-mer that lies beyond the overlap (syncerr.c:186-190).  With F the vertex's forward
+        if (ECW_LIKELY(m_live && depth < mm.depth)) {  // the bases are there (EcwMemo)
+            c_len += ext;
+            ++mm.n_reuse;
+        } else {
+            // append the part of w's k-mer that lies beyond the overlap (syncerr.c:186-190).  With F the vertex's forward
             // string, base t of the extension is F[ls + t] for a forward w and comp(F[K - ls - 1 - t]) for a reverse one; F itself is
             // the first occurrence's k-mer, reverse-complemented when that occurrence is reverse: two cases remain.
             const uint8_t *vs = rd.hoco_s + ((uint64_t) w_hs16 << 4);
@@ -505,8 +544,11 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
                 s.cs[wi] = x;
             }
             c_len += ext;
+            if (m_live && depth == mm.depth) ++mm.depth;
+            ecw_sync();
         }
-        ecw_sync();
+        if (depth == 0) cl0 = c_len;
+        if (ff_walk && w == wk.end_utg && depth > 0) mm.ff_end = wk.end_utg, mm.ff_d = depth, mm.ff_arc = a, mm.ff_cl0 = cl0, mm.ff_clp = c_len - ext;
         // A vertex on an unbranched stretch that cannot be the end of the path needs no alignment of its own.  wf_ed_core RESUMES: run on the
         // consensus up to w and then on the consensus up to w's successor, it leaves the wavefront (and score, ends) that a single run on the longer
         // consensus leaves -- extending a diagonal in two goes or in one is the same run of matches, and a step that ends early stores nothing
@@ -519,6 +561,7 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
             vpend = true, v_arc = w_lp, v_depth = depth + 1;
             continue;
         }
+        ff_walk = false;
         // wf_ed_core (levdist.c:265-310)
         for (;;) {
             ++wf_steps, wf_diag += (uint64_t) wv.n;
@@ -619,6 +662,8 @@ struct EcwArgs {
     int32_t skip_l;               // blocks longer than this were routed to a larger tier before the launch (ec_route_kernel): not this launch's business
     int32_t batch;                // blocks taken from the queue per atomic: ECW_BATCH where the blocks are millions and small, 1 where they are few and long
     int32_t arc_budget;           // first tier: arcs after which a block is left to the classes behind it (0: never)
+    int32_t memo;                 // EcwMemo::mode
+    unsigned long long *memo_stat; // OATK_DEBUG_EC_STAGES: [0] levels reused, [1] blocks started at their sink, added once per wave (null: not counted)
     // oatk_hip_ec_keep_seq (the KEEP instantiations of the solver kernels; null otherwise): what a corrected read's sequence needs of a block besides its path
     uint32_t *seq_qend;           // [n_work] q_end of the optimum alignment = bases of the optimum consensus that replace the block (syncerr.c:247-248); 0 = not replaced
     uint32_t *seq_slots;          // the optimum consensus itself, sixteen bases to a word as the solver holds it: block i at word seq_slot_off[i]
@@ -662,6 +707,16 @@ __global__ void ec_route_keys_kernel(const EcWork *work, const uint32_t *list, u
 {
     const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) keys[i] = ~(uint32_t) work[list[i]].l;
+}
+// a queue in source order: the source's first live arc (one per source that has an arc), then the low eb bits of the sink (EC_NONE, an open block: of end_max)
+__global__ void ec_queue_keys_kernel(const EcWork *work, const uint32_t *list, uint64_t n, uint32_t lp_max, uint64_t end_max, int eb, uint32_t *keys)
+{
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const EcWork *w = work + (list? list[i] : i);
+    const uint32_t lp = w->lp < lp_max? w->lp : lp_max;
+    const uint64_t en = w->end_utg < end_max? w->end_utg : end_max;
+    keys[i] = (uint32_t) ((uint64_t) lp << eb | (en & ((1ULL << eb) - 1ULL)));
 }
 // ... and how many of them are longer than `cap` (in a list sorted longest first: the head of the list)
 __global__ void ec_route_longer_kernel(const EcWork *work, const uint32_t *list, uint64_t n, int32_t cap, unsigned long long *cnt)
@@ -751,11 +806,14 @@ __global__ __launch_bounds__(64 * WPB) void ec_wave_kernel(EcwArgs a)
     s.frames = (uint8_t *) p;
     const uint64_t total = a.todo? a.n_todo : a.n_work;
     uint64_t pool_at = 0, pool_end = 0;                // this wave's chunk of the path pool
+    EcwMemo mm;
+    mm.mode = a.memo, mm.n_reuse = mm.n_ff = 0;
     for (;;) {
         unsigned long long t0 = 0;
         if (lane == 0) t0 = atomicAdd(a.next, (unsigned long long) a.batch);
         t0 = ecw_uni64(t0);
         if (t0 >= total) break;
+        mm.reset();
         const int cnt = total - t0 < (uint64_t) a.batch? (int) (total - t0) : a.batch;
         // lane i holds block i of the batch
         uint64_t my_wi = 0;
@@ -781,7 +839,7 @@ __global__ __launch_bounds__(64 * WPB) void ec_wave_kernel(EcwArgs a)
                 o.short_block = 1;                     // syncerr.c:502-504
             } else {
                 uint32_t st = 0, np = 0, o_len = 0;
-                if (ECW_RARE(!ecw_solve_block<KEEP>(a.lv, a.rd, wk, s, a.max_edist, st, np, o.tried, o.n_path, o.wf_steps, o.wf_diag, o_len))) {
+                if (ECW_RARE(!ecw_solve_block<KEEP>(a.lv, a.rd, wk, s, a.max_edist, mm, st, np, o.tried, o.n_path, o.wf_steps, o.wf_diag, o_len))) {
                     o.flags = 1;
                     if (lane == 0) a.todo_out[atomicAdd(a.todo_cnt, 1ULL)] = (uint32_t) wi;
                 } else {
@@ -804,6 +862,10 @@ __global__ __launch_bounds__(64 * WPB) void ec_wave_kernel(EcwArgs a)
             if (lane == 0) a.out[wi] = o;
             ecw_sync();
         }
+    }
+    if (a.memo_stat && lane == 0 && (mm.n_reuse | mm.n_ff)) {
+        atomicAdd(a.memo_stat, (unsigned long long) mm.n_reuse);
+        atomicAdd(a.memo_stat + 1, (unsigned long long) mm.n_ff);
     }
 }
 
