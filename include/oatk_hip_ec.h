@@ -163,7 +163,8 @@ int oatk_hip_ec_reserve_import(oatk_hip_ctx *ctx, uint64_t bytes);
 
 enum {
     OATK_BUF_EG_IDX_P = 120, OATK_BUF_EG_IDX_N, OATK_BUF_EG_ARC_V, OATK_BUF_EG_ARC_W, OATK_BUF_EG_ARC_LS, OATK_BUF_EG_ARC_COV,
-    OATK_BUF_EG_ARC_COMP
+    OATK_BUF_EG_ARC_COMP,
+    OATK_BUF_EG_OTHER           /* u8[2 n_scm]  of a light graph: 1 where the oriented vertex has an arc to a syncmer below err_mer_c; 0 bytes without a light graph */
 };
 
 #ifdef __cplusplus

@@ -30,7 +30,7 @@ BUF.update({name: 140 + i for i, name in enumerate(["CONS_SEL", "CONS_SLOT", "CO
 BUF.update({name: 200 + i for i, name in enumerate(["RA_ALN_SID", "RA_ALN_OFF", "RA_ALN_S", "RA_FRG_UID", "RA_FRG_UBEG", "RA_FRG_UEND", "RA_FRG_SBEG", "RA_FRG_SEND", "RA_SKIPPED"])})
 BUF.update({name: 150 + i for i, name in enumerate(["OVL_KEY", "OVL_OFF", "OVL_DIST", "OVL_CNT", "OVL_TAIL"])})
 BUF.update({name: 120 + i for i, name in enumerate([
-    "EG_IDX_P", "EG_IDX_N", "EG_ARC_V", "EG_ARC_W", "EG_ARC_LS", "EG_ARC_COV", "EG_ARC_COMP"])})
+    "EG_IDX_P", "EG_IDX_N", "EG_ARC_V", "EG_ARC_W", "EG_ARC_LS", "EG_ARC_COV", "EG_ARC_COMP", "EG_OTHER"])})
 # include/oatk_hip_graph.h
 BUF.update({name: 180 + i for i, name in enumerate([
     "AG_SCM_DEL", "AG_VTX_SCM", "AG_VTX_COV", "AG_IDX_P", "AG_IDX_N", "AG_ARC_V", "AG_ARC_W", "AG_ARC_COV", "AG_ARC_COMP", "AG_ARC_LINK"])})

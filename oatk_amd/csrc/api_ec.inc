@@ -31,6 +31,7 @@ struct EcState {
     DevBuf g_keys, g_keys2, g_ukeys, g_counts, g_nruns, g_nout, g_nout64, g_outoff, g_akey, g_aval, g_skey, g_sval, g_comp, g_flags, g_huge;
     DevBuf g_dist, g_dist2, g_cnt64, g_runoff, g_runls;
     DevBuf g_big, g_keep, g_other, g_lkeys, g_ldist, g_val2, g_wgt2, g_runcov, g_head, g_hpos, g_iota, g_segk, g_segv;   // light graph / weighted segments
+    DevBuf g_cbits, g_wcnt, g_wpre, g_candid, g_gcnt, g_gpre;            // light graph on candidate ranks: one bit per vertex, candidates per word and in front of it, the inverse table; kept pairs per workgroup
     uint32_t light_c = 0;               // the resident graph is a light one built for this err_mer_c (0: the full graph)
     uint64_t g_n_vtx = 0, g_n_arc = 0;
     bool graph_resident = false;
@@ -62,7 +63,7 @@ static void ec_state_free(oatk_hip_ctx *ctx)
 static int ec_buffer(oatk_hip_ctx *ctx, int which, const void **d_ptr, uint64_t *bytes)
 {
     EcState *e = ctx->ec;
-    if (e && which >= OATK_BUF_EG_IDX_P && which <= OATK_BUF_EG_ARC_COMP) {
+    if (e && which >= OATK_BUF_EG_IDX_P && which <= OATK_BUF_EG_OTHER) {
         if (!e->graph_resident) { ctx->err = "EC graph requested before oatk_hip_ec_graph"; return OATK_E_STATE; }
         const uint64_t gv = e->g_n_vtx, ga = e->g_n_arc;
         switch (which) {
@@ -72,6 +73,7 @@ static int ec_buffer(oatk_hip_ctx *ctx, int which, const void **d_ptr, uint64_t 
             case OATK_BUF_EG_ARC_W: *d_ptr = e->arc_w.p, *bytes = ga * 8; break;
             case OATK_BUF_EG_ARC_LS: *d_ptr = e->arc_ls.p, *bytes = ga * 4; break;
             case OATK_BUF_EG_ARC_COV: *d_ptr = e->arc_cov.p, *bytes = ga * 4; break;
+            case OATK_BUF_EG_OTHER: *d_ptr = e->g_other.p, *bytes = e->light_c? 2 * gv : 0; break;
             default: *d_ptr = e->g_comp.p, *bytes = ga; break;
         }
         return OATK_OK;
@@ -403,7 +405,27 @@ extern "C" int oatk_hip_ec_pairs(oatk_hip_ctx *ctx, const void **d_keys, const v
 // make_syncmer_graph(sr_db, scm_db, 0, 0.) + the arc overlaps of scg_consensus(hoco) from a list of adjacent pairs (ecgraph.hpp).
 // The list is this batch's own (oatk_hip_ec_graph) or, with sharded reads, the lists of all shards in shard order.  Entries are single
 // pairs (d_dist) or weighted segments (d_val = distance | calls << 32: that many consecutive pairs of one key and one distance).
-static int ec_graph_build(oatk_hip_ctx *ctx, const uint64_t *d_keys, const uint32_t *d_dist, const uint64_t *d_val, uint64_t nocc, bool timer_running = false)
+// The light graph on candidate ranks (ec_light_packed) enters with its keys already packed: `pk` names them (d_keys is null).  They are sorted and
+// run-length encoded in that form, the distinct ones are written to g_ukeys as keys on vertex ids, and from there on nothing differs.
+struct EgrPacked { void *keys; uint32_t B; bool wide; const uint32_t *cand_id; };      // keys: uint32_t, or uint64_t when wide; ra << B | rb (ecgraph.hpp)
+
+template <class KeyT>
+static int ec_sort_packed(oatk_hip_ctx *ctx, EcState *e, const EgrPacked &pk, uint32_t *dist_in, uint64_t nocc)
+{
+    KeyT *in = (KeyT *) pk.keys, *sorted = e->g_keys2.as<KeyT>();
+    size_t tb = 0;              // stable, and from bit 0 (DESIGN.md 6: rocPRIM's small-input paths and ranges that start higher)
+    CK(rocprim::radix_sort_pairs(nullptr, tb, in, sorted, dist_in, e->g_dist2.as<uint32_t>(), nocc, 0, 2 * pk.B, ctx->stream));
+    ENSURE(tmp, tb);
+    CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, in, sorted, dist_in, e->g_dist2.as<uint32_t>(), nocc, 0, 2 * pk.B, ctx->stream));
+    tb = 0;                     // the distinct keys go where the unsorted ones were
+    CK(rocprim::run_length_encode(nullptr, tb, sorted, (unsigned int) nocc, in, e->g_counts.as<uint32_t>(), e->g_nruns.as<uint32_t>(), ctx->stream));
+    ENSURE(tmp, tb);
+    CK(rocprim::run_length_encode(ctx->tmp.p, tb, sorted, (unsigned int) nocc, in, e->g_counts.as<uint32_t>(), e->g_nruns.as<uint32_t>(), ctx->stream));
+    return OATK_OK;
+}
+
+static int ec_graph_build(oatk_hip_ctx *ctx, const uint64_t *d_keys, const uint32_t *d_dist, const uint64_t *d_val, uint64_t nocc, bool timer_running = false,
+                          const EgrPacked *pk = nullptr)
 {
     using namespace oatk;
     if (!ctx) return OATK_E_NODEV;
@@ -438,20 +460,29 @@ static int ec_graph_build(oatk_hip_ctx *ctx, const uint64_t *d_keys, const uint3
             ENSURE(tmp, tb);
             CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, keys_in, e->g_keys2.as<uint64_t>(), val_in, e->g_val2.as<uint64_t>(), nocc, 0, 64, ctx->stream));
             hipLaunchKernelGGL(egr_seg_split_kernel, blocks(nocc), dim3(256), 0, ctx->stream, nocc, e->g_val2.as<uint64_t>(), e->g_dist2.as<uint32_t>(), e->g_wgt2.as<uint32_t>());
+        } else if (pk) {
+            int rc = pk->wide? ec_sort_packed<uint64_t>(ctx, e, *pk, dist_in, nocc) : ec_sort_packed<uint32_t>(ctx, e, *pk, dist_in, nocc);
+            if (rc) return rc;
         } else {
             CK(rocprim::radix_sort_pairs(nullptr, tb, keys_in, e->g_keys2.as<uint64_t>(), dist_in, e->g_dist2.as<uint32_t>(), nocc, 0, 64, ctx->stream));
             ENSURE(tmp, tb);
             CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, keys_in, e->g_keys2.as<uint64_t>(), dist_in, e->g_dist2.as<uint32_t>(), nocc, 0, 64, ctx->stream));
         }
-        tb = 0;
-        CK(rocprim::run_length_encode(nullptr, tb, e->g_keys2.as<uint64_t>(), (unsigned int) nocc, e->g_ukeys.as<uint64_t>(), e->g_counts.as<uint32_t>(),
-                                      e->g_nruns.as<uint32_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::run_length_encode(ctx->tmp.p, tb, e->g_keys2.as<uint64_t>(), (unsigned int) nocc, e->g_ukeys.as<uint64_t>(), e->g_counts.as<uint32_t>(),
-                                      e->g_nruns.as<uint32_t>(), ctx->stream));
+        if (!pk) {
+            tb = 0;
+            CK(rocprim::run_length_encode(nullptr, tb, e->g_keys2.as<uint64_t>(), (unsigned int) nocc, e->g_ukeys.as<uint64_t>(), e->g_counts.as<uint32_t>(),
+                                          e->g_nruns.as<uint32_t>(), ctx->stream));
+            ENSURE(tmp, tb);
+            CK(rocprim::run_length_encode(ctx->tmp.p, tb, e->g_keys2.as<uint64_t>(), (unsigned int) nocc, e->g_ukeys.as<uint64_t>(), e->g_counts.as<uint32_t>(),
+                                          e->g_nruns.as<uint32_t>(), ctx->stream));
+        }
         uint32_t n_runs = 0;
         CK(hipMemcpyAsync(&n_runs, e->g_nruns.p, 4, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
+        if (pk && n_runs) {
+            if (pk->wide) hipLaunchKernelGGL(egr_unpack_keys_kernel<uint64_t>, blocks(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, (const uint64_t *) pk->keys, pk->B, pk->cand_id, e->g_ukeys.as<uint64_t>());
+            else hipLaunchKernelGGL(egr_unpack_keys_kernel<uint32_t>, blocks(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, (const uint32_t *) pk->keys, pk->B, pk->cand_id, e->g_ukeys.as<uint64_t>());
+        }
         // 2. every distinct key becomes an arc and (unless it is its own) the complementary arc, syncasm.c:264-282
         EENSURE(g_nout, ((uint64_t) n_runs + 1) * 4);
         hipLaunchKernelGGL(egr_expand_count_kernel, blocks(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, e->g_ukeys.as<uint64_t>(), e->g_nout.as<uint32_t>());
@@ -547,7 +578,8 @@ static int ec_select(oatk_hip_ctx *ctx, EcState *e, const T *in, const uint8_t *
 }
 
 // the pairs a light graph is made of (ecgraph.hpp, egr_pair_light_wave_kernel): both ends seen at least `c` times; the others leave their mark
-// in g_other, one byte per oriented vertex
+// in g_other, one byte per oriented vertex.  Keys of 64 bits on vertex ids: what the sharded round exchanges (api_multi.inc), and the light graph of a single
+// handle under OATK_DEBUG_EC_LIGHT_PACKED=0; otherwise that one takes ec_light_packed below
 static int ec_light_pairs(oatk_hip_ctx *ctx, uint32_t c, const uint64_t **d_keys, const uint32_t **d_dist, uint64_t *n_keep)
 {
     using namespace oatk;
@@ -582,25 +614,6 @@ static int ec_light_pairs(oatk_hip_ctx *ctx, uint32_t c, const uint64_t **d_keys
     (void) rc;
     CK(hipGetLastError());
     *d_keys = e->g_lkeys.as<uint64_t>(), *d_dist = e->g_ldist.as<uint32_t>(), *n_keep = nk;
-    return OATK_OK;
-}
-
-// The graph read_error_correction needs and no more (include/oatk_hip_ec.h): arcs between syncmers seen at least err_mer_c times, plus one
-// flag per oriented vertex for "has arcs to rarer syncmers".  oatk_hip_ec_mark / oatk_hip_ec accept it for err_arc_c >= err_mer_c >= this c.
-extern "C" int oatk_hip_ec_graph_light(oatk_hip_ctx *ctx, uint32_t err_mer_c)
-{
-    if (!ctx) return OATK_E_NODEV;
-    if (!ctx->counted) { ctx->err = "oatk_hip_ec_graph_light needs a resident scan + count"; return OATK_E_STATE; }
-    CK(hipSetDevice(ctx->device));
-    if (!ctx->ec) ctx->ec = new EcState();
-    if (err_mer_c == 0) return oatk_hip_ec_graph(ctx);
-    const uint64_t *k = nullptr;
-    const uint32_t *d = nullptr;
-    uint64_t n = 0;
-    int rc = ec_light_pairs(ctx, err_mer_c, &k, &d, &n);
-    if (rc) return rc;
-    if ((rc = ec_graph_build(ctx, k, d, nullptr, n, true)) != OATK_OK) return rc;
-    ctx->ec->light_c = err_mer_c;
     return OATK_OK;
 }
 
@@ -745,6 +758,9 @@ struct EcKnobs {
     bool queue_sort = true;       // OATK_DEBUG_EC_QUEUE_SORT=0: the wave solver's queues in read order (A/B, tests)
     bool list_walk = false;       // OATK_DEBUG_EC_LIST_WALK=1: the blocks listed by a second walk behind the scan (ec_count_blocks_wave_kernel, ec_list_blocks_wave_kernel) instead of from the
                                   // descriptors the one walk stages (ec_stage_blocks_wave_kernel, ec_fill_work_kernel) (A/B, tests)
+    bool light_packed = true;     // OATK_DEBUG_EC_LIGHT_PACKED=0: the light graph's pairs sorted as 64-bit keys on vertex ids (ec_light_pairs), not on candidate ranks (A/B, tests)
+    bool light_pairs = true;      // OATK_DEBUG_EC_LIGHT_PAIRS=0: in front of the sort on ranks, the pairs by a wave per read, a scan and a compaction instead of a lane per entry (A/B, tests)
+    bool light_wide = false;      // OATK_DEBUG_EC_LIGHT_KEYBITS=64: packed keys of 64 bits whatever the number of candidates (tests: the form large candidate sets take)
 };
 static EcKnobs ec_knobs_read()
 {
@@ -761,8 +777,116 @@ static EcKnobs ec_knobs_read()
     { const char *e = getenv("OATK_DEBUG_EC_LIST_WALK"); k.list_walk = e && e[0] == '1'; }
     { const char *e = getenv("OATK_DEBUG_EC_MEMO"); k.memo = e && (e[0] == '0' || e[0] == '1') && !e[1]? e[0] - '0' : 2; }
     { const char *e = getenv("OATK_DEBUG_EC_QUEUE_SORT"); k.queue_sort = !(e && e[0] == '0' && !e[1]); }
+    { const char *e = getenv("OATK_DEBUG_EC_LIGHT_PACKED"); k.light_packed = !(e && e[0] == '0' && !e[1]); }
+    { const char *e = getenv("OATK_DEBUG_EC_LIGHT_PAIRS"); k.light_pairs = !(e && e[0] == '0' && !e[1]); }
+    { const char *e = getenv("OATK_DEBUG_EC_LIGHT_KEYBITS"); k.light_wide = e && !strcmp(e, "64"); }
     return k;
 }
+
+static int ec_scan_u32(oatk_hip_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n)
+{
+    size_t tb = 0;
+    CK(rocprim::exclusive_scan(nullptr, tb, in, out, 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
+    ENSURE(tmp, tb);
+    CK(rocprim::exclusive_scan(ctx->tmp.p, tb, in, out, 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
+    return OATK_OK;
+}
+
+// The light graph of a handle in local ids, on candidate ranks (ecgraph.hpp): the rank table, the kept pairs with packed keys -- by a lane per chain entry in
+// two passes, or (pairs_old) by the three kernels of ec_light_pairs with the packing in the compaction -- and ec_graph_build's entry for packed keys.
+// One wait on the host brings the number of candidates and of kept pairs; pairs_old has a second one, because its compaction needs the key width first.
+static int ec_light_packed(oatk_hip_ctx *ctx, uint32_t c, bool pairs_old, bool force_wide)
+{
+    using namespace oatk;
+    EcState *e = ctx->ec;
+    const uint64_t nv = ec_n_vtx(ctx), nr = ctx->n_reads, n = ctx->n_occ, nw = (nv + 63) / 64, nwg = (nr + 255) / 256;
+    if (n >= 0xFFFFFFFFULL) { ctx->err = "more than 2^32 adjacent pairs"; return OATK_E_ARG; }
+    if (nv >= 0x7FFFFFFFULL) { ctx->err = "too many syncmers for 32-bit oriented vertex ids"; return OATK_E_ARG; }
+    auto blocks = [](uint64_t x) { return dim3((unsigned) ((x + 255) / 256 > 0? (x + 255) / 256 : 1)); };
+    EENSURE(g_other, 2 * nv + 8); EENSURE(g_cbits, (nw + 1) * 8); EENSURE(g_wcnt, (nw + 1) * 4); EENSURE(g_wpre, (nw + 1) * 4);
+    EENSURE(g_gcnt, (nwg + 1) * 4); EENSURE(g_gpre, (nwg + 1) * 4); EENSURE(g_nruns, 64);
+    t_begin(ctx, OATK_T_EC_GRAPH);
+    CK(hipMemsetAsync(e->g_other.p, 0, 2 * nv + 8, ctx->stream));
+    uint32_t n_cand = 0, nk32 = 0;
+    uint64_t nk = 0;
+    EgrPacked pk = {nullptr, 1, force_wide, nullptr};
+    int rc;
+    if (n && nv) {
+        const uint64_t *bits = e->g_cbits.as<uint64_t>();
+        const uint32_t *wpre = e->g_wpre.as<uint32_t>();
+        const uint64_t *scm_off = ctx->scm_off.as<uint64_t>(), *chains = ec_chains(ctx);
+        const uint32_t *mpos = ctx->pos_mpos.as<uint32_t>();
+        hipLaunchKernelGGL(egr_cand_flag_kernel, blocks(nv), dim3(256), 0, ctx->stream, nv, nw, ctx->scm_cov.as<uint32_t>(), c, e->g_cbits.as<uint64_t>(), e->g_wcnt.as<uint32_t>());
+        if ((rc = ec_scan_u32(ctx, e->g_wcnt.as<uint32_t>(), e->g_wpre.as<uint32_t>(), nw + 1)) != OATK_OK) return rc;
+        CK(hipMemcpyAsync(&n_cand, e->g_wpre.as<uint32_t>() + nw, 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (pairs_old) {
+            EENSURE(g_keys, (n + 1) * 8); EENSURE(g_dist, (n + 1) * 4); EENSURE(g_keep, n + 8); EENSURE(g_keys2, (n + 1) * 8);
+            hipLaunchKernelGGL(egr_pair_light_wave_kernel, dim3((unsigned) ((nr + 3) / 4)), dim3(256), 0, ctx->stream, nr, scm_off, chains, mpos, ctx->scm_cov.as<uint32_t>(), c,
+                               e->g_keys.as<uint64_t>(), e->g_dist.as<uint32_t>(), e->g_keep.as<uint8_t>(), e->g_other.as<uint8_t>());
+            auto flags = rocprim::make_transform_iterator(e->g_keep.as<uint8_t>(), [] __device__(uint8_t f) -> uint32_t { return f; });
+            size_t tb = 0;
+            CK(rocprim::exclusive_scan(nullptr, tb, flags, e->g_keys2.as<uint32_t>(), 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
+            ENSURE(tmp, tb);
+            CK(rocprim::exclusive_scan(ctx->tmp.p, tb, flags, e->g_keys2.as<uint32_t>(), 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
+        } else {
+            hipLaunchKernelGGL((egr_pair_entry_kernel<uint32_t, false>), dim3((unsigned) nwg), dim3(256), 0, ctx->stream, nr, scm_off, chains, mpos, bits, wpre, 0u,
+                               e->g_gcnt.as<uint32_t>(), (const uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint8_t *) nullptr);
+            if ((rc = ec_scan_u32(ctx, e->g_gcnt.as<uint32_t>(), e->g_gpre.as<uint32_t>(), nwg + 1)) != OATK_OK) return rc;
+            CK(hipMemcpyAsync(&nk32, e->g_gpre.as<uint32_t>() + nwg, 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        CK(hipStreamSynchronize(ctx->stream));
+        // B = the bits of the largest oriented rank, 2 n_cand - 1; n_cand <= nv < 2^31 keeps a key within 64 bits, and the test stays all the same
+        while ((1ULL << pk.B) < 2 * (uint64_t) n_cand) ++pk.B;
+        if (2 * pk.B > 64) { ctx->err = "light EC graph: a pair of candidate ranks does not fit a 64-bit key"; return OATK_E_ARG; }
+        pk.wide = force_wide || 2 * pk.B > 32;
+        const uint64_t cap = pairs_old? n : (uint64_t) nk32;
+        EENSURE(g_lkeys, (cap + 1) * (pk.wide? 8 : 4)); EENSURE(g_ldist, (cap + 1) * 4); EENSURE(g_candid, ((uint64_t) n_cand + 1) * 4);
+        pk.keys = e->g_lkeys.p, pk.cand_id = e->g_candid.as<uint32_t>();
+        if (n_cand) hipLaunchKernelGGL(egr_cand_id_kernel, blocks(nv), dim3(256), 0, ctx->stream, nv, bits, wpre, e->g_candid.as<uint32_t>());
+        if (pairs_old) {
+            uint64_t *d_cnt = e->g_nruns.as<uint64_t>() + 2;
+            if (pk.wide) hipLaunchKernelGGL(egr_compact_pack_kernel<uint64_t>, blocks(n), dim3(256), 0, ctx->stream, n, e->g_keep.as<uint8_t>(), e->g_keys2.as<uint32_t>(), e->g_keys.as<uint64_t>(),
+                                            e->g_dist.as<uint32_t>(), bits, wpre, pk.B, e->g_lkeys.as<uint64_t>(), e->g_ldist.as<uint32_t>(), d_cnt);
+            else hipLaunchKernelGGL(egr_compact_pack_kernel<uint32_t>, blocks(n), dim3(256), 0, ctx->stream, n, e->g_keep.as<uint8_t>(), e->g_keys2.as<uint32_t>(), e->g_keys.as<uint64_t>(),
+                                    e->g_dist.as<uint32_t>(), bits, wpre, pk.B, e->g_lkeys.as<uint32_t>(), e->g_ldist.as<uint32_t>(), d_cnt);
+            CK(hipMemcpyAsync(&nk, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+            CK(hipStreamSynchronize(ctx->stream));
+        } else {
+            nk = nk32;
+            if (pk.wide) hipLaunchKernelGGL((egr_pair_entry_kernel<uint64_t, true>), dim3((unsigned) nwg), dim3(256), 0, ctx->stream, nr, scm_off, chains, mpos, bits, wpre, pk.B,
+                                            (uint32_t *) nullptr, (const uint32_t *) e->g_gpre.as<uint32_t>(), e->g_lkeys.as<uint64_t>(), e->g_ldist.as<uint32_t>(), e->g_other.as<uint8_t>());
+            else hipLaunchKernelGGL((egr_pair_entry_kernel<uint32_t, true>), dim3((unsigned) nwg), dim3(256), 0, ctx->stream, nr, scm_off, chains, mpos, bits, wpre, pk.B,
+                                    (uint32_t *) nullptr, (const uint32_t *) e->g_gpre.as<uint32_t>(), e->g_lkeys.as<uint32_t>(), e->g_ldist.as<uint32_t>(), e->g_other.as<uint8_t>());
+        }
+        CK(hipGetLastError());
+    }
+    return ec_graph_build(ctx, nullptr, e->g_ldist.as<uint32_t>(), nullptr, nk, true, &pk);
+}
+
+// The graph read_error_correction needs and no more (include/oatk_hip_ec.h): arcs between syncmers seen at least err_mer_c times, plus one
+// flag per oriented vertex for "has arcs to rarer syncmers".  oatk_hip_ec_mark / oatk_hip_ec accept it for err_arc_c >= err_mer_c >= this c.
+extern "C" int oatk_hip_ec_graph_light(oatk_hip_ctx *ctx, uint32_t err_mer_c)
+{
+    if (!ctx) return OATK_E_NODEV;
+    if (!ctx->counted) { ctx->err = "oatk_hip_ec_graph_light needs a resident scan + count"; return OATK_E_STATE; }
+    CK(hipSetDevice(ctx->device));
+    if (!ctx->ec) ctx->ec = new EcState();
+    if (err_mer_c == 0) return oatk_hip_ec_graph(ctx);
+    const uint64_t *k = nullptr;
+    const uint32_t *d = nullptr;
+    uint64_t n = 0;
+    const EcKnobs kn = ec_knobs_read();
+    int rc;
+    if (kn.light_packed && !ctx->ec->global) {           // (a handle in global ids: the sharded round's pairs, 64-bit keys on global ids)
+        if ((rc = ec_light_packed(ctx, err_mer_c, !kn.light_pairs, kn.light_wide)) != OATK_OK) return rc;
+    } else {
+        if ((rc = ec_light_pairs(ctx, err_mer_c, &k, &d, &n)) != OATK_OK) return rc;
+        if ((rc = ec_graph_build(ctx, k, d, nullptr, n, true)) != OATK_OK) return rc;
+    }
+    ctx->ec->light_c = err_mer_c;
+    return OATK_OK;
+}
+
 
 namespace oatk {
 

@@ -5,6 +5,9 @@
 //   make_syncmer_graph(sr_db, scm_db, 0, 0.)   syncasm.c:203-299  -> egr_pair_keys_kernel, one 64-bit radix sort, a run-length
 //                                                                    encode (= the khashl arc counter :242-261), egr_expand /
 //                                                                    egr_unpack kernels, a second sort into (v, w) order
+//                                                                    (the light graph of a handle in local ids: egr_pair_entry_kernel, packed
+//                                                                    keys on candidate ranks and a radix sort over their 2 B bits, the
+//                                                                    distinct keys back on vertex ids by egr_unpack_keys_kernel; below)
 //   asmg_arc_index / asmg_arc_fix_symm          graph.c:85-113, :205-233 -> egr_unpack_kernel (+ the self-complement flag flip)
 //   arc overlaps of scg_consensus(hoco)         syncasm.c:793-812, calc_syncmer_overlap :477-582 -> egr_mode_kernel: the distance
 //                                                                    of every adjacent pair rides through the key sort, so a run
@@ -50,7 +53,10 @@ __global__ void egr_pair_keys_kernel(uint64_t n_reads, const uint64_t *scm_off, 
 // (b[k] = 0 rather than -1, :699-706) and (b) whether it is "good" -- which it cannot be when err_arc_c >= err_mer_c, because an arc is seen at
 // most as often as its rarer end.  So pairs with an end below `c` do not go through the sorts at all: they leave one flag per oriented
 // candidate vertex (`other`), and only pairs between two candidates become arcs.  keep[i] = 1 for those.
-// Pair keys and the split are made in one pass, a wave per read (lane j holds entry j of the chain and its left neighbour's comes by a lane
+// A handle in local ids takes the route on CANDIDATE RANKS at the end of this file (egr_cand_flag_kernel, egr_pair_entry_kernel: packed keys from a lane per
+// chain entry, a sort over 2 B bits).  The kernel below serves handles in global ids (the sharded round, api_multi.inc, exchanges 64-bit keys on global ids)
+// and the switches OATK_DEBUG_EC_LIGHT_PACKED=0 / OATK_DEBUG_EC_LIGHT_PAIRS=0:
+// pair keys and the split are made in one pass, a wave per read (lane j holds entry j of the chain and its left neighbour's comes by a lane
 // shift; reads with more than 64 syncmers are walked by lane 0): a lane-per-read key kernel that strides through the chains plus a pass over its
 // output took 2.4 ms at 2 M reads, this takes 0.85.
 __global__ __launch_bounds__(256) void egr_pair_light_wave_kernel(uint64_t n_reads, const uint64_t *scm_off, const uint64_t *k_mer, const uint32_t *m_pos, const uint32_t *cov,
@@ -517,6 +523,148 @@ __global__ void egr_compact_pairs_kernel(uint64_t n, const uint8_t *keep, const 
     const uint32_t k = keep[i], p = pos[i];
     if (k) lkeys[p] = keys[i], ldist[p] = dist[i];
     if (i == n - 1) *n_out = (uint64_t) p + k;
+}
+
+// ---- the light graph on CANDIDATE RANKS (api_ec.inc, ec_light_packed; a handle in local ids) ----
+// Only vertices with cov >= c can appear in a kept pair, a few thousand of twelve million at config 3.  Numbered densely in id order -- the rank
+// is monotone in the id, so the canonical choice v0 <= v1 ? (v0, v1) : (v1 ^ 1, v0 ^ 1) and the order of two keys are the same on oriented ranks
+// rank << 1 | strand as on oriented ids -- a key is ra << B | rb with B = bits of 2 n_cand - 1: 28 bits there instead of 64, four onesweep
+// passes over 32-bit keys instead of eight over 64-bit keys.
+// The table is one BIT per vertex plus the number of candidates in front of every 64-bit word: rank(v) = wpre[v >> 6] + popcount(the bits below v).
+// At 12 M vertices that is 1.5 MB + 0.75 MB, which stays in cache under the two passes below, where a rank (or coverage) word per vertex is 48 MB
+// that every chain entry looks up at a random place.
+__global__ __launch_bounds__(256) void egr_cand_flag_kernel(uint64_t nv, uint64_t nw, const uint32_t *cov, uint32_t c, uint64_t *bits, uint32_t *wcnt)
+{
+    const uint64_t v = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+    const uint64_t m = __ballot(v < nv && cov[v < nv? v : 0] >= c);
+    if ((threadIdx.x & 63) == 0 && (v >> 6) < nw) bits[v >> 6] = m, wcnt[v >> 6] = (uint32_t) __builtin_popcountll(m);
+    if (v == 0) wcnt[nw] = 0;                                              // the scan's last entry is the total
+}
+__device__ __forceinline__ bool egr_is_cand(const uint64_t *bits, uint64_t v) { return (bits[v >> 6] >> (v & 63)) & 1ULL; }
+__device__ __forceinline__ uint32_t egr_rank(const uint64_t *bits, const uint32_t *wpre, uint64_t v)      // of a candidate
+{
+    return wpre[v >> 6] + (uint32_t) __builtin_popcountll(bits[v >> 6] & ((1ULL << (v & 63)) - 1ULL));
+}
+// oriented vertex ids v0, v1 of two candidates adjacent on a read -> the canonical key on oriented ranks
+__device__ __forceinline__ uint64_t egr_packed_key(const uint64_t *bits, const uint32_t *wpre, uint32_t B, uint64_t v0, uint64_t v1)
+{
+    const uint64_t o0 = (uint64_t) egr_rank(bits, wpre, v0 >> 1) << 1 | (v0 & 1ULL), o1 = (uint64_t) egr_rank(bits, wpre, v1 >> 1) << 1 | (v1 & 1ULL);
+    return v0 <= v1? o0 << B | o1 : (o1 ^ 1ULL) << B | (o0 ^ 1ULL);
+}
+// the inverse table: cand_id[rank] = vertex
+__global__ __launch_bounds__(256) void egr_cand_id_kernel(uint64_t nv, const uint64_t *bits, const uint32_t *wpre, uint32_t *cand_id)
+{
+    const uint64_t v = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+    if (v < nv && egr_is_cand(bits, v)) cand_id[egr_rank(bits, wpre, v)] = (uint32_t) v;
+}
+
+// The pairs in one pass per ENTRY: entry j of the chains makes the pair (j - 1, j) unless it is the first entry of its read.  That comes from
+// scm_off and not from an ordinal stored with the entry (pos_lo is a k-mer word, not a slot number; scm_off is what every caller of the light
+// graph has for the chains in use): a workgroup takes 256 reads, their 257 offsets sit in LDS and a lane finds its entry's read by bisection, as
+// ec_fill_work_kernel does.  Reads with no syncmer repeat an offset and reads with one have only a first entry, so neither makes a pair, and a
+// read of any length is covered by as many lanes as it has entries.  The left neighbour's words are loaded again: the lane beside has them.
+// WRITE = false counts the workgroup's kept pairs (gcnt[blockIdx.x]; a scan over the n_reads / 256 counts follows); WRITE = true makes the same
+// pairs again and writes packed key and distance at their final places, in (read, slot) order, and the flags of `other` as
+// egr_pair_light_wave_kernel does.  Nothing per entry is stored in between: the old route wrote 13 bytes for every entry and read them twice.
+#define EGR_PAIR_ROWS 4
+template <class KeyT, bool WRITE>
+__global__ __launch_bounds__(256) void egr_pair_entry_kernel(uint64_t n_reads, const uint64_t *scm_off, const uint64_t *k_mer, const uint32_t *m_pos, const uint64_t *bits,
+                                                             const uint32_t *wpre, uint32_t B, uint32_t *gcnt, const uint32_t *gpre, KeyT *lkeys, uint32_t *ldist, uint8_t *other)
+{
+    __shared__ uint64_t offs[257];
+    __shared__ uint32_t wsum[EGR_PAIR_ROWS][4];
+    const uint64_t r0 = (uint64_t) blockIdx.x * 256;
+    for (uint32_t t = threadIdx.x; t < 257; t += 256) offs[t] = scm_off[r0 + t < n_reads? r0 + t : n_reads];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t j1 = offs[256];
+    uint32_t base = WRITE? gpre[blockIdx.x] : 0u;
+    // A trip takes EGR_PAIR_ROWS rows of 256 entries, a lane one entry of each, and every stage runs over the rows before the next one starts, so that a lane has
+    // the loads of four entries in flight and a trip has one pair of barriers.  It bought little: with one entry per lane and trip the passes took 0.26 and 0.69 ms
+    // at config 3, with four 0.27 and 0.64, and the `ec_graph` timer is not apart by the rule (2.125 -> 2.076 ms, profiles/r18a_ab_bench.txt) -- the passes do not
+    // wait on that chain of loads.  The same trips for every lane: the workgroup meets at the barriers.
+    for (uint64_t jb = offs[0]; jb < j1; jb += 256 * EGR_PAIR_ROWS) {
+        bool has[EGR_PAIR_ROWS], keep[EGR_PAIR_ROWS];
+        uint64_t v0[EGR_PAIR_ROWS], v1[EGR_PAIR_ROWS], w0[EGR_PAIR_ROWS], w1[EGR_PAIR_ROWS], bal[EGR_PAIR_ROWS];
+        uint32_t d[EGR_PAIR_ROWS], p0[EGR_PAIR_ROWS], p1[EGR_PAIR_ROWS];
+#pragma unroll
+        for (int q = 0; q < EGR_PAIR_ROWS; ++q) {
+            const uint64_t j = jb + (uint64_t) q * 256 + threadIdx.x;
+            has[q] = false;
+            if (j < j1) {
+                uint32_t lo = 0, hi = 256;                                 // the last read with offs[.] <= j: the one entry j belongs to
+                while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (offs[mid] <= j) lo = mid; else hi = mid; }
+                has[q] = offs[lo] != j;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < EGR_PAIR_ROWS; ++q) {                           // (a lane without a pair loads entry 0, which exists, and drops it)
+            const uint64_t j = has[q]? jb + (uint64_t) q * 256 + threadIdx.x : 0, jm = has[q]? j - 1 : 0;
+            const uint32_t m0 = m_pos[jm], m1 = m_pos[j];
+            v0[q] = (k_mer[jm] >> 1) << 1 | (m0 & 1u), v1[q] = (k_mer[j] >> 1) << 1 | (m1 & 1u);
+            d[q] = (m1 >> 1) - (m0 >> 1);
+        }
+#pragma unroll
+        for (int q = 0; q < EGR_PAIR_ROWS; ++q) {
+            w0[q] = bits[v0[q] >> 7], w1[q] = bits[v1[q] >> 7];            // vertex v >> 1, its word (v >> 1) >> 6
+            if (WRITE) p0[q] = wpre[v0[q] >> 7], p1[q] = wpre[v1[q] >> 7];
+        }
+#pragma unroll
+        for (int q = 0; q < EGR_PAIR_ROWS; ++q) {
+            const bool c0 = (w0[q] >> ((v0[q] >> 1) & 63)) & 1ULL, c1 = (w1[q] >> ((v1[q] >> 1) & 63)) & 1ULL;
+            keep[q] = has[q] && c0 && c1;
+            if (WRITE && has[q] && c0 != c1) {
+                const uint64_t a = v0[q] <= v1[q]? v0[q] : v1[q] ^ 1ULL, b = v0[q] <= v1[q]? v1[q] : v0[q] ^ 1ULL;      // the key stands for a -> b and (b ^ 1) -> (a ^ 1)
+                const bool ca = v0[q] <= v1[q]? c0 : c1;
+                other[ca? a : b ^ 1ULL] = 1;
+            }
+            bal[q] = __ballot(keep[q]);
+            if (lane == 0) wsum[q][wave] = (uint32_t) __builtin_popcountll(bal[q]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < EGR_PAIR_ROWS; ++q) {                           // rows in order, waves in order, lanes in order: (read, slot) order
+            uint32_t before = 0, tot = 0;
+            for (int w = 0; w < 4; ++w) { const uint32_t s = wsum[q][w]; before += w < wave? s : 0u; tot += s; }
+            if (WRITE && keep[q]) {
+                const uint32_t at = base + before + (uint32_t) __builtin_popcountll(bal[q] & ((1ULL << lane) - 1ULL));
+                const uint64_t o0 = (uint64_t) (p0[q] + (uint32_t) __builtin_popcountll(w0[q] & ((1ULL << ((v0[q] >> 1) & 63)) - 1ULL))) << 1 | (v0[q] & 1ULL);
+                const uint64_t o1 = (uint64_t) (p1[q] + (uint32_t) __builtin_popcountll(w1[q] & ((1ULL << ((v1[q] >> 1) & 63)) - 1ULL))) << 1 | (v1[q] & 1ULL);
+                lkeys[at] = (KeyT) (v0[q] <= v1[q]? o0 << B | o1 : (o1 ^ 1ULL) << B | (o0 ^ 1ULL)), ldist[at] = d[q];
+            }
+            base += tot;
+        }
+        __syncthreads();                                                   // wsum is written again
+    }
+    if (!WRITE && threadIdx.x == 0) {
+        gcnt[blockIdx.x] = base;
+        if (blockIdx.x == 0) gcnt[gridDim.x] = 0;                          // the scan's last entry is the total
+    }
+}
+
+// egr_compact_pairs_kernel with the keys packed on the way (the old three kernels in front of the sort on ranks, OATK_DEBUG_EC_LIGHT_PAIRS=0)
+template <class KeyT>
+__global__ void egr_compact_pack_kernel(uint64_t n, const uint8_t *keep, const uint32_t *pos, const uint64_t *keys, const uint32_t *dist, const uint64_t *bits,
+                                        const uint32_t *wpre, uint32_t B, KeyT *lkeys, uint32_t *ldist, uint64_t *n_out)
+{
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t k = keep[i], p = pos[i];
+    if (k) {
+        const uint64_t a = keys[i] >> 32, b = keys[i] & 0xFFFFFFFFULL;    // canonical already: a <= b
+        lkeys[p] = (KeyT) egr_packed_key(bits, wpre, B, a, b), ldist[p] = dist[i];
+    }
+    if (i == n - 1) *n_out = (uint64_t) p + k;
+}
+
+// the distinct packed keys back in the form the rest of the builder reads: a << 32 | b on oriented vertex ids
+template <class KeyT>
+__global__ void egr_unpack_keys_kernel(uint64_t n_keys, const KeyT *pkeys, uint32_t B, const uint32_t *cand_id, uint64_t *ukeys)
+{
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_keys) return;
+    const uint64_t k = pkeys[i], a = k >> B, b = k & ((1ULL << B) - 1ULL);
+    ukeys[i] = ((uint64_t) cand_id[a >> 1] << 1 | (a & 1ULL)) << 32 | ((uint64_t) cand_id[b >> 1] << 1 | (b & 1ULL));
 }
 
 }  // namespace oatk
