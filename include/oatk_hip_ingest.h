@@ -81,6 +81,28 @@ int oatk_hip_inflate_last_byte(oatk_hip_ctx *ctx);
  * memory owned by the context, valid until its next call. */
 int oatk_hip_ingest_names(oatk_hip_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const uint8_t **h_packed, const uint64_t **h_off, uint64_t *n_names);
 
+/* ---- unaligned BAM (PacBio's *.hifi_reads.bam) read on the device (oatk_amd/csrc/bam.hpp) ----
+ * d_bam: n_bytes of the INFLATED stream (BAM is a BGZF container: oatk_hip_inflate_bgzf above), at any byte alignment.  header = 1: the bytes begin with the BAM
+ * header ("BAM\1", text, reference list), which is walked on the host over a copy of the chunk's head; a wrong magic or a negative length is OATK_E_ARG, a header
+ * that is not whole inside the chunk gives OATK_OK with *n_reads = 0 and *consumed = 0 when final = 0 (come back with more) and OATK_E_ARG when final = 1.
+ * The records are found on the device: every byte offset that passes the record check is a candidate, and the chain of records from the first byte behind the
+ * header is the set of candidates reachable from it -- found by pointer doubling, not by a walk (oatk_amd/csrc/bam.hpp).  The chain stops at the end of
+ * the chunk (all taken), inside a record (final = 0: *consumed is that record's offset, feed the rest again in front of the next chunk; final = 1: OATK_E_ARG,
+ * "BAM stream ends inside a record"), or at bytes that are no record (OATK_E_ARG with the offset).  *consumed counts from the chunk's first byte, header included.
+ * A record with flag & 0x910 (reverse-complemented, secondary, supplementary) is one samtools fasta would reverse or drop: the whole input is refused with
+ * OATK_E_SPLIT and the record named.  n_cigar_op need not be 0; quality and tags are never read; l_seq = 0 is a read of length 0.
+ * A read is its l_seq letters of "=ACMGRSVTWYHKDBN", what samtools fasta prints.  On success the packed stream is resident exactly as oatk_hip_ingest leaves it
+ * (OATK_BUF_INGEST_*; INGEST_HDR: the byte offset of each record's block_size), and oatk_hip_scan_ingested, oatk_hip_ingest_truncate and oatk_hip_ingest_names
+ * (a name: the bytes at INGEST_HDR + 36 up to the first NUL) work on it.  On any error nothing is resident. */
+int oatk_hip_ingest_bam(oatk_hip_ctx *ctx, const uint8_t *d_bam, uint64_t n_bytes, int header, int final, uint64_t *n_reads, uint64_t *consumed);
+/* the same from host memory (one hipMemcpy first, into the context's text buffer: that is the d_text oatk_hip_ingest_names wants afterwards) */
+int oatk_hip_ingest_bam_host(oatk_hip_ctx *ctx, const uint8_t *h_bam, uint64_t n_bytes, int header, int final, uint64_t *n_reads, uint64_t *consumed);
+/* candidates, records, header bytes of the latest oatk_hip_ingest_bam */
+int oatk_hip_ingest_bam_stats(oatk_hip_ctx *ctx, uint64_t out[3]);
+/* milliseconds of the phases of the latest oatk_hip_ingest_bam, if it ran with oatk_hip_set_timing on (zeros otherwise): candidate passes, successors + doubling
+ * rounds, compaction + stop, record kernel + offsets scan, unpack kernel (tests/bam_time.py) */
+int oatk_hip_ingest_bam_times(oatk_hip_ctx *ctx, float ms[5]);
+
 /* INGEST_SEQ u8[seq_bytes]  INGEST_OFF u64[n_reads]  INGEST_LEN u32[n_reads]  INGEST_HDR u64[n_reads] byte offset of each header line */
 enum { OATK_BUF_INGEST_SEQ = 160, OATK_BUF_INGEST_OFF, OATK_BUF_INGEST_LEN, OATK_BUF_INGEST_HDR };
 

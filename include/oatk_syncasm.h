@@ -154,7 +154,9 @@ void oatk_asmg_destroy(oatk_asmg_t *g);
 
 /* sstream_open + the sstream_read loop (sstream.c:70-103, syncmer.c:519-543) without kseq: the files (plain or gzip'ed FASTA / four-line
  * FASTQ, read one after the other) are inflated into host memory and their TEXT is handed to the device reader
- * (include/oatk_hip_ingest.h), which leaves the packed read stream resident: follow with oatk_hip_scan_ingested. */
+ * (include/oatk_hip_ingest.h), which leaves the packed read stream resident: follow with oatk_hip_scan_ingested.  A file whose inflated content
+ * begins with "BAM\1" is an unaligned BAM file and goes to oatk_hip_ingest_bam instead: exactly one such file per call (a BAM file among several
+ * files, or several BAM files: OATK_E_ARG). */
 int oatk_ingest_files(oatk_hip_ctx *ctx, char **files, int n_files, uint64_t *n_reads);
 
 /* sr_db_stat (syncmer.c:867): the two sorts and the tabulation on the device (include/oatk_hip_stat.h), the peak finder and the report

@@ -56,6 +56,7 @@ EXPORTS = [
     "oatk_hip_ra_triplet_scores", "oatk_hip_ra_triplet_scores_sharded",
     "oatk_hip_ec_keep_seq", "oatk_hip_ec_corrected_reads",
     "oatk_hip_inflate_bgzf", "oatk_hip_inflate_bgzf_host", "oatk_hip_inflate_last_byte", "oatk_hip_ingest_names",
+    "oatk_hip_ingest_bam", "oatk_hip_ingest_bam_host", "oatk_hip_ingest_bam_stats", "oatk_hip_ingest_bam_times",
 ]
 
 # the N-handle mirror in liboatk_host.so (include/oatk_multi.h) of entry points listed above; EXPORTS itself is checked against liboatk_hip.so
@@ -250,6 +251,10 @@ def load():
     L.oatk_hip_inflate_bgzf_host.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
     L.oatk_hip_inflate_last_byte.argtypes = [vp]
     L.oatk_hip_ingest_names.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.oatk_hip_ingest_bam.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.oatk_hip_ingest_bam_host.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.oatk_hip_ingest_bam_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.oatk_hip_ingest_bam_times.argtypes = [vp, C.POINTER(C.c_float)]
     L.oatk_hip_stat.argtypes = [vp, C.POINTER(StatRaw)]
     L.oatk_hip_stat_keys.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64), vp]
     L.oatk_hip_stat_from_keys.argtypes = [vp, vp, vp, C.c_uint64, vp, C.POINTER(StatRaw)]

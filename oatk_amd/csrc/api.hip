@@ -141,6 +141,7 @@ static void t_collect(oatk_hip_ctx *ctx, int first, int last)
 #include "api_ovl.inc"
 #include "api_align.inc"
 #include "api_ingest.inc"
+#include "api_bam.inc"
 #include "api_inflate.inc"
 #include "api_stat.inc"
 #include "api_multi.inc"

@@ -104,13 +104,15 @@ extern "C" int oatk_hip_ingest_names(oatk_hip_ctx *ctx, const uint8_t *d_text, u
     if (n) {
         const dim3 grid((unsigned) ((n + 1 + 255) / 256));
         FENSURE(name_len, (n + 1) * 8); FENSURE(name_off, (n + 1) * 8);
-        hipLaunchKernelGGL(ing_name_len_kernel, grid, dim3(256), 0, ctx->stream, d_text, n_bytes, ig->hdr_off.as<uint64_t>(), n, g->name_len.as<uint64_t>());
+        if (ig->bam) hipLaunchKernelGGL(ing_bam_name_len_kernel, grid, dim3(256), 0, ctx->stream, d_text, n_bytes, ig->hdr_off.as<uint64_t>(), n, g->name_len.as<uint64_t>());
+        else hipLaunchKernelGGL(ing_name_len_kernel, grid, dim3(256), 0, ctx->stream, d_text, n_bytes, ig->hdr_off.as<uint64_t>(), n, g->name_len.as<uint64_t>());
         { int rc = ing_scan_u64(ctx, g->name_len.as<uint64_t>(), g->name_off.as<uint64_t>(), n + 1); if (rc) return rc; }
         uint64_t total = 0;
         CK(hipMemcpyAsync(&total, g->name_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
         FENSURE(name_out, (n + 1) * 8 + total + 8);
-        hipLaunchKernelGGL(ing_name_copy_kernel, grid, dim3(256), 0, ctx->stream, d_text, ig->hdr_off.as<uint64_t>(), n, g->name_off.as<uint64_t>(), g->name_out.as<uint8_t>());
+        if (ig->bam) hipLaunchKernelGGL(ing_bam_name_copy_kernel, grid, dim3(256), 0, ctx->stream, d_text, ig->hdr_off.as<uint64_t>(), n, g->name_off.as<uint64_t>(), g->name_out.as<uint8_t>());
+        else hipLaunchKernelGGL(ing_name_copy_kernel, grid, dim3(256), 0, ctx->stream, d_text, ig->hdr_off.as<uint64_t>(), n, g->name_off.as<uint64_t>(), g->name_out.as<uint8_t>());
         CK(hipGetLastError());
         g->h_names.resize((size_t) ((n + 1) * 8 + total));
         CK(hipMemcpyAsync(g->h_names.data(), g->name_out.p, g->h_names.size(), hipMemcpyDeviceToHost, ctx->stream));

@@ -4,12 +4,19 @@
 
 struct IngState {
     DevBuf text, cnt, cnt64, blk_off, nl_pos, is_hdr, seq_len, hdr_rank, seq_before, hdr_line, len, padded, off, hdr_off, seq, flags, info;
+    DevBuf bam_cand, bam_jump, bam_jump2, bam_mark, bam_rank, bam_rec;      // the record chain of a BAM chunk (api_bam.inc)
     uint64_t n_reads = 0, seq_bytes = 0;
+    uint64_t bam_stats[3] = {0, 0, 0};      // candidates, records, header bytes of the latest oatk_hip_ingest_bam
+    hipEvent_t bam_ev[7];                   // phase marks of oatk_hip_ingest_bam, made when a call first runs with oatk_hip_set_timing on
+    bool bam_ev_made = false;
+    float bam_ms[5] = {0, 0, 0, 0, 0};      // candidate passes, successors + doubling, compaction + stop, record kernel + scan, unpack kernel
     bool done = false;
+    bool bam = false;             // the resident stream came from oatk_hip_ingest_bam: INGEST_HDR holds record offsets, and a name lies 36 bytes behind one
 };
 
 static void ing_state_free(oatk_hip_ctx *ctx)
 {
+    if (ctx->ing && ctx->ing->bam_ev_made) for (hipEvent_t e : ctx->ing->bam_ev) (void) hipEventDestroy(e);
     delete ctx->ing;          // (its buffers free themselves: ~DevBuf)
     ctx->ing = nullptr;
 }
@@ -49,7 +56,7 @@ extern "C" int oatk_hip_ingest(oatk_hip_ctx *ctx, const uint8_t *d_text, uint64_
     CK(hipSetDevice(ctx->device));
     if (!ctx->ing) ctx->ing = new IngState();
     IngState *g = ctx->ing;
-    g->done = false, g->n_reads = 0, g->seq_bytes = 0;
+    g->done = false, g->bam = false, g->n_reads = 0, g->seq_bytes = 0;
     if (n_reads) *n_reads = 0;
     if (consumed) *consumed = 0;
     auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };

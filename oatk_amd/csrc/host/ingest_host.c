@@ -208,12 +208,21 @@ static int ingest_files(oatk_hip_ctx *ctx, char **files, int n_files, uint64_t *
     int rc = OATK_OK;
     seg_t *seg = open_segments(files, n_files, &total, &rc, 0, 0);
     if (!seg) return rc;
+    /* an unaligned BAM file (a BGZF container: inflated above, its content begins with "BAM\1") is read by oatk_hip_ingest_bam -- one such file per call */
+    int i, n_bam = 0;
+    for (i = 0; i < n_files; ++i) n_bam += seg[i].mem && seg[i].size >= 4 && memcmp(seg[i].mem, "BAM\1", 4) == 0;
+    if (n_bam && n_files > 1) {
+        fprintf(stderr, "[E::%s] one BAM file per call: %d of the %d files are BAM\n", __func__, n_bam, n_files);
+        seg_close(seg, n_files);
+        return OATK_E_ARG;
+    }
+    if (n_bam) seg[0].add_nl = 0, total = seg[0].size;               /* binary: no newline behind it */
     uint8_t *d_text = 0;
     struct timespec t0, t1, t2;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     rc = upload_text(ctx, seg, n_files, total, &d_text);
     clock_gettime(CLOCK_MONOTONIC, &t1);
-    if (!rc) rc = oatk_hip_ingest(ctx, d_text, total, OATK_FMT_AUTO, 1, n_reads, &used);
+    if (!rc) rc = n_bam? oatk_hip_ingest_bam(ctx, d_text, total, 1, 1, n_reads, &used) : oatk_hip_ingest(ctx, d_text, total, OATK_FMT_AUTO, 1, n_reads, &used);
     clock_gettime(CLOCK_MONOTONIC, &t2);
     {
         const char *lg = getenv("OATK_DROPIN_LOG");

@@ -375,6 +375,34 @@ class HipSyncasm:
         self._check(self.L.oatk_hip_ingest(self.h, d_text, n_bytes, fmt, 1 if final else 0, C.byref(n), C.byref(used)), "oatk_hip_ingest")
         return int(n.value), int(used.value)
 
+    # ---- unaligned BAM -> packed read stream on the device (include/oatk_hip_ingest.h: oatk_hip_ingest_bam) ----
+    def ingest_bam_host(self, data, header=True, final=True):
+        """data: bytes / uint8 array with the INFLATED content of an unaligned BAM file, or a chunk of one (header: it begins with the BAM header; final=False:
+        more follows).  Returns (n_reads, consumed bytes); the packed stream stays resident as after ingest_host, and self.bam_text = (device pointer, bytes)
+        is what ingest_names wants."""
+        t = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        self._keep_text = t
+        n, used = C.c_uint64(), C.c_uint64()
+        self._check(self.L.oatk_hip_ingest_bam_host(self.h, t.ctypes.data if t.size else None, t.size, 1 if header else 0, 1 if final else 0, C.byref(n), C.byref(used)),
+                    "oatk_hip_ingest_bam_host")
+        d_text = C.c_void_p()
+        self._check(self.L.oatk_hip_ingest_text_buffer(self.h, t.size, C.byref(d_text)), "oatk_hip_ingest_text_buffer")       # (the buffer the call above filled: no growth)
+        self.bam_text = (d_text.value, t.size)
+        return int(n.value), int(used.value)
+
+    def ingest_bam_device(self, d_ptr, n_bytes, header=True, final=True):
+        """the same for bytes that lie on the device, e.g. self.inflated after inflate_bgzf of the .bam file's bytes: no text on the host"""
+        n, used = C.c_uint64(), C.c_uint64()
+        self._check(self.L.oatk_hip_ingest_bam(self.h, d_ptr, n_bytes, 1 if header else 0, 1 if final else 0, C.byref(n), C.byref(used)), "oatk_hip_ingest_bam")
+        self.bam_text = (d_ptr, n_bytes)
+        return int(n.value), int(used.value)
+
+    def bam_stats(self):
+        """{candidates, records, header_bytes} of the latest BAM ingest: byte offsets that pass the record check, those of them on the chain, the header's length"""
+        out = (C.c_uint64 * 3)()
+        self._check(self.L.oatk_hip_ingest_bam_stats(self.h, out), "oatk_hip_ingest_bam_stats")
+        return {"candidates": int(out[0]), "records": int(out[1]), "header_bytes": int(out[2])}
+
     # ---- BGZF members inflated on the device (include/oatk_hip_ingest.h: oatk_hip_inflate_bgzf) ----
     def inflate_members(self, comp, members, d_text, text_cap):
         """comp: the compressed bytes (host); members: a record array of _lib.BGZF_MEMBER; d_text: device pointer (int) with room for text_cap bytes.
