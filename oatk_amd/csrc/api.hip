@@ -94,14 +94,6 @@ struct oatk_hip_ctx {
             return OATK_E_NODEV;                                                                   \
         }                                                                                          \
     } while (0)
-#define ENSURE(buf, bytes, ...)                                                                    \
-    do {                                                                                           \
-        if (!ctx->buf.ensure((bytes), ctx->stream, ##__VA_ARGS__)) {                               \
-            ctx->err = "hipMalloc failed for " #buf;                                               \
-            return OATK_E_NOMEM;                                                                   \
-        }                                                                                          \
-    } while (0)
-
 // Test hook (tests/test_gpu_cli.py): OATK_DEBUG_REFUSE=<bit mask> makes an entry point decline with OATK_E_SPLIT as if its input were one of the
 // rare shapes it refuses -- 1 the EC graph (duplicate arcs), 2 the assembly graph, 4 the count (oversized hash group), 8 the pair-distance tables --
 // so that a caller's fallback to the original routine can be exercised on inputs that do not produce those shapes.  Unset in production.
@@ -135,6 +127,7 @@ static void t_collect(oatk_hip_ctx *ctx, int first, int last)
     }
 }
 
+#include "api_prim.inc"
 #include "api_ec.inc"
 #include "api_graph.inc"
 #include "api_cons.inc"
@@ -290,13 +283,6 @@ int oatk_hip_debug_hash_mask(oatk_hip_ctx *ctx, uint64_t mask)
     return OATK_OK;
 }
 
-__global__ void widen_kernel(const uint32_t *in, uint64_t *out, uint64_t n)
-{
-    uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = in[i];
-    if (i == n) out[i] = 0;
-}
-
 static void scan_reset_downstream(oatk_hip_ctx *ctx);
 
 static int launch_scan_kernels(oatk_hip_ctx *ctx)
@@ -433,31 +419,19 @@ int oatk_hip_scan(oatk_hip_ctx *ctx, const uint8_t *d_seq, const uint64_t *d_off
     t_begin(ctx, OATK_T_SCAN_POST);
     ctx->nn_sorted_in_2 = ctx->lrl_sorted_in_2 = false;
     if (ctx->tot_nn > 1) {
-        size_t tb = 0;
-        CK(rocprim::radix_sort_keys(nullptr, tb, ctx->nn_key.as<uint64_t>(), ctx->nn_key2.as<uint64_t>(), ctx->tot_nn, 0, 64, ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::radix_sort_keys(ctx->tmp.p, tb, ctx->nn_key.as<uint64_t>(), ctx->nn_key2.as<uint64_t>(), ctx->tot_nn, 0, 64, ctx->stream));
+        PRIM(rocprim::radix_sort_keys, ctx->nn_key.as<uint64_t>(), ctx->nn_key2.as<uint64_t>(), ctx->tot_nn, 0, 64, ctx->stream);
         ctx->nn_sorted_in_2 = true;
     }
     if (ctx->tot_lrl > 1) {
-        size_t tb = 0;
-        CK(rocprim::radix_sort_pairs(nullptr, tb, ctx->lrl_key.as<uint64_t>(), ctx->lrl_key2.as<uint64_t>(), ctx->lrl_val.as<uint32_t>(),
-                                     ctx->lrl_val2.as<uint32_t>(), ctx->tot_lrl, 0, 64, ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, ctx->lrl_key.as<uint64_t>(), ctx->lrl_key2.as<uint64_t>(), ctx->lrl_val.as<uint32_t>(),
-                                     ctx->lrl_val2.as<uint32_t>(), ctx->tot_lrl, 0, 64, ctx->stream));
+        PRIM(rocprim::radix_sort_pairs, ctx->lrl_key.as<uint64_t>(), ctx->lrl_key2.as<uint64_t>(), ctx->lrl_val.as<uint32_t>(), ctx->lrl_val2.as<uint32_t>(), ctx->tot_lrl, 0, 64,
+             ctx->stream);
         ctx->lrl_sorted_in_2 = true;
     }
     {
         ENSURE(n_scm64, (n_reads + 1) * 8); ENSURE(scm_off, (n_reads + 1) * 8);
         unsigned nb = (unsigned) ((n_reads + 1 + 255) / 256);
         hipLaunchKernelGGL(widen_kernel, dim3(nb), dim3(256), 0, ctx->stream, ctx->n_scm.as<uint32_t>(), ctx->n_scm64.as<uint64_t>(), n_reads);
-        size_t tb = 0;
-        CK(rocprim::exclusive_scan(nullptr, tb, ctx->n_scm64.as<uint64_t>(), ctx->scm_off.as<uint64_t>(), (uint64_t) 0, n_reads + 1,
-                                   rocprim::plus<uint64_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::exclusive_scan(ctx->tmp.p, tb, ctx->n_scm64.as<uint64_t>(), ctx->scm_off.as<uint64_t>(), (uint64_t) 0, n_reads + 1,
-                                   rocprim::plus<uint64_t>(), ctx->stream));
+        PRIM(rocprim::exclusive_scan, ctx->n_scm64.as<uint64_t>(), ctx->scm_off.as<uint64_t>(), (uint64_t) 0, n_reads + 1, rocprim::plus<uint64_t>(), ctx->stream);
     }
     t_end(ctx, OATK_T_SCAN_POST);
 
@@ -601,19 +575,18 @@ int oatk_hip_scan_append(oatk_hip_ctx *ctx, oatk_hip_ctx *src)
     { int rc = append_ensure(ctx, n0 + n1, b0 + b1, o0 + o1, ctx->tot_nn + src->tot_nn, ctx->tot_lrl + src->tot_lrl); if (rc) return rc; }
     if (hipStreamSynchronize(src->stream) != hipSuccess) { ctx->err = "oatk_hip_scan_append: the piece's stream failed"; return OATK_E_NODEV; }
     hipStream_t st = ctx->stream;
-    auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };
     auto d2d = [&](void *dst, const void *from, size_t bytes) { return bytes? hipMemcpyAsync(dst, from, bytes, hipMemcpyDeviceToDevice, st) : hipSuccess; };
     CK(d2d(ctx->ho_rl.as<uint8_t>() + b0, src->ho_rl.p, b1));
     CK(d2d(ctx->hoco_s.as<uint8_t>() + b0 / 4, src->hoco_s.p, b1 / 4 + 64));
     CK(d2d(ctx->hoco_l.as<uint32_t>() + n0, src->hoco_l.p, n1 * 4)); CK(d2d(ctx->n_scm.as<uint32_t>() + n0, src->n_scm.p, n1 * 4));
     CK(d2d(ctx->n_nn.as<uint32_t>() + n0, src->n_nn.p, n1 * 4)); CK(d2d(ctx->n_lrl.as<uint32_t>() + n0, src->n_lrl.p, n1 * 4));
-    hipLaunchKernelGGL(append_rebase_kernel, blocks(n1), dim3(256), 0, st, src->d_off, ctx->in_off.as<uint64_t>() + n0, n1, b0);
-    hipLaunchKernelGGL(append_rebase_kernel, blocks(n1 + 1), dim3(256), 0, st, src->scm_off.as<uint64_t>(), ctx->scm_off.as<uint64_t>() + n0, n1 + 1, o0);
+    hipLaunchKernelGGL(append_rebase_kernel, grid256(n1), dim3(256), 0, st, src->d_off, ctx->in_off.as<uint64_t>() + n0, n1, b0);
+    hipLaunchKernelGGL(append_rebase_kernel, grid256(n1 + 1), dim3(256), 0, st, src->scm_off.as<uint64_t>(), ctx->scm_off.as<uint64_t>() + n0, n1 + 1, o0);
     if (o1) {
         CK(d2d(ctx->pos_hash.as<uint64_t>() + o0, src->pos_hash.p, o1 * 8)); CK(d2d(ctx->pos_lo.as<uint64_t>() + o0, src->pos_lo.p, o1 * 8));
         CK(d2d(ctx->pos_smer.as<uint64_t>() + o0, src->pos_smer.p, o1 * 8)); CK(d2d(ctx->pos_mpos.as<uint32_t>() + o0, src->pos_mpos.p, o1 * 4));
         CK(d2d(ctx->key_hash.as<uint64_t>() + o0, src->key_hash.p, o1 * 8));
-        hipLaunchKernelGGL(append_iota_kernel, blocks(o1), dim3(256), 0, st, ctx->iota.as<uint32_t>(), o0, o1);
+        hipLaunchKernelGGL(append_iota_kernel, grid256(o1), dim3(256), 0, st, ctx->iota.as<uint32_t>(), o0, o1);
     }
     // keys carry global read ids and the pieces come in read order: the concatenation is sorted
     CK(d2d(ctx->nn_key.as<uint64_t>() + ctx->tot_nn, src->nn_sorted_in_2? src->nn_key2.p : src->nn_key.p, src->tot_nn * 8));
@@ -672,12 +645,7 @@ sort_again:
     t_begin(ctx, OATK_T_COUNT_SORT);
     {
         const unsigned lo_bit = full_sort? 0u : (unsigned) OATK_SORT_LOW_BITS;
-        size_t tb = 0;
-        CK(rocprim::radix_sort_pairs(nullptr, tb, ctx->key_hash.as<uint64_t>(), ctx->key_sorted.as<uint64_t>(), ctx->iota.as<uint32_t>(),
-                                     ctx->perm.as<uint32_t>(), n, lo_bit, 64, ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, ctx->key_hash.as<uint64_t>(), ctx->key_sorted.as<uint64_t>(), ctx->iota.as<uint32_t>(),
-                                     ctx->perm.as<uint32_t>(), n, lo_bit, 64, ctx->stream));
+        PRIM(rocprim::radix_sort_pairs, ctx->key_hash.as<uint64_t>(), ctx->key_sorted.as<uint64_t>(), ctx->iota.as<uint32_t>(), ctx->perm.as<uint32_t>(), n, lo_bit, 64, ctx->stream);
         if (!full_sort) {
             uint32_t *owner = ctx->head.as<uint32_t>();              // (free until mark_heads_kernel)
             CK(hipMemsetAsync(owner, 0xFF, n * 4, ctx->stream));
@@ -711,19 +679,12 @@ sort_again:
     // (the pass over the sorted keys that checks the sort also marks the heads)
     hipLaunchKernelGGL((pair_sum_kernel<true>), dim3(2048), dim3(256), 0, ctx->stream, ctx->key_sorted.as<uint64_t>(), ctx->perm.as<uint32_t>(), (uint32_t) n, ctx->flags.as<uint32_t>(), 12,
                        g.head, g.newclus, g.head_idx);
-    {   // head_idx := index of the latest head at or before i
-        size_t tb = 0;
-        CK(rocprim::inclusive_scan(nullptr, tb, ctx->head_idx.as<uint32_t>(), ctx->head_idx.as<uint32_t>(), n, rocprim::maximum<uint32_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::inclusive_scan(ctx->tmp.p, tb, ctx->head_idx.as<uint32_t>(), ctx->head_idx.as<uint32_t>(), n, rocprim::maximum<uint32_t>(), ctx->stream));
-    }
+    // head_idx := index of the latest head at or before i
+    PRIM(rocprim::inclusive_scan, ctx->head_idx.as<uint32_t>(), ctx->head_idx.as<uint32_t>(), n, rocprim::maximum<uint32_t>(), ctx->stream);
     uint32_t n_scm = 0;
     FinishArgs f;
     auto ids = [&]() -> int {               // clus_id := number of heads at or before i (= id + 1); n_scm; room for the table
-        size_t tb = 0;
-        CK(rocprim::inclusive_scan(nullptr, tb, ctx->newclus.as<uint32_t>(), ctx->clus_id.as<uint32_t>(), n, rocprim::plus<uint32_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::inclusive_scan(ctx->tmp.p, tb, ctx->newclus.as<uint32_t>(), ctx->clus_id.as<uint32_t>(), n, rocprim::plus<uint32_t>(), ctx->stream));
+        PRIM(rocprim::inclusive_scan, ctx->newclus.as<uint32_t>(), ctx->clus_id.as<uint32_t>(), n, rocprim::plus<uint32_t>(), ctx->stream);
         uint32_t last_id = 0;
         CK(hipMemcpyAsync(&last_id, ctx->clus_id.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));

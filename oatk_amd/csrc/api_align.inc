@@ -76,10 +76,7 @@ __global__ void ra_debug_kernel(oatk::RaArgs a, unsigned long long *dbg)
     atomicAdd(&dbg[8 + b], 1ULL);
 }
 
-#define RENSURE(buf, bytes)                                                                        \
-    do {                                                                                           \
-        if (!g->buf.ensure((bytes), ctx->stream)) { ctx->err = "hipMalloc failed for align." #buf; return OATK_E_NOMEM; } \
-    } while (0)
+#define RENSURE(buf, bytes) ENSURE_IN(g, "align.", buf, bytes)
 #define RUPLOAD(buf, src, bytes)                                                                   \
     do {                                                                                           \
         RENSURE(buf, (bytes) + 8);                                                                 \
@@ -201,14 +198,8 @@ static int ra_big_run(oatk_hip_ctx *ctx, RaState *g, const oatk::RaArgs &a, int 
         uint64_t *lo2 = g->bg[7].as<uint64_t>(), *hi2 = g->bg[8].as<uint64_t>();
         hipLaunchKernelGGL(rab_expand_kernel, dim3((unsigned) ((nb + 3) / 4)), dim3(256), 0, ctx->stream, q);
         {   // sr_scm_cmpfunc's order (alignment.c:93-107) over the whole batch: by (read position, unitig position), then -- stable -- by (read, unitig)
-            size_t tb = 0;
-            CK(rocprim::radix_sort_pairs(nullptr, tb, q.key_lo, lo2, q.key_hi, hi2, H, 0, 48, ctx->stream));
-            RENSURE(tmp64, tb);
-            CK(rocprim::radix_sort_pairs(g->tmp64.p, tb, q.key_lo, lo2, q.key_hi, hi2, H, 0, 48, ctx->stream));
-            tb = 0;
-            CK(rocprim::radix_sort_pairs(nullptr, tb, hi2, q.key_hi, lo2, q.key_lo, H, 0, 43 + RAB_IDX_BITS, ctx->stream));
-            RENSURE(tmp64, tb);
-            CK(rocprim::radix_sort_pairs(g->tmp64.p, tb, hi2, q.key_hi, lo2, q.key_lo, H, 0, 43 + RAB_IDX_BITS, ctx->stream));
+            PRIM_IN(g->tmp64, ctx->stream, "hipMalloc failed for align.tmp64", rocprim::radix_sort_pairs, q.key_lo, lo2, q.key_hi, hi2, H, 0, 48, ctx->stream);
+            PRIM_IN(g->tmp64, ctx->stream, "hipMalloc failed for align.tmp64", rocprim::radix_sort_pairs, hi2, q.key_hi, lo2, q.key_lo, H, 0, 43 + RAB_IDX_BITS, ctx->stream);
         }
         CK(hipMemsetAsync(q.haspred, 0, H, ctx->stream));
         hipLaunchKernelGGL(rab_links_kernel, dim3((unsigned) nb), dim3(256), 0, ctx->stream, q);
@@ -224,10 +215,7 @@ static int ra_big_run(oatk_hip_ctx *ctx, RaState *g, const oatk::RaArgs &a, int 
             uint32_t *iota = (uint32_t *) lo2, *order = (uint32_t *) hi2;              // (the sort's second buffers are free again)
             hipLaunchKernelGGL(rab_iota_kernel, dim3((unsigned) ((H + 255) / 256)), dim3(256), 0, ctx->stream, iota, H);
             BTAKE(bgH, curH, 19, H * 8);
-            size_t tb = 0;
-            CK(rocprim::radix_sort_pairs(nullptr, tb, q.f_key, g->bg[19].as<uint64_t>(), iota, order, H, 0, 64, ctx->stream));
-            RENSURE(tmp64, tb);
-            CK(rocprim::radix_sort_pairs(g->tmp64.p, tb, q.f_key, g->bg[19].as<uint64_t>(), iota, order, H, 0, 64, ctx->stream));
+            PRIM_IN(g->tmp64, ctx->stream, "hipMalloc failed for align.tmp64", rocprim::radix_sort_pairs, q.f_key, g->bg[19].as<uint64_t>(), iota, order, H, 0, 64, ctx->stream);
             q.f_order = order;
         }
         CK(hipStreamSynchronize(ctx->stream));
@@ -324,8 +312,8 @@ extern "C" int oatk_hip_read_alignment(oatk_hip_ctx *ctx, const oatk_ra_graph_t 
         if (!getenv("OATK_DEBUG_RA_NO_BIG")) { int rc = ra_big_count(ctx, g, a, &big); if (rc) return rc; }
         ra_mark("reads with many hits");
         CK(hipMemcpyAsync(pu, g->pool_used.p, sizeof(pu), hipMemcpyDeviceToHost, ctx->stream));
-        { int rc = ec_exclusive_scan_u32(ctx, nullptr, g->cnt_aln, g->tmp64, g->aln_off, nr, &tot_a); if (rc) return rc; }
-        { int rc = ec_exclusive_scan_u32(ctx, nullptr, g->cnt_frg, g->tmp64, g->frg_off, nr, &tot_f); if (rc) return rc; }
+        { int rc = prim_scan_total_u32(ctx, g->cnt_aln, g->tmp64, g->aln_off, nr, &tot_a); if (rc) return rc; }
+        { int rc = prim_scan_total_u32(ctx, g->cnt_frg, g->tmp64, g->frg_off, nr, &tot_f); if (rc) return rc; }
     }
     RENSURE(o_sid, (tot_a + 1) * 4); RENSURE(o_off, (tot_a + 2) * 8); RENSURE(o_s, (tot_a + 1) * 8);
     RENSURE(o_uid, (tot_f + 1) * 8); RENSURE(o_ubeg, (tot_f + 1) * 4); RENSURE(o_uend, (tot_f + 1) * 4); RENSURE(o_sbeg, (tot_f + 1) * 4); RENSURE(o_send, (tot_f + 1) * 4);

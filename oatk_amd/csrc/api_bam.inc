@@ -36,7 +36,6 @@ extern "C" int oatk_hip_ingest_bam(oatk_hip_ctx *ctx, const uint8_t *d_bam, uint
     g->bam_stats[0] = g->bam_stats[1] = g->bam_stats[2] = 0;
     if (n_reads) *n_reads = 0;
     if (consumed) *consumed = 0;
-    auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };
     if (n_bytes && !d_bam) { ctx->err = "oatk_hip_ingest_bam: null argument"; return OATK_E_ARG; }
     uint64_t s0 = 0;
     if (header) {
@@ -64,8 +63,8 @@ extern "C" int oatk_hip_ingest_bam(oatk_hip_ctx *ctx, const uint8_t *d_bam, uint
     if (s0 < n_bytes) {
         GENSURE(cnt, (nb + 1) * 4); GENSURE(cnt64, (nb + 1) * 8); GENSURE(blk_off, (nb + 1) * 8);
         hipLaunchKernelGGL(bam_count_cand_kernel, dim3((unsigned) nb), dim3(256), 0, ctx->stream, d_bam, n_bytes, s0, g->cnt.as<uint32_t>());
-        hipLaunchKernelGGL(ec_widen_kernel, blocks(nb + 1), dim3(256), 0, ctx->stream, g->cnt.as<uint32_t>(), g->cnt64.as<uint64_t>(), nb);
-        { int rc = ing_scan_u64(ctx, g->cnt64.as<uint64_t>(), g->blk_off.as<uint64_t>(), nb + 1); if (rc) return rc; }
+        hipLaunchKernelGGL(widen_kernel, grid256(nb + 1), dim3(256), 0, ctx->stream, g->cnt.as<uint32_t>(), g->cnt64.as<uint64_t>(), nb);
+        PRIM(rocprim::exclusive_scan, g->cnt64.as<const uint64_t>(), g->blk_off.as<uint64_t>(), (uint64_t) 0, nb + 1, rocprim::plus<uint64_t>(), ctx->stream);
         CK(hipMemcpyAsync(&m, g->blk_off.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
         g->bam_stats[0] = m;
@@ -77,21 +76,21 @@ extern "C" int oatk_hip_ingest_bam(oatk_hip_ctx *ctx, const uint8_t *d_bam, uint
         hipLaunchKernelGGL(bam_fill_cand_kernel, dim3((unsigned) nb), dim3(256), 0, ctx->stream, d_bam, n_bytes, s0, g->blk_off.as<uint64_t>(), g->bam_cand.as<uint64_t>());
         mark(1);
         // ---- successors, reachability from s0 by pointer doubling ----
-        hipLaunchKernelGGL(bam_succ_kernel, blocks(m + 1), dim3(256), 0, ctx->stream, d_bam, g->bam_cand.as<uint64_t>(), m, s0, g->bam_jump.as<uint32_t>(), g->bam_mark.as<uint64_t>());
+        hipLaunchKernelGGL(bam_succ_kernel, grid256(m + 1), dim3(256), 0, ctx->stream, d_bam, g->bam_cand.as<uint64_t>(), m, s0, g->bam_jump.as<uint32_t>(), g->bam_mark.as<uint64_t>());
         uint32_t *ja = g->bam_jump.as<uint32_t>(), *jb = g->bam_jump2.as<uint32_t>();
         for (uint64_t reach = 1; reach < m + 1; reach <<= 1) {                                      // ceil(log2(m + 1)) rounds
-            hipLaunchKernelGGL(bam_double_kernel, blocks(m + 1), dim3(256), 0, ctx->stream, m, ja, jb, g->bam_mark.as<uint64_t>());
+            hipLaunchKernelGGL(bam_double_kernel, grid256(m + 1), dim3(256), 0, ctx->stream, m, ja, jb, g->bam_mark.as<uint64_t>());
             std::swap(ja, jb);
         }
         mark(2);
         // ---- the marked candidates are the records ----
-        { int rc = ing_scan_u64(ctx, g->bam_mark.as<uint64_t>(), g->bam_rank.as<uint64_t>(), m + 1); if (rc) return rc; }
+        PRIM(rocprim::exclusive_scan, g->bam_mark.as<const uint64_t>(), g->bam_rank.as<uint64_t>(), (uint64_t) 0, m + 1, rocprim::plus<uint64_t>(), ctx->stream);
         CK(hipMemcpyAsync(&n_rec, g->bam_rank.as<uint64_t>() + m, 8, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
     }
     g->bam_stats[1] = n_rec;
     GENSURE(bam_rec, (n_rec + 1) * 8);
-    if (n_rec) hipLaunchKernelGGL(bam_compact_kernel, blocks(m), dim3(256), 0, ctx->stream, g->bam_cand.as<uint64_t>(), m, g->bam_mark.as<uint64_t>(), g->bam_rank.as<uint64_t>(),
+    if (n_rec) hipLaunchKernelGGL(bam_compact_kernel, grid256(m), dim3(256), 0, ctx->stream, g->bam_cand.as<uint64_t>(), m, g->bam_mark.as<uint64_t>(), g->bam_rank.as<uint64_t>(),
                                   g->bam_rec.as<uint64_t>());
     // ---- where the chain stops ----
     uint64_t stop[2] = {s0, oatk_bam::STOP_CLEAN};
@@ -110,9 +109,9 @@ extern "C" int oatk_hip_ingest_bam(oatk_hip_ctx *ctx, const uint8_t *d_bam, uint
     // ---- per record: length, place in the packed stream; the letters ----
     mark(3);
     GENSURE(len, (n_rec + 1) * 4); GENSURE(padded, (n_rec + 2) * 8); GENSURE(off, (n_rec + 2) * 8); GENSURE(hdr_off, (n_rec + 1) * 8);
-    hipLaunchKernelGGL(bam_record_kernel, blocks(n_rec + 1), dim3(256), 0, ctx->stream, d_bam, g->bam_rec.as<uint64_t>(), n_rec, g->len.as<uint32_t>(), g->padded.as<uint64_t>(),
+    hipLaunchKernelGGL(bam_record_kernel, grid256(n_rec + 1), dim3(256), 0, ctx->stream, d_bam, g->bam_rec.as<uint64_t>(), n_rec, g->len.as<uint32_t>(), g->padded.as<uint64_t>(),
                        g->hdr_off.as<uint64_t>(), g->flags.as<uint32_t>(), (unsigned long long *) (g->flags.as<uint8_t>() + 8));
-    { int rc = ing_scan_u64(ctx, g->padded.as<uint64_t>(), g->off.as<uint64_t>(), n_rec + 1); if (rc) return rc; }
+    PRIM(rocprim::exclusive_scan, g->padded.as<const uint64_t>(), g->off.as<uint64_t>(), (uint64_t) 0, n_rec + 1, rocprim::plus<uint64_t>(), ctx->stream);
     mark(4);
     uint64_t seq_bytes = 0;
     uint32_t fl[4] = {0, 0, 0, 0};

@@ -31,10 +31,7 @@ static int cons_buffer(oatk_hip_ctx *ctx, int which, const void **d_ptr, uint64_
     return OATK_OK;
 }
 
-#define CENSURE(buf, bytes)                                                                        \
-    do {                                                                                           \
-        if (!c->buf.ensure((bytes), ctx->stream)) { ctx->err = "hipMalloc failed for cons." #buf; return OATK_E_NOMEM; } \
-    } while (0)
+#define CENSURE(buf, bytes) ENSURE_IN(c, "cons.", buf, bytes)
 
 // run-length totals of the syncmers listed in c->sel[0..n_sel)
 static int cons_run(oatk_hip_ctx *ctx, ConsState *c, uint64_t n_sel)
@@ -59,15 +56,8 @@ static int cons_run(oatk_hip_ctx *ctx, ConsState *c, uint64_t n_sel)
         // workgroups: one per CONS_CHUNK occurrences of a syncmer (consensus.hpp)
         CENSURE(nch, (n_sel + 2) * 8); CENSURE(ch_off, (n_sel + 2) * 8);
         hipLaunchKernelGGL(cons_chunks_kernel, dim3((unsigned) ((n_sel + 1 + 255) / 256)), dim3(256), 0, ctx->stream, n_sel, a.sel, a.occ_off, c->nch.as<uint64_t>());
-        {
-            size_t tb = 0;
-            CK(rocprim::exclusive_scan(nullptr, tb, c->nch.as<uint64_t>(), c->ch_off.as<uint64_t>(), (uint64_t) 0, n_sel + 1, rocprim::plus<uint64_t>(), ctx->stream));
-            ENSURE(tmp, tb);
-            CK(rocprim::exclusive_scan(ctx->tmp.p, tb, c->nch.as<uint64_t>(), c->ch_off.as<uint64_t>(), (uint64_t) 0, n_sel + 1, rocprim::plus<uint64_t>(), ctx->stream));
-        }
         uint64_t n_wg = 0;
-        CK(hipMemcpyAsync(&n_wg, c->ch_off.as<uint64_t>() + n_sel, 8, hipMemcpyDeviceToHost, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
+        { int rc = prim_scan_total(ctx, ctx->tmp, c->nch.as<uint64_t>(), c->ch_off.as<uint64_t>(), n_sel, &n_wg); if (rc) return rc; }
         if (n_wg > 0x7FFFFFFFULL) { ctx->err = "too many occurrences selected for consensus"; return OATK_E_ARG; }
         a.ch_off = c->ch_off.as<uint64_t>(), a.n_wg = n_wg;
         if (n_wg > n_sel) hipLaunchKernelGGL(cons_zero_shared_kernel, dim3((unsigned) n_sel), dim3(256), 0, ctx->stream, a);
@@ -101,23 +91,13 @@ extern "C" int oatk_hip_consensus_ids(oatk_hip_ctx *ctx, const uint32_t *d_ids, 
 static int cons_select(oatk_hip_ctx *ctx, ConsState *c, uint64_t ns, const uint32_t *cov, const uint8_t *del, uint32_t min_cov, uint64_t *n_sel_out)
 {
     using namespace oatk;
-    auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };
     CENSURE(flag, (ns + 1) * 4); CENSURE(slot, (ns + 1) * 4);
-    hipLaunchKernelGGL(cons_flag_kernel, blocks(ns), dim3(256), 0, ctx->stream, ns, cov, del, min_cov, c->flag.as<uint32_t>());
+    hipLaunchKernelGGL(cons_flag_kernel, grid256(ns), dim3(256), 0, ctx->stream, ns, cov, del, min_cov, c->flag.as<uint32_t>());
     uint64_t n_sel = 0;
-    {   // exclusive scan of the flags = slots
-        if (!c->flag64.ensure((ns + 1) * 8, ctx->stream) || !c->slot_of.ensure((ns + 1) * 8, ctx->stream)) { ctx->err = "hipMalloc failed (cons scan)"; return OATK_E_NOMEM; }
-        hipLaunchKernelGGL(ec_widen_kernel, dim3((unsigned) ((ns + 1 + 255) / 256)), dim3(256), 0, ctx->stream, c->flag.as<uint32_t>(), c->flag64.as<uint64_t>(), ns);
-        size_t tb = 0;
-        CK(rocprim::exclusive_scan(nullptr, tb, c->flag64.as<uint64_t>(), c->slot_of.as<uint64_t>(), (uint64_t) 0, ns + 1, rocprim::plus<uint64_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::exclusive_scan(ctx->tmp.p, tb, c->flag64.as<uint64_t>(), c->slot_of.as<uint64_t>(), (uint64_t) 0, ns + 1, rocprim::plus<uint64_t>(), ctx->stream));
-        CK(hipMemcpyAsync(&n_sel, c->slot_of.as<uint64_t>() + ns, 8, hipMemcpyDeviceToHost, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
-    }
+    { int rc = prim_scan_total_u32(ctx, c->flag, c->flag64, c->slot_of, ns, &n_sel); if (rc) return rc; }      // exclusive scan of the flags = slots
     c->n_sel = n_sel;
     CENSURE(sel, (n_sel + 1) * 4);
-    hipLaunchKernelGGL(cons_select_kernel, blocks(ns), dim3(256), 0, ctx->stream, ns, c->flag.as<uint32_t>(), c->slot_of.as<uint64_t>(), c->sel.as<uint32_t>(),
+    hipLaunchKernelGGL(cons_select_kernel, grid256(ns), dim3(256), 0, ctx->stream, ns, c->flag.as<uint32_t>(), c->slot_of.as<uint64_t>(), c->sel.as<uint32_t>(),
                        c->slot.as<uint32_t>());
     *n_sel_out = n_sel;
     return OATK_OK;

@@ -6,8 +6,6 @@
 #include "ec_fused.hpp"
 #include "ecgraph.hpp"
 #include "ec_seq.hpp"
-#include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
 struct EcState {
@@ -122,33 +120,7 @@ __global__ void ec_narrow_kernel(const uint64_t *in, uint32_t *out, uint64_t n)
     uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (uint32_t) in[i];
 }
-__global__ void ec_widen_kernel(const uint32_t *in, uint64_t *out, uint64_t n)      // out has n + 1 entries
-{
-    uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = in[i];
-    if (i == n) out[i] = 0;
-}
-#define EENSURE(buf, bytes, ...)                                                                   \
-    do {                                                                                           \
-        if (!e->buf.ensure((bytes), ctx->stream, ##__VA_ARGS__)) {                                 \
-            ctx->err = "hipMalloc failed for ec." #buf;                                            \
-            return OATK_E_NOMEM;                                                                   \
-        }                                                                                          \
-    } while (0)
-
-static int ec_exclusive_scan_u32(oatk_hip_ctx *ctx, EcState *e, DevBuf &in32, DevBuf &tmp64, DevBuf &out64, uint64_t n, uint64_t *total)
-{
-    if (!tmp64.ensure((n + 1) * 8, ctx->stream) || !out64.ensure((n + 1) * 8, ctx->stream)) { ctx->err = "hipMalloc failed (ec scan)"; return OATK_E_NOMEM; }
-    hipLaunchKernelGGL(ec_widen_kernel, dim3((unsigned) ((n + 1 + 255) / 256)), dim3(256), 0, ctx->stream, in32.as<uint32_t>(), tmp64.as<uint64_t>(), n);
-    size_t tb = 0;
-    CK(rocprim::exclusive_scan(nullptr, tb, tmp64.as<uint64_t>(), out64.as<uint64_t>(), (uint64_t) 0, n + 1, rocprim::plus<uint64_t>(), ctx->stream));
-    if (!ctx->tmp.ensure(tb, ctx->stream)) { ctx->err = "hipMalloc failed (ec scan tmp)"; return OATK_E_NOMEM; }
-    CK(rocprim::exclusive_scan(ctx->tmp.p, tb, tmp64.as<uint64_t>(), out64.as<uint64_t>(), (uint64_t) 0, n + 1, rocprim::plus<uint64_t>(), ctx->stream));
-    CK(hipMemcpyAsync(total, out64.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    (void) e;
-    return OATK_OK;
-}
+#define EENSURE(buf, bytes, ...) ENSURE_IN(e, "ec.", buf, bytes, ##__VA_ARGS__)
 
 extern "C" int oatk_hip_debug_ec_tiers(oatk_hip_ctx *ctx, int cap_t0, int cap_t1)
 {
@@ -409,21 +381,6 @@ extern "C" int oatk_hip_ec_pairs(oatk_hip_ctx *ctx, const void **d_keys, const v
 // run-length encoded in that form, the distinct ones are written to g_ukeys as keys on vertex ids, and from there on nothing differs.
 struct EgrPacked { void *keys; uint32_t B; bool wide; const uint32_t *cand_id; };      // keys: uint32_t, or uint64_t when wide; ra << B | rb (ecgraph.hpp)
 
-template <class KeyT>
-static int ec_sort_packed(oatk_hip_ctx *ctx, EcState *e, const EgrPacked &pk, uint32_t *dist_in, uint64_t nocc)
-{
-    KeyT *in = (KeyT *) pk.keys, *sorted = e->g_keys2.as<KeyT>();
-    size_t tb = 0;              // stable, and from bit 0 (DESIGN.md 6: rocPRIM's small-input paths and ranges that start higher)
-    CK(rocprim::radix_sort_pairs(nullptr, tb, in, sorted, dist_in, e->g_dist2.as<uint32_t>(), nocc, 0, 2 * pk.B, ctx->stream));
-    ENSURE(tmp, tb);
-    CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, in, sorted, dist_in, e->g_dist2.as<uint32_t>(), nocc, 0, 2 * pk.B, ctx->stream));
-    tb = 0;                     // the distinct keys go where the unsorted ones were
-    CK(rocprim::run_length_encode(nullptr, tb, sorted, (unsigned int) nocc, in, e->g_counts.as<uint32_t>(), e->g_nruns.as<uint32_t>(), ctx->stream));
-    ENSURE(tmp, tb);
-    CK(rocprim::run_length_encode(ctx->tmp.p, tb, sorted, (unsigned int) nocc, in, e->g_counts.as<uint32_t>(), e->g_nruns.as<uint32_t>(), ctx->stream));
-    return OATK_OK;
-}
-
 static int ec_graph_build(oatk_hip_ctx *ctx, const uint64_t *d_keys, const uint32_t *d_dist, const uint64_t *d_val, uint64_t nocc, bool timer_running = false,
                           const EgrPacked *pk = nullptr)
 {
@@ -438,7 +395,6 @@ static int ec_graph_build(oatk_hip_ctx *ctx, const uint64_t *d_keys, const uint3
     if (nocc >= 0xFFFFFFFFULL) { ctx->err = "more than 2^32 adjacent pairs"; return OATK_E_ARG; }
     const uint64_t nv = ec_n_vtx(ctx);
     if (nv >= 0x7FFFFFFFULL) { ctx->err = "too many syncmers for 32-bit oriented vertex ids"; return OATK_E_ARG; }
-    auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };
     EENSURE(g_flags, 64);
     if (!timer_running) t_begin(ctx, OATK_T_EC_GRAPH);
     CK(hipMemsetAsync(e->g_flags.p, 0, 64, ctx->stream));
@@ -452,45 +408,35 @@ static int ec_graph_build(oatk_hip_ctx *ctx, const uint64_t *d_keys, const uint3
         EENSURE(g_nruns, 64); EENSURE(g_dist2, (nocc + 1) * 4);
         uint64_t *keys_in = const_cast<uint64_t *>(d_keys);
         uint32_t *dist_in = const_cast<uint32_t *>(d_dist);
-        size_t tb = 0;          // stable: the distances of one key stay in (read, slot) order
-        if (weighted) {
+        uint32_t *counts = e->g_counts.as<uint32_t>(), *d_nruns = e->g_nruns.as<uint32_t>();
+        int rc = OATK_OK;       // the sorts are stable: the distances of one key stay in (read, slot) order
+        if (weighted) {         // (the segments' values are split between the sort and the runs, so the two steps are spelt out)
             EENSURE(g_val2, (nocc + 1) * 8); EENSURE(g_wgt2, (nocc + 1) * 4);
             uint64_t *val_in = const_cast<uint64_t *>(d_val);
-            CK(rocprim::radix_sort_pairs(nullptr, tb, keys_in, e->g_keys2.as<uint64_t>(), val_in, e->g_val2.as<uint64_t>(), nocc, 0, 64, ctx->stream));
-            ENSURE(tmp, tb);
-            CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, keys_in, e->g_keys2.as<uint64_t>(), val_in, e->g_val2.as<uint64_t>(), nocc, 0, 64, ctx->stream));
-            hipLaunchKernelGGL(egr_seg_split_kernel, blocks(nocc), dim3(256), 0, ctx->stream, nocc, e->g_val2.as<uint64_t>(), e->g_dist2.as<uint32_t>(), e->g_wgt2.as<uint32_t>());
-        } else if (pk) {
-            int rc = pk->wide? ec_sort_packed<uint64_t>(ctx, e, *pk, dist_in, nocc) : ec_sort_packed<uint32_t>(ctx, e, *pk, dist_in, nocc);
-            if (rc) return rc;
-        } else {
-            CK(rocprim::radix_sort_pairs(nullptr, tb, keys_in, e->g_keys2.as<uint64_t>(), dist_in, e->g_dist2.as<uint32_t>(), nocc, 0, 64, ctx->stream));
-            ENSURE(tmp, tb);
-            CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, keys_in, e->g_keys2.as<uint64_t>(), dist_in, e->g_dist2.as<uint32_t>(), nocc, 0, 64, ctx->stream));
+            PRIM(rocprim::radix_sort_pairs, keys_in, e->g_keys2.as<uint64_t>(), val_in, e->g_val2.as<uint64_t>(), nocc, 0, 64, ctx->stream);
+            hipLaunchKernelGGL(egr_seg_split_kernel, grid256(nocc), dim3(256), 0, ctx->stream, nocc, e->g_val2.as<uint64_t>(), e->g_dist2.as<uint32_t>(), e->g_wgt2.as<uint32_t>());
+            PRIM(rocprim::run_length_encode, e->g_keys2.as<uint64_t>(), (unsigned int) nocc, e->g_ukeys.as<uint64_t>(), counts, d_nruns, ctx->stream);
         }
-        if (!pk) {
-            tb = 0;
-            CK(rocprim::run_length_encode(nullptr, tb, e->g_keys2.as<uint64_t>(), (unsigned int) nocc, e->g_ukeys.as<uint64_t>(), e->g_counts.as<uint32_t>(),
-                                          e->g_nruns.as<uint32_t>(), ctx->stream));
-            ENSURE(tmp, tb);
-            CK(rocprim::run_length_encode(ctx->tmp.p, tb, e->g_keys2.as<uint64_t>(), (unsigned int) nocc, e->g_ukeys.as<uint64_t>(), e->g_counts.as<uint32_t>(),
-                                          e->g_nruns.as<uint32_t>(), ctx->stream));
-        }
+        // packed keys: from bit 0 (DESIGN.md 6: rocPRIM's small-input paths and ranges that start higher); the distinct keys go where the unsorted ones were
+        else if (pk && pk->wide) rc = prim_sort_runs(ctx, (uint64_t *) pk->keys, e->g_keys2.as<uint64_t>(), dist_in, e->g_dist2.as<uint32_t>(), nocc, 0, 2 * pk->B, (uint64_t *) pk->keys, counts, d_nruns);
+        else if (pk) rc = prim_sort_runs(ctx, (uint32_t *) pk->keys, e->g_keys2.as<uint32_t>(), dist_in, e->g_dist2.as<uint32_t>(), nocc, 0, 2 * pk->B, (uint32_t *) pk->keys, counts, d_nruns);
+        else rc = prim_sort_runs(ctx, keys_in, e->g_keys2.as<uint64_t>(), dist_in, e->g_dist2.as<uint32_t>(), nocc, 0, 64, e->g_ukeys.as<uint64_t>(), counts, d_nruns);
+        if (rc) return rc;
         uint32_t n_runs = 0;
         CK(hipMemcpyAsync(&n_runs, e->g_nruns.p, 4, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
         if (pk && n_runs) {
-            if (pk->wide) hipLaunchKernelGGL(egr_unpack_keys_kernel<uint64_t>, blocks(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, (const uint64_t *) pk->keys, pk->B, pk->cand_id, e->g_ukeys.as<uint64_t>());
-            else hipLaunchKernelGGL(egr_unpack_keys_kernel<uint32_t>, blocks(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, (const uint32_t *) pk->keys, pk->B, pk->cand_id, e->g_ukeys.as<uint64_t>());
+            if (pk->wide) hipLaunchKernelGGL(egr_unpack_keys_kernel<uint64_t>, grid256(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, (const uint64_t *) pk->keys, pk->B, pk->cand_id, e->g_ukeys.as<uint64_t>());
+            else hipLaunchKernelGGL(egr_unpack_keys_kernel<uint32_t>, grid256(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, (const uint32_t *) pk->keys, pk->B, pk->cand_id, e->g_ukeys.as<uint64_t>());
         }
         // 2. every distinct key becomes an arc and (unless it is its own) the complementary arc, syncasm.c:264-282
         EENSURE(g_nout, ((uint64_t) n_runs + 1) * 4);
-        hipLaunchKernelGGL(egr_expand_count_kernel, blocks(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, e->g_ukeys.as<uint64_t>(), e->g_nout.as<uint32_t>());
-        { int rc = ec_exclusive_scan_u32(ctx, e, e->g_nout, e->g_nout64, e->g_outoff, n_runs, &na); if (rc) return rc; }
+        hipLaunchKernelGGL(egr_expand_count_kernel, grid256(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, e->g_ukeys.as<uint64_t>(), e->g_nout.as<uint32_t>());
+        { int rc = prim_scan_total_u32(ctx, e->g_nout, e->g_nout64, e->g_outoff, n_runs, &na); if (rc) return rc; }
         // the overlap of each key's arc: K - the most frequent distance of its run (syncasm.c:793-812)
         uint64_t chk = 0;
         EENSURE(g_runls, ((uint64_t) n_runs + 1) * 4); EENSURE(g_runcov, ((uint64_t) n_runs + 1) * 4);
-        { int rc = ec_exclusive_scan_u32(ctx, e, e->g_counts, e->g_cnt64, e->g_runoff, n_runs, &chk); if (rc) return rc; }
+        { int rc = prim_scan_total_u32(ctx, e->g_counts, e->g_cnt64, e->g_runoff, n_runs, &chk); if (rc) return rc; }
         if (n_runs) {
             EENSURE(g_big, ((uint64_t) n_runs + 1) * 8);                     // the list of long runs, and behind it the list of runs with more than 48 distinct distances
             EENSURE(g_huge, EGR_HUGE_SCRATCH);
@@ -508,13 +454,10 @@ static int ec_graph_build(oatk_hip_ctx *ctx, const uint64_t *d_keys, const uint3
         }
         EENSURE(g_akey, (na + 1) * 8); EENSURE(g_aval, (na + 1) * 8); EENSURE(g_skey, (na + 1) * 8); EENSURE(g_sval, (na + 1) * 8);
         if (na) {
-            hipLaunchKernelGGL(egr_expand_kernel, blocks(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, e->g_ukeys.as<uint64_t>(),
+            hipLaunchKernelGGL(egr_expand_kernel, grid256(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, e->g_ukeys.as<uint64_t>(),
                                weighted? e->g_runcov.as<uint32_t>() : e->g_counts.as<uint32_t>(), e->g_runls.as<uint32_t>(), e->g_outoff.as<uint64_t>(), e->g_akey.as<uint64_t>(), e->g_aval.as<uint64_t>());
             // 3. (v, w) order, asmg_arc_sort graph.c:70-83
-            tb = 0;
-            CK(rocprim::radix_sort_pairs(nullptr, tb, e->g_akey.as<uint64_t>(), e->g_skey.as<uint64_t>(), e->g_aval.as<uint64_t>(), e->g_sval.as<uint64_t>(), na, 0, 64, ctx->stream));
-            ENSURE(tmp, tb);
-            CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, e->g_akey.as<uint64_t>(), e->g_skey.as<uint64_t>(), e->g_aval.as<uint64_t>(), e->g_sval.as<uint64_t>(), na, 0, 64, ctx->stream));
+            PRIM(rocprim::radix_sort_pairs, e->g_akey.as<uint64_t>(), e->g_skey.as<uint64_t>(), e->g_aval.as<uint64_t>(), e->g_sval.as<uint64_t>(), na, 0, 64, ctx->stream);
         }
     }
     EENSURE(arc_v, (na + 1) * 8); EENSURE(arc_w, (na + 1) * 8); EENSURE(arc_ls, (na + 1) * 4); EENSURE(arc_cov, (na + 1) * 4); EENSURE(arc_del, na + 8);
@@ -524,7 +467,7 @@ static int ec_graph_build(oatk_hip_ctx *ctx, const uint64_t *d_keys, const uint3
     a.arc_comp = e->g_comp.as<uint8_t>(), a.arc_del = e->arc_del.as<uint8_t>(), a.idx_p = e->idx_p.as<uint64_t>(), a.idx_n = e->idx_n.as<uint32_t>();
     a.flags = e->g_flags.as<uint32_t>();
     if (na) {
-        hipLaunchKernelGGL(egr_unpack_kernel, blocks(na), dim3(256), 0, ctx->stream, a, (const uint64_t *) e->g_skey.p, (const uint64_t *) e->g_sval.p);
+        hipLaunchKernelGGL(egr_unpack_kernel, grid256(na), dim3(256), 0, ctx->stream, a, (const uint64_t *) e->g_skey.p, (const uint64_t *) e->g_sval.p);
     }
     uint32_t fl[4] = {0, 0, 0, 0};
     CK(hipMemcpyAsync(fl, e->g_flags.p, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
@@ -560,23 +503,6 @@ extern "C" int oatk_hip_ec_graph(oatk_hip_ctx *ctx)
     return oatk_hip_ec_graph_from_pairs(ctx, (const uint64_t *) k, (const uint32_t *) d, n);
 }
 
-// out = the entries of `in` whose flag is set (count on the host)
-template <class T>
-static int ec_select(oatk_hip_ctx *ctx, EcState *e, const T *in, const uint8_t *flag, uint64_t n, T *out, uint64_t *n_out)
-{
-    *n_out = 0;
-    if (n == 0) return OATK_OK;
-    EENSURE(g_nruns, 64);
-    uint64_t *d_cnt = e->g_nruns.as<uint64_t>() + 2;
-    size_t tb = 0;
-    CK(rocprim::select(nullptr, tb, in, flag, out, d_cnt, n, ctx->stream));
-    ENSURE(tmp, tb);
-    CK(rocprim::select(ctx->tmp.p, tb, in, flag, out, d_cnt, n, ctx->stream));
-    CK(hipMemcpyAsync(n_out, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    return OATK_OK;
-}
-
 // the pairs a light graph is made of (ecgraph.hpp, egr_pair_light_wave_kernel): both ends seen at least `c` times; the others leave their mark
 // in g_other, one byte per oriented vertex.  Keys of 64 bits on vertex ids: what the sharded round exchanges (api_multi.inc), and the light graph of a single
 // handle under OATK_DEBUG_EC_LIGHT_PACKED=0; otherwise that one takes ec_light_packed below
@@ -602,10 +528,7 @@ static int ec_light_pairs(oatk_hip_ctx *ctx, uint32_t c, const uint64_t **d_keys
         uint32_t *pos = e->g_keys2.as<uint32_t>();
         uint64_t *d_cnt = e->g_nruns.as<uint64_t>() + 2;
         auto flags = rocprim::make_transform_iterator(e->g_keep.as<uint8_t>(), [] __device__(uint8_t f) -> uint32_t { return f; });
-        size_t tb = 0;
-        CK(rocprim::exclusive_scan(nullptr, tb, flags, pos, 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::exclusive_scan(ctx->tmp.p, tb, flags, pos, 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
+        PRIM(rocprim::exclusive_scan, flags, pos, 0u, n, rocprim::plus<uint32_t>(), ctx->stream);
         hipLaunchKernelGGL(egr_compact_pairs_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, n, e->g_keep.as<uint8_t>(), pos, e->g_keys.as<uint64_t>(),
                            e->g_dist.as<uint32_t>(), e->g_lkeys.as<uint64_t>(), e->g_ldist.as<uint32_t>(), d_cnt);
         CK(hipMemcpyAsync(&nk, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -620,7 +543,6 @@ static int ec_light_pairs(oatk_hip_ctx *ctx, uint32_t c, const uint64_t **d_keys
 // the views the EC kernels work on (local ids, or global ids with sharded reads)
 #define EC_VIEWS()                                                                                                                       \
     const uint64_t nv = e->g_n_vtx, na = e->g_n_arc, nr = ctx->n_reads, nocc = ctx->n_occ;                                               \
-    auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };                                 \
     EcGraph g;                                                                                                                           \
     g.n_vtx = nv, g.n_arc = na, g.idx_p = e->idx_p.as<uint64_t>(), g.idx_n = e->idx_n.as<uint32_t>();                                    \
     g.arc_v = e->arc_v.as<uint64_t>(), g.arc_w = e->arc_w.as<uint64_t>(), g.arc_ls = e->arc_ls.as<uint32_t>(), g.arc_cov = e->arc_cov.as<uint32_t>(); \
@@ -631,27 +553,26 @@ static int ec_light_pairs(oatk_hip_ctx *ctx, uint32_t c, const uint64_t **d_keys
     EcReads rd;                                                                                                                          \
     rd.n_reads = nr, rd.sid0 = ctx->sid0, rd.K = ctx->K, rd.hoco_s = ctx->hoco_s.as<uint8_t>(), rd.off = ctx->d_off, rd.hoco_l = ctx->hoco_l.as<uint32_t>(); \
     rd.scm_off = ctx->scm_off.as<uint64_t>(), rd.k_mer = ec_chains(ctx), rd.m_pos = ctx->pos_mpos.as<uint32_t>();                        \
-    (void) nocc; (void) blocks; (void) rd
+    (void) nocc; (void) rd
 
 // the reference's own graph, flattened by the host, replaces a resident one
 static int ec_upload_graph(oatk_hip_ctx *ctx, const oatk_ec_graph_t *hg)
 {
     EcState *e = ctx->ec;
     const uint64_t nv = hg->n_vtx, na = hg->n_arc;
-    auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };
     e->graph_resident = false, e->light_c = 0;
 
     EENSURE(idx_p, (2 * nv + 1) * 8); EENSURE(idx_n, (2 * nv + 1) * 4); EENSURE(conv, (2 * nv + na + 2) * 8);
     EENSURE(arc_v, (na + 1) * 8); EENSURE(arc_w, (na + 1) * 8); EENSURE(arc_ls, (na + 1) * 4); EENSURE(arc_cov, (na + 1) * 4); EENSURE(arc_del, na + 8);
     CK(hipMemcpyAsync(e->idx_p.p, hg->idx_p, 2 * nv * 8, hipMemcpyHostToDevice, ctx->stream));
     CK(hipMemcpyAsync(e->conv.p, hg->idx_n, 2 * nv * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(ec_narrow_kernel, blocks(2 * nv), dim3(256), 0, ctx->stream, e->conv.as<uint64_t>(), e->idx_n.as<uint32_t>(), 2 * nv);
+    hipLaunchKernelGGL(ec_narrow_kernel, grid256(2 * nv), dim3(256), 0, ctx->stream, e->conv.as<uint64_t>(), e->idx_n.as<uint32_t>(), 2 * nv);
     if (na) {
         CK(hipMemcpyAsync(e->arc_v.p, hg->arc_v, na * 8, hipMemcpyHostToDevice, ctx->stream));
         CK(hipMemcpyAsync(e->arc_w.p, hg->arc_w, na * 8, hipMemcpyHostToDevice, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));          // conv is reused below
         CK(hipMemcpyAsync(e->conv.p, hg->arc_ls, na * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(ec_narrow_kernel, blocks(na), dim3(256), 0, ctx->stream, e->conv.as<uint64_t>(), e->arc_ls.as<uint32_t>(), na);
+        hipLaunchKernelGGL(ec_narrow_kernel, grid256(na), dim3(256), 0, ctx->stream, e->conv.as<uint64_t>(), e->arc_ls.as<uint32_t>(), na);
         CK(hipMemcpyAsync(e->arc_cov.p, hg->arc_cov, na * 4, hipMemcpyHostToDevice, ctx->stream));
         CK(hipMemcpyAsync(e->arc_del.p, hg->arc_del, na, hipMemcpyHostToDevice, ctx->stream));
     }
@@ -683,10 +604,10 @@ extern "C" int oatk_hip_ec_mark(oatk_hip_ctx *ctx, uint32_t err_mer_c, uint32_t 
     if (na) CK(hipMemsetAsync(e->arc_del.p, 0, na, ctx->stream));           // a previous correction marked arcs (a host graph brings its own flags)
     CK(hipMemsetAsync(e->vtx_hs_off.p, 0xFF, (nv + 1) * 8, ctx->stream));   // EC_NO_SRC
     const uint64_t nl = ctx->n_scm_total;
-    if (nl) hipLaunchKernelGGL(ec_vtx_src_kernel, blocks(nl), dim3(256), 0, ctx->stream, nl, ctx->scm_loc.as<uint64_t>(),
+    if (nl) hipLaunchKernelGGL(ec_vtx_src_kernel, grid256(nl), dim3(256), 0, ctx->stream, nl, ctx->scm_loc.as<uint64_t>(),
                                e->global? e->g_l2g.as<uint32_t>() : (const uint32_t *) nullptr, e->vtx_hs_off.as<uint64_t>(), e->vtx_mpos.as<uint32_t>());
-    hipLaunchKernelGGL(ec_mark_kernel, blocks(nv), dim3(256), 0, ctx->stream, g, err_mer_c, max_err_c, err_arc_c, max_arc_f);
-    if (na) hipLaunchKernelGGL(ec_arc_del_kernel, blocks(na), dim3(256), 0, ctx->stream, g);
+    hipLaunchKernelGGL(ec_mark_kernel, grid256(nv), dim3(256), 0, ctx->stream, g, err_mer_c, max_err_c, err_arc_c, max_arc_f);
+    if (na) hipLaunchKernelGGL(ec_arc_del_kernel, grid256(na), dim3(256), 0, ctx->stream, g);
     CK(hipMemcpyAsync(e->err_del.p, e->scm_del.p, nv, hipMemcpyDeviceToDevice, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
     CK(hipGetLastError());
@@ -783,15 +704,6 @@ static EcKnobs ec_knobs_read()
     return k;
 }
 
-static int ec_scan_u32(oatk_hip_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n)
-{
-    size_t tb = 0;
-    CK(rocprim::exclusive_scan(nullptr, tb, in, out, 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
-    ENSURE(tmp, tb);
-    CK(rocprim::exclusive_scan(ctx->tmp.p, tb, in, out, 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
-    return OATK_OK;
-}
-
 // The light graph of a handle in local ids, on candidate ranks (ecgraph.hpp): the rank table, the kept pairs with packed keys -- by a lane per chain entry in
 // two passes, or (pairs_old) by the three kernels of ec_light_pairs with the packing in the compaction -- and ec_graph_build's entry for packed keys.
 // One wait on the host brings the number of candidates and of kept pairs; pairs_old has a second one, because its compaction needs the key width first.
@@ -802,7 +714,6 @@ static int ec_light_packed(oatk_hip_ctx *ctx, uint32_t c, bool pairs_old, bool f
     const uint64_t nv = ec_n_vtx(ctx), nr = ctx->n_reads, n = ctx->n_occ, nw = (nv + 63) / 64, nwg = (nr + 255) / 256;
     if (n >= 0xFFFFFFFFULL) { ctx->err = "more than 2^32 adjacent pairs"; return OATK_E_ARG; }
     if (nv >= 0x7FFFFFFFULL) { ctx->err = "too many syncmers for 32-bit oriented vertex ids"; return OATK_E_ARG; }
-    auto blocks = [](uint64_t x) { return dim3((unsigned) ((x + 255) / 256 > 0? (x + 255) / 256 : 1)); };
     EENSURE(g_other, 2 * nv + 8); EENSURE(g_cbits, (nw + 1) * 8); EENSURE(g_wcnt, (nw + 1) * 4); EENSURE(g_wpre, (nw + 1) * 4);
     EENSURE(g_gcnt, (nwg + 1) * 4); EENSURE(g_gpre, (nwg + 1) * 4); EENSURE(g_nruns, 64);
     t_begin(ctx, OATK_T_EC_GRAPH);
@@ -816,22 +727,19 @@ static int ec_light_packed(oatk_hip_ctx *ctx, uint32_t c, bool pairs_old, bool f
         const uint32_t *wpre = e->g_wpre.as<uint32_t>();
         const uint64_t *scm_off = ctx->scm_off.as<uint64_t>(), *chains = ec_chains(ctx);
         const uint32_t *mpos = ctx->pos_mpos.as<uint32_t>();
-        hipLaunchKernelGGL(egr_cand_flag_kernel, blocks(nv), dim3(256), 0, ctx->stream, nv, nw, ctx->scm_cov.as<uint32_t>(), c, e->g_cbits.as<uint64_t>(), e->g_wcnt.as<uint32_t>());
-        if ((rc = ec_scan_u32(ctx, e->g_wcnt.as<uint32_t>(), e->g_wpre.as<uint32_t>(), nw + 1)) != OATK_OK) return rc;
+        hipLaunchKernelGGL(egr_cand_flag_kernel, grid256(nv), dim3(256), 0, ctx->stream, nv, nw, ctx->scm_cov.as<uint32_t>(), c, e->g_cbits.as<uint64_t>(), e->g_wcnt.as<uint32_t>());
+        PRIM(rocprim::exclusive_scan, e->g_wcnt.as<const uint32_t>(), e->g_wpre.as<uint32_t>(), 0u, nw + 1, rocprim::plus<uint32_t>(), ctx->stream);
         CK(hipMemcpyAsync(&n_cand, e->g_wpre.as<uint32_t>() + nw, 4, hipMemcpyDeviceToHost, ctx->stream));
         if (pairs_old) {
             EENSURE(g_keys, (n + 1) * 8); EENSURE(g_dist, (n + 1) * 4); EENSURE(g_keep, n + 8); EENSURE(g_keys2, (n + 1) * 8);
             hipLaunchKernelGGL(egr_pair_light_wave_kernel, dim3((unsigned) ((nr + 3) / 4)), dim3(256), 0, ctx->stream, nr, scm_off, chains, mpos, ctx->scm_cov.as<uint32_t>(), c,
                                e->g_keys.as<uint64_t>(), e->g_dist.as<uint32_t>(), e->g_keep.as<uint8_t>(), e->g_other.as<uint8_t>());
             auto flags = rocprim::make_transform_iterator(e->g_keep.as<uint8_t>(), [] __device__(uint8_t f) -> uint32_t { return f; });
-            size_t tb = 0;
-            CK(rocprim::exclusive_scan(nullptr, tb, flags, e->g_keys2.as<uint32_t>(), 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
-            ENSURE(tmp, tb);
-            CK(rocprim::exclusive_scan(ctx->tmp.p, tb, flags, e->g_keys2.as<uint32_t>(), 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
+            PRIM(rocprim::exclusive_scan, flags, e->g_keys2.as<uint32_t>(), 0u, n, rocprim::plus<uint32_t>(), ctx->stream);
         } else {
             hipLaunchKernelGGL((egr_pair_entry_kernel<uint32_t, false>), dim3((unsigned) nwg), dim3(256), 0, ctx->stream, nr, scm_off, chains, mpos, bits, wpre, 0u,
                                e->g_gcnt.as<uint32_t>(), (const uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint8_t *) nullptr);
-            if ((rc = ec_scan_u32(ctx, e->g_gcnt.as<uint32_t>(), e->g_gpre.as<uint32_t>(), nwg + 1)) != OATK_OK) return rc;
+            PRIM(rocprim::exclusive_scan, e->g_gcnt.as<const uint32_t>(), e->g_gpre.as<uint32_t>(), 0u, nwg + 1, rocprim::plus<uint32_t>(), ctx->stream);
             CK(hipMemcpyAsync(&nk32, e->g_gpre.as<uint32_t>() + nwg, 4, hipMemcpyDeviceToHost, ctx->stream));
         }
         CK(hipStreamSynchronize(ctx->stream));
@@ -842,12 +750,12 @@ static int ec_light_packed(oatk_hip_ctx *ctx, uint32_t c, bool pairs_old, bool f
         const uint64_t cap = pairs_old? n : (uint64_t) nk32;
         EENSURE(g_lkeys, (cap + 1) * (pk.wide? 8 : 4)); EENSURE(g_ldist, (cap + 1) * 4); EENSURE(g_candid, ((uint64_t) n_cand + 1) * 4);
         pk.keys = e->g_lkeys.p, pk.cand_id = e->g_candid.as<uint32_t>();
-        if (n_cand) hipLaunchKernelGGL(egr_cand_id_kernel, blocks(nv), dim3(256), 0, ctx->stream, nv, bits, wpre, e->g_candid.as<uint32_t>());
+        if (n_cand) hipLaunchKernelGGL(egr_cand_id_kernel, grid256(nv), dim3(256), 0, ctx->stream, nv, bits, wpre, e->g_candid.as<uint32_t>());
         if (pairs_old) {
             uint64_t *d_cnt = e->g_nruns.as<uint64_t>() + 2;
-            if (pk.wide) hipLaunchKernelGGL(egr_compact_pack_kernel<uint64_t>, blocks(n), dim3(256), 0, ctx->stream, n, e->g_keep.as<uint8_t>(), e->g_keys2.as<uint32_t>(), e->g_keys.as<uint64_t>(),
+            if (pk.wide) hipLaunchKernelGGL(egr_compact_pack_kernel<uint64_t>, grid256(n), dim3(256), 0, ctx->stream, n, e->g_keep.as<uint8_t>(), e->g_keys2.as<uint32_t>(), e->g_keys.as<uint64_t>(),
                                             e->g_dist.as<uint32_t>(), bits, wpre, pk.B, e->g_lkeys.as<uint64_t>(), e->g_ldist.as<uint32_t>(), d_cnt);
-            else hipLaunchKernelGGL(egr_compact_pack_kernel<uint32_t>, blocks(n), dim3(256), 0, ctx->stream, n, e->g_keep.as<uint8_t>(), e->g_keys2.as<uint32_t>(), e->g_keys.as<uint64_t>(),
+            else hipLaunchKernelGGL(egr_compact_pack_kernel<uint32_t>, grid256(n), dim3(256), 0, ctx->stream, n, e->g_keep.as<uint8_t>(), e->g_keys2.as<uint32_t>(), e->g_keys.as<uint64_t>(),
                                     e->g_dist.as<uint32_t>(), bits, wpre, pk.B, e->g_lkeys.as<uint32_t>(), e->g_ldist.as<uint32_t>(), d_cnt);
             CK(hipMemcpyAsync(&nk, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
             CK(hipStreamSynchronize(ctx->stream));
@@ -1020,10 +928,7 @@ static int ec_sort_longest_first(oatk_hip_ctx *ctx, EcState *e, uint32_t *list, 
 {
     uint32_t *k_in = e->todo2.as<uint32_t>(), *k_out = k_in + (n + 1), *v_out = k_out + (n + 1);
     hipLaunchKernelGGL(ec_route_keys_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), list, n, k_in);
-    size_t tb = 0;
-    CK(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, list, v_out, n, 0, 32, ctx->stream));
-    ENSURE(tmp, tb);
-    CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, k_in, k_out, list, v_out, n, 0, 32, ctx->stream));
+    PRIM(rocprim::radix_sort_pairs, k_in, k_out, list, v_out, n, 0, 32, ctx->stream);
     CK(hipMemcpyAsync(list, v_out, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
     return OATK_OK;
 }
@@ -1052,16 +957,10 @@ static int ec_queue_sort(oatk_hip_ctx *ctx, EcState *e, const uint32_t *list, ui
     uint32_t *v_out = e->qidx.as<uint32_t>() + e->q_used, *k_in = e->qkey.as<uint32_t>() + e->qk_used, *k_out = k_in + (n + 1);
     e->q_used += n, e->qk_used += 2 * (n + 1);
     hipLaunchKernelGGL(ec_queue_keys_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, e->work.as<EcWork>(), list, n, lp_max, end_max, eb, k_in);
-    size_t tb = 0;
-    if (list) {
-        CK(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, list, v_out, n, 0, (unsigned) (eb + lb), st));
-        if (!tmp.ensure(tb, st)) { ctx->err = "hipMalloc failed (EC queue sort)"; return OATK_E_NOMEM; }
-        CK(rocprim::radix_sort_pairs(tmp.p, tb, k_in, k_out, list, v_out, n, 0, (unsigned) (eb + lb), st));
-    } else {
+    if (list) PRIM_IN(tmp, st, "hipMalloc failed (EC queue sort)", rocprim::radix_sort_pairs, k_in, k_out, list, v_out, n, 0, (unsigned) (eb + lb), st);
+    else {
         rocprim::counting_iterator<uint32_t> iota(0);
-        CK(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, iota, v_out, n, 0, (unsigned) (eb + lb), st));
-        if (!tmp.ensure(tb, st)) { ctx->err = "hipMalloc failed (EC queue sort)"; return OATK_E_NOMEM; }
-        CK(rocprim::radix_sort_pairs(tmp.p, tb, k_in, k_out, iota, v_out, n, 0, (unsigned) (eb + lb), st));
+        PRIM_IN(tmp, st, "hipMalloc failed (EC queue sort)", rocprim::radix_sort_pairs, k_in, k_out, iota, v_out, n, 0, (unsigned) (eb + lb), st);
     }
     *sorted = v_out;
     return OATK_OK;
@@ -1491,14 +1390,14 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
         EENSURE(g_flags, 64);
         CK(hipMemsetAsync(e->g_flags.as<uint32_t>() + 8, 0, 12, ctx->stream));         // [8] a live vertex without its k-mer here, [9] the live graph branches, [10] a block beyond a read's staging entries
         EENSURE(live32, (na + 1) * 4); EENSURE(lidx_p, (2 * nv + 1) * 4); EENSURE(lidx_n, (2 * nv + 1) * 4);
-        if (na) hipLaunchKernelGGL(ec_live_flag_kernel, blocks(na), dim3(256), 0, ctx->stream, na, (const uint8_t *) e->arc_del.p, e->live32.as<uint32_t>());
-        { int rc = ec_exclusive_scan_u32(ctx, e, e->live32, e->live64, e->live_off, na, &n_live); if (rc) return rc; }
+        if (na) hipLaunchKernelGGL(ec_live_flag_kernel, grid256(na), dim3(256), 0, ctx->stream, na, (const uint8_t *) e->arc_del.p, e->live32.as<uint32_t>());
+        { int rc = prim_scan_total_u32(ctx, e->live32, e->live64, e->live_off, na, &n_live); if (rc) return rc; }
         if (n_live >= 0xFFFFFFFFULL) { ctx->err = "error correction: more than 2^32 live arcs"; return OATK_E_ARG; }
         EENSURE(larc, (n_live + 1) * sizeof(EcLiveArc));
         e->n_live = n_live;
-        hipLaunchKernelGGL(ec_live_idx_kernel, blocks(2 * nv), dim3(256), 0, ctx->stream, 2 * nv, e->idx_p.as<uint64_t>(), e->idx_n.as<uint32_t>(),
+        hipLaunchKernelGGL(ec_live_idx_kernel, grid256(2 * nv), dim3(256), 0, ctx->stream, 2 * nv, e->idx_p.as<uint64_t>(), e->idx_n.as<uint32_t>(),
                            e->live_off.as<uint64_t>(), e->lidx_p.as<uint32_t>(), e->lidx_n.as<uint32_t>(), e->g_flags.as<uint32_t>() + 9);
-        if (na) hipLaunchKernelGGL(ec_live_arc_kernel, blocks(na), dim3(256), 0, ctx->stream, na, (const uint8_t *) e->arc_del.p, e->live_off.as<uint64_t>(),
+        if (na) hipLaunchKernelGGL(ec_live_arc_kernel, grid256(na), dim3(256), 0, ctx->stream, na, (const uint8_t *) e->arc_del.p, e->live_off.as<uint64_t>(),
                                    e->arc_w.as<uint64_t>(), e->arc_ls.as<uint32_t>(), e->vtx_hs_off.as<uint64_t>(), e->vtx_mpos.as<uint32_t>(),
                                    e->lidx_p.as<uint32_t>(), e->lidx_n.as<uint32_t>(), e->larc.as<EcLiveArc>(), e->g_flags.as<uint32_t>() + 8);
         uint32_t fl[2] = {0, 0};
@@ -1528,20 +1427,20 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
         CK(hipMemcpyAsync(&e->staged_over, e->g_flags.as<uint32_t>() + 10, 4, hipMemcpyDeviceToHost, ctx->stream));       // (waited for with the scan's total)
     }
     uint64_t n_work = 0;
-    { int rc = ec_exclusive_scan_u32(ctx, e, e->n_blocks, e->n_blocks64, e->blk_off, nr, &n_work); if (rc) return rc; }
+    { int rc = prim_scan_total_u32(ctx, e->n_blocks, e->n_blocks64, e->blk_off, nr, &n_work); if (rc) return rc; }
     if (e->staged_over) { ctx->err = "error correction: a read has more error blocks than syncmers + 1 (the block walk's staging array)"; return OATK_E_STATE; }
     EENSURE(work, (n_work + 1) * sizeof(EcWork)); EENSURE(out, (n_work + 1) * sizeof(EcBlockOut));
     e->n_work = n_work;
     EENSURE(seg, (n_work + 1) * sizeof(EcSeg));
     if (kn.list_walk) hipLaunchKernelGGL(ec_list_blocks_wave_kernel, rblocks, dim3(256), 0, ctx->stream, rd, lv, (const uint8_t *) e->scm_del.p, e->blk_off.as<uint64_t>(), e->work.as<EcWork>(),
                                          e->copy_n.as<uint32_t>(), e->seg.as<EcSeg>(), e->keep_all.as<uint8_t>());
-    else hipLaunchKernelGGL(ec_fill_work_kernel, blocks(nr), dim3(256), 0, ctx->stream, rd, lv, e->blk_off.as<uint64_t>(), (const EcSeg *) e->val_occ.as<EcSeg>(), e->work.as<EcWork>(), e->seg.as<EcSeg>());
+    else hipLaunchKernelGGL(ec_fill_work_kernel, grid256(nr), dim3(256), 0, ctx->stream, rd, lv, e->blk_off.as<uint64_t>(), (const EcSeg *) e->val_occ.as<EcSeg>(), e->work.as<EcWork>(), e->seg.as<EcSeg>());
     // a fixed slot per block for its optimum consensus (oatk_hip_ec_keep_seq): no atomics, no overflow, and the same addresses whichever launch finishes a block
     if (keep_seq) {
         uint64_t slot_words = 0;
         EENSURE(slot_w, (n_work + 1) * 4); EENSURE(qend, (n_work + 1) * 4);
-        if (n_work) hipLaunchKernelGGL(ec_slot_words_kernel, blocks(n_work), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), n_work, max_edist, e->slot_w.as<uint32_t>());
-        { int rc = ec_exclusive_scan_u32(ctx, e, e->slot_w, e->slot_w64, e->slot_off, n_work, &slot_words); if (rc) return rc; }
+        if (n_work) hipLaunchKernelGGL(ec_slot_words_kernel, grid256(n_work), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), n_work, max_edist, e->slot_w.as<uint32_t>());
+        { int rc = prim_scan_total_u32(ctx, e->slot_w, e->slot_w64, e->slot_off, n_work, &slot_words); if (rc) return rc; }
         EENSURE(slots, (slot_words + 4) * 4);
     }
     t_end(ctx, OATK_T_EC_MARK);
@@ -1594,10 +1493,10 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     if (n_work) hipLaunchKernelGGL(ec_block_stats_kernel, dim3((unsigned) (n_work / 256 + 1 < 512? n_work / 256 + 1 : 512)), dim3(256), 0, ctx->stream, e->work.as<EcWork>(),
                                    e->out.as<EcBlockOut>(), n_work, (unsigned long long *) e->stats.p);
     // the chains' lengths and then the chains from the descriptors the list walk left, nobody walking a chain again (ec.hpp: EcSeg)
-    if (kn.assemble_walk) hipLaunchKernelGGL(ec_new_n_kernel, blocks(nr), dim3(256), 0, ctx->stream, nr, e->copy_n.as<uint32_t>(), e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->out.as<EcBlockOut>(), e->new_n.as<uint32_t>());
-    else hipLaunchKernelGGL(ec_new_n_seg_kernel, blocks(nr), dim3(256), 0, ctx->stream, nr, e->copy_n.as<uint32_t>(), e->blk_off.as<uint64_t>(), e->seg.as<EcSeg>(), e->out.as<EcBlockOut>(), e->new_n.as<uint32_t>());
+    if (kn.assemble_walk) hipLaunchKernelGGL(ec_new_n_kernel, grid256(nr), dim3(256), 0, ctx->stream, nr, e->copy_n.as<uint32_t>(), e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->out.as<EcBlockOut>(), e->new_n.as<uint32_t>());
+    else hipLaunchKernelGGL(ec_new_n_seg_kernel, grid256(nr), dim3(256), 0, ctx->stream, nr, e->copy_n.as<uint32_t>(), e->blk_off.as<uint64_t>(), e->seg.as<EcSeg>(), e->out.as<EcBlockOut>(), e->new_n.as<uint32_t>());
     uint64_t tot = 0;
-    { int rc = ec_exclusive_scan_u32(ctx, e, e->new_n, e->new_n64, e->new_off, nr, &tot); if (rc) return rc; }
+    { int rc = prim_scan_total_u32(ctx, e->new_n, e->new_n64, e->new_off, nr, &tot); if (rc) return rc; }
     e->new_tot = tot;
     EENSURE(new_k, (tot + 1) * 8); EENSURE(new_m, (tot + 1) * 4); EENSURE(new_s, (tot + 1) * 8);
     // (val_occ held the block walk's staging entries until ec_fill_work_kernel had read them, "blocks" above: nothing may write it between the two)
@@ -1612,24 +1511,19 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     CK(hipMemsetAsync(e->cov.p, 0, (nv + 1) * 4, ctx->stream));
     CK(hipMemsetAsync(e->fwd.p, 0, (nv + 1) * 4, ctx->stream));
     if (tot) {
-        size_t tb = 0;      // stable: occurrences of one syncmer stay in (sid, idx) order (syncerr.c:796-805)
         unsigned id_bits = 1;   // the keys are syncmer ids: the passes stop at the id's highest bit
         while (id_bits < 32 && (nv - 1) >> id_bits) ++id_bits;
-        CK(rocprim::radix_sort_pairs(nullptr, tb, e->key_id.as<uint32_t>(), e->key_sorted.as<uint32_t>(), e->val_occ.as<uint64_t>(), e->occ.as<uint64_t>(), tot, 0, id_bits, ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, e->key_id.as<uint32_t>(), e->key_sorted.as<uint32_t>(), e->val_occ.as<uint64_t>(), e->occ.as<uint64_t>(), tot, 0, id_bits, ctx->stream));
+        // stable: occurrences of one syncmer stay in (sid, idx) order (syncerr.c:796-805)
+        PRIM(rocprim::radix_sort_pairs, e->key_id.as<uint32_t>(), e->key_sorted.as<uint32_t>(), e->val_occ.as<uint64_t>(), e->occ.as<uint64_t>(), tot, 0, id_bits, ctx->stream);
         // coverage and forward-strand counts per syncmer from the sorted lists (key_id is free again: it carries the flags and their prefix sums)
-        hipLaunchKernelGGL(ec_fwd_flag_kernel, blocks(tot), dim3(256), 0, ctx->stream, tot, e->occ.as<uint64_t>(), e->key_id.as<uint32_t>());
-        tb = 0;
-        CK(rocprim::inclusive_scan(nullptr, tb, e->key_id.as<uint32_t>(), e->key_id.as<uint32_t>(), tot, rocprim::plus<uint32_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::inclusive_scan(ctx->tmp.p, tb, e->key_id.as<uint32_t>(), e->key_id.as<uint32_t>(), tot, rocprim::plus<uint32_t>(), ctx->stream));
-        hipLaunchKernelGGL(ec_cov_sorted_kernel, blocks(tot), dim3(256), 0, ctx->stream, tot, e->key_sorted.as<uint32_t>(), e->key_id.as<uint32_t>(),
+        hipLaunchKernelGGL(ec_fwd_flag_kernel, grid256(tot), dim3(256), 0, ctx->stream, tot, e->occ.as<uint64_t>(), e->key_id.as<uint32_t>());
+        PRIM(rocprim::inclusive_scan, e->key_id.as<uint32_t>(), e->key_id.as<uint32_t>(), tot, rocprim::plus<uint32_t>(), ctx->stream);
+        hipLaunchKernelGGL(ec_cov_sorted_kernel, grid256(tot), dim3(256), 0, ctx->stream, tot, e->key_sorted.as<uint32_t>(), e->key_id.as<uint32_t>(),
                            e->cov.as<uint32_t>(), e->fwd.as<uint32_t>());
     }
-    hipLaunchKernelGGL(ec_del_kernel, blocks(nv), dim3(256), 0, ctx->stream, nv, e->fwd.as<uint32_t>(), e->scm_del.as<uint8_t>());
+    hipLaunchKernelGGL(ec_del_kernel, grid256(nv), dim3(256), 0, ctx->stream, nv, e->fwd.as<uint32_t>(), e->scm_del.as<uint8_t>());
     uint64_t chk = 0;
-    { int rc = ec_exclusive_scan_u32(ctx, e, e->cov, e->cov64, e->occ_off, nv, &chk); if (rc) return rc; }
+    { int rc = prim_scan_total_u32(ctx, e->cov, e->cov64, e->occ_off, nv, &chk); if (rc) return rc; }
     unsigned long long st[16];
     CK(hipMemcpyAsync(st, e->stats.p, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
     t_end(ctx, OATK_T_EC_REFRESH);
@@ -1676,10 +1570,10 @@ extern "C" int oatk_hip_ec_corrected_reads(oatk_hip_ctx *ctx, uint64_t *n_bases)
     if (stages) for (int i = 0; i < 3; ++i) CK(hipEventCreate(&ev[i]));
     EENSURE(sblk, (n_work + nr + 1) * sizeof(EcSeqBlk)); EENSURE(clen, (nr + 1) * 4); EENSURE(cbytes, (nr + 1) * 4);
     if (stages) CK(hipEventRecord(ev[0], ctx->stream));
-    if (nr) hipLaunchKernelGGL(ec_cseq_len_kernel, blocks(nr), dim3(256), 0, ctx->stream, rd, e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->out.as<EcBlockOut>(), e->qend.as<uint32_t>(),
+    if (nr) hipLaunchKernelGGL(ec_cseq_len_kernel, grid256(nr), dim3(256), 0, ctx->stream, rd, e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->out.as<EcBlockOut>(), e->qend.as<uint32_t>(),
                                e->sblk.as<EcSeqBlk>(), e->clen.as<uint32_t>(), e->cbytes.as<uint32_t>());
     uint64_t bytes = 0;
-    { int rc = ec_exclusive_scan_u32(ctx, e, e->cbytes, e->cbytes64, e->coff, nr, &bytes); if (rc) return rc; }
+    { int rc = prim_scan_total_u32(ctx, e->cbytes, e->cbytes64, e->coff, nr, &bytes); if (rc) return rc; }
     EENSURE(cseq, bytes + 16);
     if (stages) CK(hipEventRecord(ev[1], ctx->stream));
     EcSeqArgs sa;

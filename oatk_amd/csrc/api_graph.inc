@@ -39,10 +39,7 @@ static int ag_buffer(oatk_hip_ctx *ctx, int which, const void **d_ptr, uint64_t 
     return OATK_OK;
 }
 
-#define AGENSURE(buf, bytes)                                                                        \
-    do {                                                                                           \
-        if (!g->buf.ensure((bytes), ctx->stream)) { ctx->err = "hipMalloc failed for graph." #buf; return OATK_E_NOMEM; } \
-    } while (0)
+#define AGENSURE(buf, bytes) ENSURE_IN(g, "graph.", buf, bytes)
 
 // canonical keys of this batch's adjacent pairs: the corrected chains after oatk_hip_ec, the counted ones otherwise
 extern "C" int oatk_hip_asm_pairs(oatk_hip_ctx *ctx, const void **d_keys, uint64_t *n_pairs)
@@ -82,17 +79,16 @@ static int ag_build(oatk_hip_ctx *ctx, const uint64_t *d_keys, const uint32_t *d
     if (!ctx->ag) ctx->ag = new AgState();
     AgState *g = ctx->ag;
     g->done = false;
-    auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };
     AGENSURE(flags, 64);
     CK(hipMemsetAsync(g->flags.p, 0, 64, ctx->stream));
 
     // 1. vertices: coverage filter, squeeze (syncasm.c:226-233, graph.c:153-173)
     uint64_t nv = 0;
     AGENSURE(del, ns + 8); AGENSURE(keep, (ns + 1) * 4);
-    if (ns) hipLaunchKernelGGL(agr_vtx_filter_kernel, blocks(ns), dim3(256), 0, ctx->stream, ns, d_cov, d_del, min_k_cov, g->del.as<uint8_t>(), g->keep.as<uint32_t>());
-    { int rc = ec_exclusive_scan_u32(ctx, nullptr, g->keep, g->keep64, g->vidx, ns, &nv); if (rc) return rc; }
+    if (ns) hipLaunchKernelGGL(agr_vtx_filter_kernel, grid256(ns), dim3(256), 0, ctx->stream, ns, d_cov, d_del, min_k_cov, g->del.as<uint8_t>(), g->keep.as<uint32_t>());
+    { int rc = prim_scan_total_u32(ctx, g->keep, g->keep64, g->vidx, ns, &nv); if (rc) return rc; }
     AGENSURE(vtx_scm, (nv + 1) * 4); AGENSURE(vtx_cov, (nv + 1) * 4);
-    if (ns) hipLaunchKernelGGL(agr_vtx_squeeze_kernel, blocks(ns), dim3(256), 0, ctx->stream, ns, g->del.as<uint8_t>(), g->vidx.as<uint64_t>(), d_cov,
+    if (ns) hipLaunchKernelGGL(agr_vtx_squeeze_kernel, grid256(ns), dim3(256), 0, ctx->stream, ns, g->del.as<uint8_t>(), g->vidx.as<uint64_t>(), d_cov,
                                g->vtx_scm.as<uint32_t>(), g->vtx_cov.as<uint32_t>());
     AGENSURE(idx_p, (2 * nv + 1) * 8); AGENSURE(idx_n, (2 * nv + 1) * 4);
     CK(hipMemsetAsync(g->idx_p.p, 0, (2 * nv + 1) * 8, ctx->stream));
@@ -104,46 +100,29 @@ static int ag_build(oatk_hip_ctx *ctx, const uint64_t *d_keys, const uint32_t *d
     if (nocc) {
         AGENSURE(keys2, (nocc + 1) * 8); AGENSURE(ukeys, (nocc + 1) * 8); AGENSURE(counts, (nocc + 1) * 4); AGENSURE(nruns, 64);
         uint64_t *keys_in = const_cast<uint64_t *>(d_keys);
-        size_t tb = 0;
         if (d_wgt) {
             AGENSURE(wgt2, (nocc + 1) * 4);
             uint32_t *wgt_in = const_cast<uint32_t *>(d_wgt);
-            CK(rocprim::radix_sort_pairs(nullptr, tb, keys_in, g->keys2.as<uint64_t>(), wgt_in, g->wgt2.as<uint32_t>(), nocc, 0, 64, ctx->stream));
-            ENSURE(tmp, tb);
-            CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, keys_in, g->keys2.as<uint64_t>(), wgt_in, g->wgt2.as<uint32_t>(), nocc, 0, 64, ctx->stream));
-            tb = 0;
-            CK(rocprim::reduce_by_key(nullptr, tb, g->keys2.as<uint64_t>(), g->wgt2.as<uint32_t>(), (unsigned int) nocc, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(),
-                                      g->nruns.as<uint32_t>(), rocprim::plus<uint32_t>(), rocprim::equal_to<uint64_t>(), ctx->stream));
-            ENSURE(tmp, tb);
-            CK(rocprim::reduce_by_key(ctx->tmp.p, tb, g->keys2.as<uint64_t>(), g->wgt2.as<uint32_t>(), (unsigned int) nocc, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(),
-                                      g->nruns.as<uint32_t>(), rocprim::plus<uint32_t>(), rocprim::equal_to<uint64_t>(), ctx->stream));
+            PRIM(rocprim::radix_sort_pairs, keys_in, g->keys2.as<uint64_t>(), wgt_in, g->wgt2.as<uint32_t>(), nocc, 0, 64, ctx->stream);
+            PRIM(rocprim::reduce_by_key, g->keys2.as<uint64_t>(), g->wgt2.as<uint32_t>(), (unsigned int) nocc, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(), g->nruns.as<uint32_t>(),
+                 rocprim::plus<uint32_t>(), rocprim::equal_to<uint64_t>(), ctx->stream);
         } else {
-        CK(rocprim::radix_sort_keys(nullptr, tb, keys_in, g->keys2.as<uint64_t>(), nocc, 0, 64, ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::radix_sort_keys(ctx->tmp.p, tb, keys_in, g->keys2.as<uint64_t>(), nocc, 0, 64, ctx->stream));
-        tb = 0;
-        CK(rocprim::run_length_encode(nullptr, tb, g->keys2.as<uint64_t>(), (unsigned int) nocc, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(),
-                                      g->nruns.as<uint32_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::run_length_encode(ctx->tmp.p, tb, g->keys2.as<uint64_t>(), (unsigned int) nocc, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(),
-                                      g->nruns.as<uint32_t>(), ctx->stream));
+            int rc = prim_sort_runs(ctx, keys_in, g->keys2.as<uint64_t>(), (void *) nullptr, (void *) nullptr, nocc, 0, 64, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(), g->nruns.as<uint32_t>());
+            if (rc) return rc;
         }
         CK(hipMemcpyAsync(&n_runs, g->nruns.p, 4, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
         // 3. the arc filter, arcs + complements in the squeezed numbering (syncasm.c:264-282, graph.c:175-200)
         AGENSURE(nout, ((uint64_t) n_runs + 1) * 4);
-        hipLaunchKernelGGL(agr_expand_count_kernel, blocks(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(),
+        hipLaunchKernelGGL(agr_expand_count_kernel, grid256(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(),
                            d_cov, g->del.as<uint8_t>(), min_a_cov_f, g->nout.as<uint32_t>());
-        { int rc = ec_exclusive_scan_u32(ctx, nullptr, g->nout, g->nout64, g->outoff, n_runs, &na); if (rc) return rc; }
+        { int rc = prim_scan_total_u32(ctx, g->nout, g->nout64, g->outoff, n_runs, &na); if (rc) return rc; }
         AGENSURE(akey, (na + 1) * 8); AGENSURE(aval, (na + 1) * 8); AGENSURE(skey, (na + 1) * 8); AGENSURE(sval, (na + 1) * 8);
         if (na) {
-            hipLaunchKernelGGL(agr_expand_kernel, blocks(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(),
+            hipLaunchKernelGGL(agr_expand_kernel, grid256(n_runs), dim3(256), 0, ctx->stream, (uint64_t) n_runs, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(),
                                g->nout.as<uint32_t>(), g->outoff.as<uint64_t>(), g->vidx.as<uint64_t>(), g->akey.as<uint64_t>(), g->aval.as<uint64_t>());
             // 4. (v, w) order, asmg_arc_sort graph.c:70-83
-            tb = 0;
-            CK(rocprim::radix_sort_pairs(nullptr, tb, g->akey.as<uint64_t>(), g->skey.as<uint64_t>(), g->aval.as<uint64_t>(), g->sval.as<uint64_t>(), na, 0, 64, ctx->stream));
-            ENSURE(tmp, tb);
-            CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, g->akey.as<uint64_t>(), g->skey.as<uint64_t>(), g->aval.as<uint64_t>(), g->sval.as<uint64_t>(), na, 0, 64, ctx->stream));
+            PRIM(rocprim::radix_sort_pairs, g->akey.as<uint64_t>(), g->skey.as<uint64_t>(), g->aval.as<uint64_t>(), g->sval.as<uint64_t>(), na, 0, 64, ctx->stream);
         }
     }
     AGENSURE(arc_v, (na + 1) * 8); AGENSURE(arc_w, (na + 1) * 8); AGENSURE(arc_ls, (na + 1) * 4); AGENSURE(arc_cov, (na + 1) * 4); AGENSURE(arc_del, na + 8);
@@ -154,13 +133,13 @@ static int ag_build(oatk_hip_ctx *ctx, const uint64_t *d_keys, const uint32_t *d
         a.n_arc = na, a.arc_v = g->arc_v.as<uint64_t>(), a.arc_w = g->arc_w.as<uint64_t>(), a.arc_ls = g->arc_ls.as<uint32_t>(), a.arc_cov = g->arc_cov.as<uint32_t>();
         a.arc_comp = g->arc_comp.as<uint8_t>(), a.arc_del = g->arc_del.as<uint8_t>(), a.idx_p = g->idx_p.as<uint64_t>(), a.idx_n = g->idx_n.as<uint32_t>();
         a.flags = g->flags.as<uint32_t>();
-        hipLaunchKernelGGL(egr_unpack_kernel, blocks(na), dim3(256), 0, ctx->stream, a, (const uint64_t *) g->skey.p, (const uint64_t *) g->sval.p);
+        hipLaunchKernelGGL(egr_unpack_kernel, grid256(na), dim3(256), 0, ctx->stream, a, (const uint64_t *) g->skey.p, (const uint64_t *) g->sval.p);
         // 6. link ids (graph.c:126-146)
         AGENSURE(opens, (na + 1) * 4); AGENSURE(comp_idx, (na + 1) * 8);
-        hipLaunchKernelGGL(agr_link_first_kernel, blocks(na), dim3(256), 0, ctx->stream, na, (const uint64_t *) g->skey.p, g->opens.as<uint32_t>(), g->comp_idx.as<uint64_t>());
+        hipLaunchKernelGGL(agr_link_first_kernel, grid256(na), dim3(256), 0, ctx->stream, na, (const uint64_t *) g->skey.p, g->opens.as<uint32_t>(), g->comp_idx.as<uint64_t>());
         uint64_t n_link = 0;
-        { int rc = ec_exclusive_scan_u32(ctx, nullptr, g->opens, g->opens64, g->open_rank, na, &n_link); if (rc) return rc; }
-        hipLaunchKernelGGL(agr_link_assign_kernel, blocks(na), dim3(256), 0, ctx->stream, na, g->opens.as<uint32_t>(), g->comp_idx.as<uint64_t>(),
+        { int rc = prim_scan_total_u32(ctx, g->opens, g->opens64, g->open_rank, na, &n_link); if (rc) return rc; }
+        hipLaunchKernelGGL(agr_link_assign_kernel, grid256(na), dim3(256), 0, ctx->stream, na, g->opens.as<uint32_t>(), g->comp_idx.as<uint64_t>(),
                            g->open_rank.as<uint64_t>(), g->link.as<uint64_t>());
     }
     uint32_t fl[4] = {0, 0, 0, 0};

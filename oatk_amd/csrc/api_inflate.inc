@@ -15,10 +15,7 @@ static void inf_state_free(oatk_hip_ctx *ctx)
     ctx->inf = nullptr;
 }
 
-#define FENSURE(buf, bytes)                                                                        \
-    do {                                                                                           \
-        if (!g->buf.ensure((bytes), ctx->stream)) { ctx->err = "hipMalloc failed for inflate." #buf; return OATK_E_NOMEM; } \
-    } while (0)
+#define FENSURE(buf, bytes) ENSURE_IN(g, "inflate.", buf, bytes)
 
 extern "C" int oatk_hip_inflate_bgzf(oatk_hip_ctx *ctx, const uint8_t *d_comp, uint64_t comp_bytes, const oatk_bgzf_member_t *h_members, uint64_t n,
                                      uint8_t *d_text, uint64_t text_cap, uint64_t *n_bad, uint8_t *h_status)
@@ -106,7 +103,7 @@ extern "C" int oatk_hip_ingest_names(oatk_hip_ctx *ctx, const uint8_t *d_text, u
         FENSURE(name_len, (n + 1) * 8); FENSURE(name_off, (n + 1) * 8);
         if (ig->bam) hipLaunchKernelGGL(ing_bam_name_len_kernel, grid, dim3(256), 0, ctx->stream, d_text, n_bytes, ig->hdr_off.as<uint64_t>(), n, g->name_len.as<uint64_t>());
         else hipLaunchKernelGGL(ing_name_len_kernel, grid, dim3(256), 0, ctx->stream, d_text, n_bytes, ig->hdr_off.as<uint64_t>(), n, g->name_len.as<uint64_t>());
-        { int rc = ing_scan_u64(ctx, g->name_len.as<uint64_t>(), g->name_off.as<uint64_t>(), n + 1); if (rc) return rc; }
+        PRIM(rocprim::exclusive_scan, g->name_len.as<const uint64_t>(), g->name_off.as<uint64_t>(), (uint64_t) 0, n + 1, rocprim::plus<uint64_t>(), ctx->stream);
         uint64_t total = 0;
         CK(hipMemcpyAsync(&total, g->name_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));

@@ -35,19 +35,7 @@ static int ing_buffer(oatk_hip_ctx *ctx, int which, const void **d_ptr, uint64_t
     return OATK_OK;
 }
 
-#define GENSURE(buf, bytes)                                                                        \
-    do {                                                                                           \
-        if (!g->buf.ensure((bytes), ctx->stream)) { ctx->err = "hipMalloc failed for ingest." #buf; return OATK_E_NOMEM; } \
-    } while (0)
-
-static int ing_scan_u64(oatk_hip_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n)
-{
-    size_t tb = 0;
-    CK(rocprim::exclusive_scan(nullptr, tb, in, out, (uint64_t) 0, n, rocprim::plus<uint64_t>(), ctx->stream));
-    ENSURE(tmp, tb);
-    CK(rocprim::exclusive_scan(ctx->tmp.p, tb, in, out, (uint64_t) 0, n, rocprim::plus<uint64_t>(), ctx->stream));
-    return OATK_OK;
-}
+#define GENSURE(buf, bytes) ENSURE_IN(g, "ingest.", buf, bytes)
 
 extern "C" int oatk_hip_ingest(oatk_hip_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, int format, int final, uint64_t *n_reads, uint64_t *consumed)
 {
@@ -59,7 +47,6 @@ extern "C" int oatk_hip_ingest(oatk_hip_ctx *ctx, const uint8_t *d_text, uint64_
     g->done = false, g->bam = false, g->n_reads = 0, g->seq_bytes = 0;
     if (n_reads) *n_reads = 0;
     if (consumed) *consumed = 0;
-    auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };
     if (n_bytes == 0) { g->done = true; return OATK_OK; }
     if (format == OATK_FMT_AUTO) {                      // the first character that is not white space
         uint8_t head[256];
@@ -78,8 +65,8 @@ extern "C" int oatk_hip_ingest(oatk_hip_ctx *ctx, const uint8_t *d_text, uint64_
     GENSURE(cnt, (nb + 1) * 4); GENSURE(cnt64, (nb + 1) * 8); GENSURE(blk_off, (nb + 1) * 8); GENSURE(flags, 64);
     CK(hipMemsetAsync(g->flags.p, 0, 64, ctx->stream));
     hipLaunchKernelGGL(ing_count_nl_kernel, dim3((unsigned) nb), dim3(256), 0, ctx->stream, d_text, n_bytes, g->cnt.as<uint32_t>());
-    hipLaunchKernelGGL(ec_widen_kernel, blocks(nb + 1), dim3(256), 0, ctx->stream, g->cnt.as<uint32_t>(), g->cnt64.as<uint64_t>(), nb);
-    { int rc = ing_scan_u64(ctx, g->cnt64.as<uint64_t>(), g->blk_off.as<uint64_t>(), nb + 1); if (rc) return rc; }
+    hipLaunchKernelGGL(widen_kernel, grid256(nb + 1), dim3(256), 0, ctx->stream, g->cnt.as<uint32_t>(), g->cnt64.as<uint64_t>(), nb);
+    PRIM(rocprim::exclusive_scan, g->cnt64.as<const uint64_t>(), g->blk_off.as<uint64_t>(), (uint64_t) 0, nb + 1, rocprim::plus<uint64_t>(), ctx->stream);
     uint64_t n_nl = 0;
     uint8_t last = 0;
     CK(hipMemcpyAsync(&n_nl, g->blk_off.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -147,16 +134,16 @@ extern "C" int oatk_hip_ingest(oatk_hip_ctx *ctx, const uint8_t *d_text, uint64_
             CK(hipMemcpyAsync(g->seq_len.p, sl.data(), (nl + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
             CK(hipStreamSynchronize(ctx->stream));      // (the vectors go out of scope)
         } else {
-            hipLaunchKernelGGL(ing_line_kernel, blocks(nl + 1), dim3(256), 0, ctx->stream, l, g->is_hdr.as<uint64_t>(), g->seq_len.as<uint64_t>(), g->flags.as<uint32_t>());
+            hipLaunchKernelGGL(ing_line_kernel, grid256(nl + 1), dim3(256), 0, ctx->stream, l, g->is_hdr.as<uint64_t>(), g->seq_len.as<uint64_t>(), g->flags.as<uint32_t>());
         }
-        { int rc = ing_scan_u64(ctx, g->is_hdr.as<uint64_t>(), g->hdr_rank.as<uint64_t>(), nl + 1); if (rc) return rc; }
-        { int rc = ing_scan_u64(ctx, g->seq_len.as<uint64_t>(), g->seq_before.as<uint64_t>(), nl + 1); if (rc) return rc; }
+        PRIM(rocprim::exclusive_scan, g->is_hdr.as<const uint64_t>(), g->hdr_rank.as<uint64_t>(), (uint64_t) 0, nl + 1, rocprim::plus<uint64_t>(), ctx->stream);
+        PRIM(rocprim::exclusive_scan, g->seq_len.as<const uint64_t>(), g->seq_before.as<uint64_t>(), (uint64_t) 0, nl + 1, rocprim::plus<uint64_t>(), ctx->stream);
         if (!cut_done) {
             CK(hipMemcpyAsync(&n_hdr, g->hdr_rank.as<uint64_t>() + nl, 8, hipMemcpyDeviceToHost, ctx->stream));
             CK(hipStreamSynchronize(ctx->stream));
         }
         GENSURE(hdr_line, (n_hdr + 2) * 8);
-        hipLaunchKernelGGL(ing_hdr_lines_kernel, blocks(nl), dim3(256), 0, ctx->stream, nl, g->is_hdr.as<uint64_t>(), g->hdr_rank.as<uint64_t>(), g->hdr_line.as<uint64_t>());
+        hipLaunchKernelGGL(ing_hdr_lines_kernel, grid256(nl), dim3(256), 0, ctx->stream, nl, g->is_hdr.as<uint64_t>(), g->hdr_rank.as<uint64_t>(), g->hdr_line.as<uint64_t>());
         CK(hipMemcpyAsync(g->hdr_line.as<uint64_t>() + n_hdr, &line_end, 8, hipMemcpyHostToDevice, ctx->stream));      // sentinel: end of the last record
         CK(hipStreamSynchronize(ctx->stream));          // (line_end lives on this stack frame)
         n_rec = n_hdr;
@@ -179,9 +166,9 @@ extern "C" int oatk_hip_ingest(oatk_hip_ctx *ctx, const uint8_t *d_text, uint64_
             used = 0;
         }
         GENSURE(len, (n_rec + 1) * 4); GENSURE(padded, (n_rec + 2) * 8); GENSURE(off, (n_rec + 2) * 8); GENSURE(hdr_off, (n_rec + 1) * 8);
-        hipLaunchKernelGGL(ing_record_kernel, blocks(n_rec + 1), dim3(256), 0, ctx->stream, l, n_rec, g->hdr_line.as<uint64_t>(), g->seq_before.as<uint64_t>(),
+        hipLaunchKernelGGL(ing_record_kernel, grid256(n_rec + 1), dim3(256), 0, ctx->stream, l, n_rec, g->hdr_line.as<uint64_t>(), g->seq_before.as<uint64_t>(),
                            g->len.as<uint32_t>(), g->padded.as<uint64_t>(), g->hdr_off.as<uint64_t>(), g->flags.as<uint32_t>());
-        { int rc = ing_scan_u64(ctx, g->padded.as<uint64_t>(), g->off.as<uint64_t>(), n_rec + 1); if (rc) return rc; }
+        PRIM(rocprim::exclusive_scan, g->padded.as<const uint64_t>(), g->off.as<uint64_t>(), (uint64_t) 0, n_rec + 1, rocprim::plus<uint64_t>(), ctx->stream);
         uint64_t seq_bytes = 0;
         CK(hipMemcpyAsync(&seq_bytes, g->off.as<uint64_t>() + n_rec, 8, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
@@ -205,9 +192,9 @@ extern "C" int oatk_hip_ingest(oatk_hip_ctx *ctx, const uint8_t *d_text, uint64_
             used = pos;
         }
         GENSURE(len, (n_rec + 1) * 4); GENSURE(padded, (n_rec + 2) * 8); GENSURE(off, (n_rec + 2) * 8); GENSURE(hdr_off, (n_rec + 1) * 8);
-        hipLaunchKernelGGL(ing_fastq_record_kernel, blocks(n_rec + 1), dim3(256), 0, ctx->stream, l, n_rec, g->len.as<uint32_t>(), g->padded.as<uint64_t>(),
+        hipLaunchKernelGGL(ing_fastq_record_kernel, grid256(n_rec + 1), dim3(256), 0, ctx->stream, l, n_rec, g->len.as<uint32_t>(), g->padded.as<uint64_t>(),
                            g->hdr_off.as<uint64_t>(), g->flags.as<uint32_t>());
-        { int rc = ing_scan_u64(ctx, g->padded.as<uint64_t>(), g->off.as<uint64_t>(), n_rec + 1); if (rc) return rc; }
+        PRIM(rocprim::exclusive_scan, g->padded.as<const uint64_t>(), g->off.as<uint64_t>(), (uint64_t) 0, n_rec + 1, rocprim::plus<uint64_t>(), ctx->stream);
         uint64_t seq_bytes = 0;
         CK(hipMemcpyAsync(&seq_bytes, g->off.as<uint64_t>() + n_rec, 8, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));

@@ -158,10 +158,7 @@ static int multi_buffer(oatk_hip_ctx *ctx, int which, const void **d_ptr, uint64
 
 // ---------------------------------------------------------------- the primitives ----------------------------------------------------------------
 
-#define MENSURE(buf, bytes)                                                                        \
-    do {                                                                                           \
-        if (!m->buf.ensure((bytes), ctx->stream)) { ctx->err = "hipMalloc failed for multi." #buf; return OATK_E_NOMEM; } \
-    } while (0)
+#define MENSURE(buf, bytes) ENSURE_IN(m, "multi.", buf, bytes)
 #define NCK(call)                                                                                  \
     do {                                                                                           \
         ncclResult_t r_ = (call);                                                                  \
@@ -656,7 +653,6 @@ static int merge_counts_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint64_t *n_global
     if (!ctx->multi) ctx->multi = new MultiState();
     MultiState *m = ctx->multi;
     m->merged = m->ec_done = false, m->rank = c->rank, m->table_root = -1;
-    auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };
     const uint64_t nl = ctx->n_scm_total;
     const int n = c->n, me = c->rank;
     int rc;
@@ -698,22 +694,17 @@ static int merge_counts_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint64_t *n_global
     const int nw = (ctx->K + 31) / 32;
     CK(hipMemsetAsync(m->need_j.p, 0, (nr + 1) * 4, ctx->stream));
     if (nr) {
-        hipLaunchKernelGGL(mg_iota_kernel, blocks(nr), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), nr);
-        size_t tb = 0;      // stable: within a hash the entries stay in (shard, local) order -- the global first-seen order of its k-mers
-        CK(rocprim::radix_sort_pairs(nullptr, tb, m->recv_h.as<uint64_t>(), m->srt_h.as<uint64_t>(), m->iota.as<uint32_t>(), m->srt_i.as<uint32_t>(), nr, 0, 64, ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, m->recv_h.as<uint64_t>(), m->srt_h.as<uint64_t>(), m->iota.as<uint32_t>(), m->srt_i.as<uint32_t>(), nr, 0, 64, ctx->stream));
-        hipLaunchKernelGGL(mg_heads_kernel, blocks(nr), dim3(256), 0, ctx->stream, m->srt_h.as<uint64_t>(), m->srt_i.as<uint32_t>(), nr, m->flag.as<uint32_t>(), m->need_j.as<uint32_t>());
-        tb = 0;
-        CK(rocprim::exclusive_scan(nullptr, tb, m->need_j.as<uint32_t>(), m->pos_of_j.as<uint32_t>(), 0u, nr + 1, rocprim::plus<uint32_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::exclusive_scan(ctx->tmp.p, tb, m->need_j.as<uint32_t>(), m->pos_of_j.as<uint32_t>(), 0u, nr + 1, rocprim::plus<uint32_t>(), ctx->stream));
+        hipLaunchKernelGGL(mg_iota_kernel, grid256(nr), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), nr);
+        // stable: within a hash the entries stay in (shard, local) order -- the global first-seen order of its k-mers
+        PRIM(rocprim::radix_sort_pairs, m->recv_h.as<uint64_t>(), m->srt_h.as<uint64_t>(), m->iota.as<uint32_t>(), m->srt_i.as<uint32_t>(), nr, 0, 64, ctx->stream);
+        hipLaunchKernelGGL(mg_heads_kernel, grid256(nr), dim3(256), 0, ctx->stream, m->srt_h.as<uint64_t>(), m->srt_i.as<uint32_t>(), nr, m->flag.as<uint32_t>(), m->need_j.as<uint32_t>());
+        PRIM(rocprim::exclusive_scan, m->need_j.as<uint32_t>(), m->pos_of_j.as<uint32_t>(), 0u, nr + 1, rocprim::plus<uint32_t>(), ctx->stream);
         uint32_t nq = 0;
         CK(hipMemcpyAsync(&nq, m->pos_of_j.as<uint32_t>() + nr, 4, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
         n_req = nq;
         if (n_req) {
-            hipLaunchKernelGGL(mg_narrow8_kernel, blocks(nr), dim3(256), 0, ctx->stream, m->need_j.as<uint32_t>(), nr, m->need8.as<uint8_t>());
+            hipLaunchKernelGGL(mg_narrow8_kernel, grid256(nr), dim3(256), 0, ctx->stream, m->need_j.as<uint32_t>(), nr, m->need8.as<uint8_t>());
             uint64_t chk = 0;
             if ((rc = mg_select_u32(ctx, m, m->iota.as<uint32_t>(), m->need8.as<uint8_t>(), nr, m->req_j, &chk)) != OATK_OK) return rc;
         }
@@ -722,7 +713,7 @@ static int merge_counts_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint64_t *n_global
     CK(hipMemcpyAsync(m->plan_d.as<uint64_t>(), m->recv_off, 65 * 8, hipMemcpyHostToDevice, ctx->stream));
     if (n_req) {
         hipLaunchKernelGGL(mg_req_bounds_kernel, dim3(1), dim3(128), 0, ctx->stream, m->req_j.as<uint32_t>(), n_req, m->plan_d.as<uint64_t>(), n, m->plan_d.as<uint64_t>() + 65);
-        hipLaunchKernelGGL(mg_req_kernel, blocks(n_req), dim3(256), 0, ctx->stream, m->req_j.as<uint32_t>(), n_req, m->plan_d.as<uint64_t>(), n, m->req_k.as<uint32_t>());
+        hipLaunchKernelGGL(mg_req_kernel, grid256(n_req), dim3(256), 0, ctx->stream, m->req_j.as<uint32_t>(), n_req, m->plan_d.as<uint64_t>(), n, m->req_k.as<uint32_t>());
         CK(hipMemcpyAsync(req_off, m->plan_d.as<uint64_t>() + 65, (size_t) (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
     }
@@ -733,7 +724,7 @@ static int merge_counts_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint64_t *n_global
     if (n_asked) {
         CK(hipMemcpyAsync(m->plan_d.as<uint64_t>(), m->send_off, 65 * 8, hipMemcpyHostToDevice, ctx->stream));
         CK(hipMemcpyAsync(m->plan_d.as<uint64_t>() + 65, asked_off, 65 * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(mg_asked_ids_kernel, blocks(n_asked), dim3(256), 0, ctx->stream, m->asked.as<uint32_t>(), n_asked, m->plan_d.as<uint64_t>(), m->plan_d.as<uint64_t>() + 65, n,
+        hipLaunchKernelGGL(mg_asked_ids_kernel, grid256(n_asked), dim3(256), 0, ctx->stream, m->asked.as<uint32_t>(), n_asked, m->plan_d.as<uint64_t>(), m->plan_d.as<uint64_t>() + 65, n,
                            m->lid.as<uint32_t>());
         hipLaunchKernelGGL(mg_export_kmers_kernel, dim3((unsigned) n_asked), dim3(64), 0, ctx->stream, m->lid.as<uint32_t>(), n_asked, ctx->scm_occ_off.as<uint64_t>(),
                            ctx->scm_occ.as<uint64_t>(), ctx->sid0, ctx->d_off, ctx->scm_off.as<uint64_t>(), ctx->pos_mpos.as<uint32_t>(), ctx->hoco_s.as<uint8_t>(), ctx->K, nw,
@@ -741,16 +732,13 @@ static int merge_counts_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint64_t *n_global
     }
     if ((rc = comm_exchange(ctx, c, m->seq_out.p, asked_off, m->seq_in.p, req_off, (uint32_t) nw * 8u)) != OATK_OK) return rc;
     if (nr) {
-        hipLaunchKernelGGL(mg_cluster_kernel, blocks(nr), dim3(256), 0, ctx->stream, m->flag.as<uint32_t>(), m->srt_i.as<uint32_t>(), nr, m->need_j.as<uint32_t>(), m->pos_of_j.as<uint32_t>(),
+        hipLaunchKernelGGL(mg_cluster_kernel, grid256(nr), dim3(256), 0, ctx->stream, m->flag.as<uint32_t>(), m->srt_i.as<uint32_t>(), nr, m->need_j.as<uint32_t>(), m->pos_of_j.as<uint32_t>(),
                            m->seq_in.as<uint64_t>(), nw, m->recv_s.as<uint64_t>(), m->rep.as<uint32_t>(), m->clhead.as<uint32_t>(), m->bad.as<uint32_t>() + 1);
-        size_t tb = 0;
-        CK(rocprim::inclusive_scan(nullptr, tb, m->clhead.as<uint32_t>(), m->grp.as<uint32_t>(), nr, rocprim::plus<uint32_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::inclusive_scan(ctx->tmp.p, tb, m->clhead.as<uint32_t>(), m->grp.as<uint32_t>(), nr, rocprim::plus<uint32_t>(), ctx->stream));
+        PRIM(rocprim::inclusive_scan, m->clhead.as<uint32_t>(), m->grp.as<uint32_t>(), nr, rocprim::plus<uint32_t>(), ctx->stream);
         CK(hipMemsetAsync(m->own_cov.p, 0, (nr + 1) * 4, ctx->stream));
-        hipLaunchKernelGGL(mg_groups_kernel, blocks(nr), dim3(256), 0, ctx->stream, m->srt_h.as<uint64_t>(), m->srt_i.as<uint32_t>(), m->grp.as<uint32_t>(), m->rep.as<uint32_t>(),
+        hipLaunchKernelGGL(mg_groups_kernel, grid256(nr), dim3(256), 0, ctx->stream, m->srt_h.as<uint64_t>(), m->srt_i.as<uint32_t>(), m->grp.as<uint32_t>(), m->rep.as<uint32_t>(),
                            m->recv_s.as<uint64_t>(), m->recv_cov.as<uint32_t>(), nr, m->own_h.as<uint64_t>(), m->own_s.as<uint64_t>(), m->own_cov.as<uint32_t>(), m->grp_of.as<uint32_t>());
-        hipLaunchKernelGGL(mg_reply_kernel, blocks(nr), dim3(256), 0, ctx->stream, m->grp_of.as<uint32_t>(), m->own_cov.as<uint32_t>(), nr, m->reply.as<uint64_t>());
+        hipLaunchKernelGGL(mg_reply_kernel, grid256(nr), dim3(256), 0, ctx->stream, m->grp_of.as<uint32_t>(), m->own_cov.as<uint32_t>(), nr, m->reply.as<uint64_t>());
         uint32_t last = 0;
         CK(hipMemcpyAsync(&last, m->grp.as<uint32_t>() + (nr - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
@@ -772,7 +760,7 @@ static int merge_counts_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint64_t *n_global
     if ((rc = comm_exchange(ctx, c, m->reply.p, m->recv_off, m->back.p, m->send_off, 8)) != OATK_OK) return rc;
     CK(hipMemcpyAsync(m->plan_d.p, m->send_off, 65 * 8, hipMemcpyHostToDevice, ctx->stream));
     CK(hipMemcpyAsync(m->plan_d.as<uint64_t>() + 65, m->first_id, 65 * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (nl) hipLaunchKernelGGL(mg_l2g_kernel, blocks(nl), dim3(256), 0, ctx->stream, m->back.as<uint64_t>(), nl, m->plan_d.as<uint64_t>(), n, m->l2g.as<uint32_t>(), m->lcov.as<uint32_t>());
+    if (nl) hipLaunchKernelGGL(mg_l2g_kernel, grid256(nl), dim3(256), 0, ctx->stream, m->back.as<uint64_t>(), nl, m->plan_d.as<uint64_t>(), n, m->l2g.as<uint32_t>(), m->lcov.as<uint32_t>());
     CK(hipStreamSynchronize(ctx->stream));
     CK(hipGetLastError());
     (void) me;
@@ -899,7 +887,7 @@ __global__ void mg_del_kernel(const uint32_t *fwd, uint64_t n, uint8_t *del)
     if (i < n) del[i] = fwd[i] == 0;
 }
 
-// out = the items of `in` (32-bit) whose flag is set; *n_out on the host
+// out = the items of `in` (32-bit) whose flag is set; *n_out on the host (prim_select with this area's room for the output and counter slot)
 static int mg_select_u32(oatk_hip_ctx *ctx, MultiState *m, const uint32_t *in, const uint8_t *flag, uint64_t n, DevBuf &out, uint64_t *n_out)
 {
     *n_out = 0;
@@ -907,13 +895,7 @@ static int mg_select_u32(oatk_hip_ctx *ctx, MultiState *m, const uint32_t *in, c
     if (n == 0) return OATK_OK;
     MENSURE(num, (64 * 65 + 64) * 8);
     uint64_t *d_cnt = m->num.as<uint64_t>() + 64 * 65 + 8;
-    size_t tb = 0;
-    CK(rocprim::select(nullptr, tb, in, flag, out.as<uint32_t>(), d_cnt, n, ctx->stream));
-    ENSURE(tmp, tb);
-    CK(rocprim::select(ctx->tmp.p, tb, in, flag, out.as<uint32_t>(), d_cnt, n, ctx->stream));
-    CK(hipMemcpyAsync(n_out, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    return OATK_OK;
+    return prim_select(ctx, in, flag, n, out.as<uint32_t>(), d_cnt, n_out);
 }
 
 static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, uint32_t err_mer_c, uint32_t max_err_c, uint32_t err_arc_c,
@@ -927,7 +909,6 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
     if (!ctx->multi || !ctx->multi->merged) { if ((rc = merge_counts_impl(ctx, c, nullptr)) != OATK_OK) return rc; }
     MultiState *m = ctx->multi;
     m->ec_done = false, m->table_root = -1;
-    auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };
     const uint64_t ng = m->n_global, nl = ctx->n_scm_total, no = m->n_owned;
     const uint32_t first_me = (uint32_t) m->first_id[c->rank];
     const int nothing = ctx->n_occ == 0;            // a rank without syncmers corrects nothing and needs no k-mers
@@ -942,11 +923,11 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
     uint64_t nc = 0;
     if (light) {
         uint64_t nc_me = 0, chk = 0;
-        hipLaunchKernelGGL(mg_iota_kernel, blocks(no), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), no);
-        hipLaunchKernelGGL(mg_cand_flag_kernel, blocks(no), dim3(256), 0, ctx->stream, m->own_cov.as<uint32_t>(), no, err_mer_c, m->flag.as<uint8_t>());
+        hipLaunchKernelGGL(mg_iota_kernel, grid256(no), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), no);
+        hipLaunchKernelGGL(mg_cand_flag_kernel, grid256(no), dim3(256), 0, ctx->stream, m->own_cov.as<uint32_t>(), no, err_mer_c, m->flag.as<uint8_t>());
         if ((rc = mg_select_u32(ctx, m, m->iota.as<uint32_t>(), m->flag.as<uint8_t>(), no, m->opack, &nc_me)) != OATK_OK) return rc;
         MENSURE(cand_mine, (nc_me + 1) * 4); MENSURE(ccov_mine, (nc_me + 1) * 4); MENSURE(cs_mine, (nc_me + 1) * 8);
-        if (nc_me) hipLaunchKernelGGL(mg_cand_emit_kernel, blocks(nc_me), dim3(256), 0, ctx->stream, m->opack.as<uint32_t>(), nc_me, first_me, m->own_cov.as<uint32_t>(),
+        if (nc_me) hipLaunchKernelGGL(mg_cand_emit_kernel, grid256(nc_me), dim3(256), 0, ctx->stream, m->opack.as<uint32_t>(), nc_me, first_me, m->own_cov.as<uint32_t>(),
                                       m->own_s.as<uint64_t>(), m->cand_mine.as<uint32_t>(), m->ccov_mine.as<uint32_t>(), m->cs_mine.as<uint64_t>());
         {   // ids, coverage and s-mers of the candidates: rank order = id order, the list is ascending
             const void *src3[3] = {m->cand_mine.p, m->ccov_mine.p, m->cs_mine.p};
@@ -956,8 +937,8 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
             (void) chk;
         }
         if (nc) {
-            hipLaunchKernelGGL(mg_scatter_kernel<uint32_t>, blocks(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), m->cand_cov.as<uint32_t>(), nc, m->gcov.as<uint32_t>());
-            hipLaunchKernelGGL(mg_scatter_kernel<uint64_t>, blocks(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), m->cand_s.as<uint64_t>(), nc, m->S.as<uint64_t>());
+            hipLaunchKernelGGL(mg_scatter_kernel<uint32_t>, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), m->cand_cov.as<uint32_t>(), nc, m->gcov.as<uint32_t>());
+            hipLaunchKernelGGL(mg_scatter_kernel<uint64_t>, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), m->cand_s.as<uint64_t>(), nc, m->S.as<uint64_t>());
         }
     } else {
         uint64_t cnt[64], bytes[64];
@@ -969,8 +950,8 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
     }
     m->n_cand = nc;
     if (nl) {
-        hipLaunchKernelGGL(mg_scatter_kernel<uint32_t>, blocks(nl), dim3(256), 0, ctx->stream, m->l2g.as<uint32_t>(), m->lcov.as<uint32_t>(), nl, m->gcov.as<uint32_t>());
-        hipLaunchKernelGGL(mg_scatter_kernel<uint64_t>, blocks(nl), dim3(256), 0, ctx->stream, m->l2g.as<uint32_t>(), ctx->scm_s.as<uint64_t>(), nl, m->S.as<uint64_t>());
+        hipLaunchKernelGGL(mg_scatter_kernel<uint32_t>, grid256(nl), dim3(256), 0, ctx->stream, m->l2g.as<uint32_t>(), m->lcov.as<uint32_t>(), nl, m->gcov.as<uint32_t>());
+        hipLaunchKernelGGL(mg_scatter_kernel<uint64_t>, grid256(nl), dim3(256), 0, ctx->stream, m->l2g.as<uint32_t>(), ctx->scm_s.as<uint64_t>(), nl, m->S.as<uint64_t>());
     }
 
     // 1. chains in global ids; the graph of all reads
@@ -987,16 +968,15 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
         if ((rc = ec_light_pairs(ctx, err_mer_c, &lk, &ld, &nk)) != OATK_OK) return rc;
         EENSURE(g_keys2, (nk + 1) * 8); EENSURE(g_dist2, (nk + 1) * 4); EENSURE(g_head, nk + 8); EENSURE(g_hpos, (nk + 1) * 4); EENSURE(g_iota, (nk + 1) * 4);
         if (nk) {
-            size_t tb = 0;          // stable: a key's distances stay in (read, slot) order, so a segment is a run of consecutive calls
-            CK(rocprim::radix_sort_pairs(nullptr, tb, const_cast<uint64_t *>(lk), e->g_keys2.as<uint64_t>(), const_cast<uint32_t *>(ld), e->g_dist2.as<uint32_t>(), nk, 0, 64, ctx->stream));
-            ENSURE(tmp, tb);
-            CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, const_cast<uint64_t *>(lk), e->g_keys2.as<uint64_t>(), const_cast<uint32_t *>(ld), e->g_dist2.as<uint32_t>(), nk, 0, 64, ctx->stream));
-            hipLaunchKernelGGL(egr_seg_head_kernel, blocks(nk), dim3(256), 0, ctx->stream, nk, e->g_keys2.as<uint64_t>(), e->g_dist2.as<uint32_t>(), e->g_head.as<uint8_t>());
-            hipLaunchKernelGGL(mg_iota_kernel, blocks(nk), dim3(256), 0, ctx->stream, e->g_iota.as<uint32_t>(), nk);
-            if ((rc = ec_select(ctx, e, e->g_iota.as<uint32_t>(), e->g_head.as<uint8_t>(), nk, e->g_hpos.as<uint32_t>(), &n_seg)) != OATK_OK) return rc;
+            // stable: a key's distances stay in (read, slot) order, so a segment is a run of consecutive calls
+            PRIM(rocprim::radix_sort_pairs, const_cast<uint64_t *>(lk), e->g_keys2.as<uint64_t>(), const_cast<uint32_t *>(ld), e->g_dist2.as<uint32_t>(), nk, 0, 64, ctx->stream);
+            hipLaunchKernelGGL(egr_seg_head_kernel, grid256(nk), dim3(256), 0, ctx->stream, nk, e->g_keys2.as<uint64_t>(), e->g_dist2.as<uint32_t>(), e->g_head.as<uint8_t>());
+            hipLaunchKernelGGL(mg_iota_kernel, grid256(nk), dim3(256), 0, ctx->stream, e->g_iota.as<uint32_t>(), nk);
+            EENSURE(g_nruns, 64);
+            if ((rc = prim_select(ctx, e->g_iota.as<uint32_t>(), e->g_head.as<uint8_t>(), nk, e->g_hpos.as<uint32_t>(), e->g_nruns.as<uint64_t>() + 2, &n_seg)) != OATK_OK) return rc;
         }
         EENSURE(g_segk, (n_seg + 1) * 8); EENSURE(g_segv, (n_seg + 1) * 8);
-        if (n_seg) hipLaunchKernelGGL(egr_seg_emit_kernel, blocks(n_seg), dim3(256), 0, ctx->stream, n_seg, nk, e->g_hpos.as<uint32_t>(), e->g_keys2.as<uint64_t>(),
+        if (n_seg) hipLaunchKernelGGL(egr_seg_emit_kernel, grid256(n_seg), dim3(256), 0, ctx->stream, n_seg, nk, e->g_hpos.as<uint32_t>(), e->g_keys2.as<uint64_t>(),
                                       e->g_dist2.as<uint32_t>(), e->g_segk.as<uint64_t>(), e->g_segv.as<uint64_t>());
         {
             const void *src2[2] = {e->g_segk.p, e->g_segv.p};
@@ -1027,9 +1007,9 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
             const uint64_t words = (2 * nc + 3) / 4;
             MENSURE(opack, words * 4 + 16);
             CK(hipMemsetAsync(m->opack.p, 0, words * 4, ctx->stream));
-            if (!rc_graph) hipLaunchKernelGGL(mg_other_pack_kernel, blocks(2 * nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), 2 * nc, e->g_other.as<uint8_t>(), m->opack.as<uint8_t>());
+            if (!rc_graph) hipLaunchKernelGGL(mg_other_pack_kernel, grid256(2 * nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), 2 * nc, e->g_other.as<uint8_t>(), m->opack.as<uint8_t>());
             if ((rc = comm_allreduce(ctx, c, m->opack.p, words, false, false)) != OATK_OK) return rc;     // at most 64 ranks: the byte sums do not carry
-            if (!rc_graph) hipLaunchKernelGGL(mg_other_unpack_kernel, blocks(2 * nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), 2 * nc, m->opack.as<uint8_t>(), e->g_other.as<uint8_t>());
+            if (!rc_graph) hipLaunchKernelGGL(mg_other_unpack_kernel, grid256(2 * nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), 2 * nc, m->opack.as<uint8_t>(), e->g_other.as<uint8_t>());
         }
         if (!rc_graph) e->light_c = err_mer_c;
     }
@@ -1043,13 +1023,13 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
     } else if (light) {
         // flags over the candidate list instead of the whole table
         MENSURE(flag, (nc > ng? nc : ng) + 8);
-        if (nc) hipLaunchKernelGGL(mg_need_cand_kernel, blocks(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), nc, (const uint8_t *) e->err_del.p,
+        if (nc) hipLaunchKernelGGL(mg_need_cand_kernel, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), nc, (const uint8_t *) e->err_del.p,
                                    e->vtx_hs_off.as<uint64_t>(), m->flag.as<uint8_t>(), nothing);
         if ((rc = mg_select_u32(ctx, m, m->cand.as<uint32_t>(), m->flag.as<uint8_t>(), nc, m->need, &n_need)) != OATK_OK) return rc;
     } else {
         MENSURE(flag, ng + 8); MENSURE(iota, (ng + 1) * 4);
-        hipLaunchKernelGGL(mg_iota_kernel, blocks(ng), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), ng);
-        hipLaunchKernelGGL(mg_need_flag_kernel, blocks(ng), dim3(256), 0, ctx->stream, (const uint8_t *) e->err_del.p, e->vtx_hs_off.as<uint64_t>(), ng, m->flag.as<uint8_t>(), nothing);
+        hipLaunchKernelGGL(mg_iota_kernel, grid256(ng), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), ng);
+        hipLaunchKernelGGL(mg_need_flag_kernel, grid256(ng), dim3(256), 0, ctx->stream, (const uint8_t *) e->err_del.p, e->vtx_hs_off.as<uint64_t>(), ng, m->flag.as<uint8_t>(), nothing);
         if ((rc = mg_select_u32(ctx, m, m->iota.as<uint32_t>(), m->flag.as<uint8_t>(), ng, m->need, &n_need)) != OATK_OK) return rc;
     }
     {   // the counts, and with them everybody's verdict on the graph and the marks
@@ -1067,26 +1047,20 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
     }
     if (n_need_all) {
         MENSURE(need_srt, (n_need_all + 1) * 4); MENSURE(uni, (n_need_all + 1) * 4); MENSURE(num, (64 * 65 + 64) * 8);
-        size_t tb = 0;
-        CK(rocprim::radix_sort_keys(nullptr, tb, m->need_all.as<uint32_t>(), m->need_srt.as<uint32_t>(), n_need_all, 0, 32, ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::radix_sort_keys(ctx->tmp.p, tb, m->need_all.as<uint32_t>(), m->need_srt.as<uint32_t>(), n_need_all, 0, 32, ctx->stream));
+        PRIM(rocprim::radix_sort_keys, m->need_all.as<uint32_t>(), m->need_srt.as<uint32_t>(), n_need_all, 0, 32, ctx->stream);
         uint64_t *d_cnt = m->num.as<uint64_t>() + 64 * 65 + 9;
-        tb = 0;
-        CK(rocprim::unique(nullptr, tb, m->need_srt.as<uint32_t>(), m->uni.as<uint32_t>(), d_cnt, n_need_all, rocprim::equal_to<uint32_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::unique(ctx->tmp.p, tb, m->need_srt.as<uint32_t>(), m->uni.as<uint32_t>(), d_cnt, n_need_all, rocprim::equal_to<uint32_t>(), ctx->stream));
+        PRIM(rocprim::unique, m->need_srt.as<uint32_t>(), m->uni.as<uint32_t>(), d_cnt, n_need_all, rocprim::equal_to<uint32_t>(), ctx->stream);
         CK(hipMemcpyAsync(&nu, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
     }
     if (nu) {
         const uint32_t nobody = (uint32_t) c->n;
         MENSURE(owner, (nu + 1) * 4); MENSURE(bad, 64);
-        hipLaunchKernelGGL(mg_owner_kernel, blocks(nu), dim3(256), 0, ctx->stream, m->uni.as<uint32_t>(), nu, e->vtx_hs_off.as<uint64_t>(), (uint32_t) c->rank, nobody, m->owner.as<uint32_t>());
+        hipLaunchKernelGGL(mg_owner_kernel, grid256(nu), dim3(256), 0, ctx->stream, m->uni.as<uint32_t>(), nu, e->vtx_hs_off.as<uint64_t>(), (uint32_t) c->rank, nobody, m->owner.as<uint32_t>());
         if ((rc = comm_allreduce(ctx, c, m->owner.p, nu, false, true)) != OATK_OK) return rc;
         CK(hipMemsetAsync(m->bad.p, 0, 64, ctx->stream));
         MENSURE(flag, (nu > ng? nu : ng) + 8);
-        hipLaunchKernelGGL(mg_eq_flag_kernel, blocks(nu), dim3(256), 0, ctx->stream, m->owner.as<uint32_t>(), nu, (uint32_t) c->rank, m->flag.as<uint8_t>(), m->bad.as<uint32_t>(), nobody);
+        hipLaunchKernelGGL(mg_eq_flag_kernel, grid256(nu), dim3(256), 0, ctx->stream, m->owner.as<uint32_t>(), nu, (uint32_t) c->rank, m->flag.as<uint8_t>(), m->bad.as<uint32_t>(), nobody);
         uint32_t orphan = 0;
         CK(hipMemcpyAsync(&orphan, m->bad.p, 4, hipMemcpyDeviceToHost, ctx->stream));
         uint64_t n_mine = 0;
@@ -1104,8 +1078,8 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
         }
         // of everything that travelled, what THIS rank lacks
         MENSURE(flag, (n_all > ng? n_all : ng) + 8); MENSURE(iota, ((n_all > ng? n_all : ng) + 1) * 4);
-        hipLaunchKernelGGL(mg_iota_kernel, blocks(n_all), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), n_all);
-        hipLaunchKernelGGL(mg_lack_kernel, blocks(n_all), dim3(256), 0, ctx->stream, m->ids_all.as<uint32_t>(), n_all, e->vtx_hs_off.as<uint64_t>(), m->flag.as<uint8_t>(), nothing);
+        hipLaunchKernelGGL(mg_iota_kernel, grid256(n_all), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), n_all);
+        hipLaunchKernelGGL(mg_lack_kernel, grid256(n_all), dim3(256), 0, ctx->stream, m->ids_all.as<uint32_t>(), n_all, e->vtx_hs_off.as<uint64_t>(), m->flag.as<uint8_t>(), nothing);
         uint64_t n_imp = 0;
         if ((rc = mg_select_u32(ctx, m, m->iota.as<uint32_t>(), m->flag.as<uint8_t>(), n_all, m->lack, &n_imp)) != OATK_OK) return rc;
         if (n_imp) {
@@ -1116,10 +1090,7 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
             if ((rc = mg_select_u32(ctx, m, m->ids_all.as<uint32_t>(), m->flag.as<uint8_t>(), n_all, m->ids_i, &chk)) != OATK_OK) return rc;
             {
                 uint64_t *d_cnt = m->num.as<uint64_t>() + 64 * 65 + 10;
-                size_t tb = 0;
-                CK(rocprim::select(nullptr, tb, m->rev_all.as<uint8_t>(), m->flag.as<uint8_t>(), m->rev_i.as<uint8_t>(), d_cnt, n_all, ctx->stream));
-                ENSURE(tmp, tb);
-                CK(rocprim::select(ctx->tmp.p, tb, m->rev_all.as<uint8_t>(), m->flag.as<uint8_t>(), m->rev_i.as<uint8_t>(), d_cnt, n_all, ctx->stream));
+                PRIM(rocprim::select, m->rev_all.as<uint8_t>(), m->flag.as<uint8_t>(), m->rev_i.as<uint8_t>(), d_cnt, n_all, ctx->stream);
             }
             if ((rc = oatk_hip_ec_import_kmers(ctx, m->ids_i.as<uint32_t>(), m->rev_i.as<uint8_t>(), m->km_i.as<uint8_t>(), n_imp, stride)) != OATK_OK) return rc;
         }
@@ -1139,9 +1110,9 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
         MENSURE(pc, (2 * nc + 2) * 4); MENSURE(loc_c, (nl + 1) * 4); MENSURE(loc_f, (nl + 1) * 4);
         const uint64_t nr = m->recv_off[c->n];
         MENSURE(rcv_c, (nr + 1) * 4); MENSURE(rcv_f, (nr + 1) * 4);
-        if (nc) hipLaunchKernelGGL(mg_pack_cand_kernel, blocks(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), nc, e->cov.as<uint32_t>(), e->fwd.as<uint32_t>(), m->pc.as<uint32_t>());
+        if (nc) hipLaunchKernelGGL(mg_pack_cand_kernel, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), nc, e->cov.as<uint32_t>(), e->fwd.as<uint32_t>(), m->pc.as<uint32_t>());
         if ((rc = comm_allreduce(ctx, c, m->pc.p, 2 * nc, false, false)) != OATK_OK) return rc;
-        if (nl) hipLaunchKernelGGL(mg_local_contrib_kernel, blocks(nl), dim3(256), 0, ctx->stream, m->l2g.as<uint32_t>(), nl, m->gcov.as<uint32_t>(), err_mer_c, e->cov.as<uint32_t>(),
+        if (nl) hipLaunchKernelGGL(mg_local_contrib_kernel, grid256(nl), dim3(256), 0, ctx->stream, m->l2g.as<uint32_t>(), nl, m->gcov.as<uint32_t>(), err_mer_c, e->cov.as<uint32_t>(),
                                    e->fwd.as<uint32_t>(), m->loc_c.as<uint32_t>(), m->loc_f.as<uint32_t>());
         {
             const void *out2[2] = {m->loc_c.p, m->loc_f.p};
@@ -1149,9 +1120,9 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
             const uint32_t w2[2] = {4, 4};
             if ((rc = comm_exchange_multi(ctx, c, 2, out2, m->send_off, in2, m->recv_off, w2)) != OATK_OK) return rc;
         }
-        if (nr) hipLaunchKernelGGL(mg_owner_add_kernel, blocks(nr), dim3(256), 0, ctx->stream, m->grp_of.as<uint32_t>(), nr, m->rcv_c.as<uint32_t>(), m->rcv_f.as<uint32_t>(),
+        if (nr) hipLaunchKernelGGL(mg_owner_add_kernel, grid256(nr), dim3(256), 0, ctx->stream, m->grp_of.as<uint32_t>(), nr, m->rcv_c.as<uint32_t>(), m->rcv_f.as<uint32_t>(),
                                    m->ec_cov.as<uint32_t>(), m->ec_fwd.as<uint32_t>());
-        if (nc) hipLaunchKernelGGL(mg_owner_cand_kernel, blocks(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), nc, m->pc.as<uint32_t>(), first_me, (uint32_t) no,
+        if (nc) hipLaunchKernelGGL(mg_owner_cand_kernel, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), nc, m->pc.as<uint32_t>(), first_me, (uint32_t) no,
                                    m->ec_cov.as<uint32_t>(), m->ec_fwd.as<uint32_t>());
     } else {
         // every id may matter: two all-reduces over the whole table, of which the rank keeps its own range
@@ -1164,7 +1135,7 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
         CK(hipMemcpyAsync(m->ec_fwd.p, m->loc_f.as<uint32_t>() + first_me, no * 4, hipMemcpyDeviceToDevice, ctx->stream));
     }
     if ((rc = comm_allreduce(ctx, c, m->st64.p, 12, true, false)) != OATK_OK) return rc;
-    hipLaunchKernelGGL(mg_del_kernel, blocks(no), dim3(256), 0, ctx->stream, m->ec_fwd.as<uint32_t>(), no, m->ec_del.as<uint8_t>());
+    hipLaunchKernelGGL(mg_del_kernel, grid256(no), dim3(256), 0, ctx->stream, m->ec_fwd.as<uint32_t>(), no, m->ec_del.as<uint8_t>());
     uint64_t st[12];
     CK(hipMemcpyAsync(st, m->st64.p, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));

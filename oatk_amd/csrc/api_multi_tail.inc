@@ -26,10 +26,7 @@ enum {
 };
 static_assert(MX_COUNT_ <= 64, "MultiState::x is too small");
 
-#define XENSURE(id, bytes)                                                                         \
-    do {                                                                                           \
-        if (!m->x[id].ensure((bytes), ctx->stream)) { ctx->err = "hipMalloc failed for multi.x[" #id "]"; return OATK_E_NOMEM; } \
-    } while (0)
+#define XENSURE(id, bytes) ENSURE_IN(m, "multi.", x[id], bytes)
 
 // rank r's n_mine items of `width` bytes land on `root` back to back in rank order (dst is grown there); *n_all on every rank
 static int comm_gather_root(oatk_hip_ctx *ctx, oatk_comm *c, const void *d_src, uint64_t n_mine, uint32_t width, DevBuf &dst, uint64_t *n_all, int root)
@@ -146,7 +143,6 @@ static int gather_table_impl(oatk_hip_ctx *ctx, oatk_comm *c, int root)
     MultiState *m = ctx->multi;
     if (!m || !m->merged) { ctx->err = "oatk_hip_gather_table needs oatk_hip_merge_counts"; return OATK_E_STATE; }
     CK(hipSetDevice(ctx->device));
-    auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };
     EcState *e = ctx->ec;
     const bool after = m->ec_done;
     const uint64_t ng = m->n_global, no = m->n_owned, nr = ctx->n_reads;
@@ -163,7 +159,7 @@ static int gather_table_impl(oatk_hip_ctx *ctx, oatk_comm *c, int root)
     } else {
         n_mine = ctx->n_occ;
         XENSURE(MX_T_GID, (n_mine + 1) * 4); XENSURE(MX_T_OCC, (n_mine + 1) * 8); XENSURE(MX_GKID, (n_mine + 1) * 8);
-        if (n_mine) hipLaunchKernelGGL(mgt_slot_kernel, blocks(nr), dim3(256), 0, ctx->stream, nr, ctx->scm_off.as<uint64_t>(), ctx->pos_kid.as<uint64_t>(), ctx->pos_mpos.as<uint32_t>(),
+        if (n_mine) hipLaunchKernelGGL(mgt_slot_kernel, grid256(nr), dim3(256), 0, ctx->stream, nr, ctx->scm_off.as<uint64_t>(), ctx->pos_kid.as<uint64_t>(), ctx->pos_mpos.as<uint32_t>(),
                                        m->l2g.as<uint32_t>(), ctx->sid0, m->x[MX_T_GID].as<uint32_t>(), m->x[MX_T_OCC].as<uint64_t>(), m->x[MX_GKID].as<uint64_t>());
         d_gid = m->x[MX_T_GID].as<uint32_t>(), d_occ = m->x[MX_T_OCC].as<uint64_t>();
         m->gkid_n = n_mine;
@@ -184,19 +180,12 @@ static int gather_table_impl(oatk_hip_ctx *ctx, oatk_comm *c, int root)
         if (!bad && n_all) {
             unsigned id_bits = 1;
             while (id_bits < 32 && (ng - 1) >> id_bits) ++id_bits;
-            size_t tb = 0;
-            CK(rocprim::radix_sort_pairs(nullptr, tb, m->x[MX_R_GID].as<uint32_t>(), m->x[MX_R_GID2].as<uint32_t>(), m->x[MX_R_OCC].as<uint64_t>(), m->x[MX_R_OCC2].as<uint64_t>(), n_all, 0,
-                                         id_bits, ctx->stream));
-            ENSURE(tmp, tb);
-            CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, m->x[MX_R_GID].as<uint32_t>(), m->x[MX_R_GID2].as<uint32_t>(), m->x[MX_R_OCC].as<uint64_t>(), m->x[MX_R_OCC2].as<uint64_t>(), n_all, 0,
-                                         id_bits, ctx->stream));
+            PRIM(rocprim::radix_sort_pairs, m->x[MX_R_GID].as<uint32_t>(), m->x[MX_R_GID2].as<uint32_t>(), m->x[MX_R_OCC].as<uint64_t>(), m->x[MX_R_OCC2].as<uint64_t>(), n_all, 0, id_bits,
+                 ctx->stream);
         }
         if (!bad) {
-            hipLaunchKernelGGL(mgt_widen_kernel, blocks(ng + 1), dim3(256), 0, ctx->stream, m->x[MX_G_COV].as<uint32_t>(), m->x[MX_G_COV64].as<uint64_t>(), ng);
-            size_t tb = 0;
-            CK(rocprim::exclusive_scan(nullptr, tb, m->x[MX_G_COV64].as<uint64_t>(), m->x[MX_G_OFF].as<uint64_t>(), (uint64_t) 0, ng + 1, rocprim::plus<uint64_t>(), ctx->stream));
-            ENSURE(tmp, tb);
-            CK(rocprim::exclusive_scan(ctx->tmp.p, tb, m->x[MX_G_COV64].as<uint64_t>(), m->x[MX_G_OFF].as<uint64_t>(), (uint64_t) 0, ng + 1, rocprim::plus<uint64_t>(), ctx->stream));
+            hipLaunchKernelGGL(mgt_widen_kernel, grid256(ng + 1), dim3(256), 0, ctx->stream, m->x[MX_G_COV].as<uint32_t>(), m->x[MX_G_COV64].as<uint64_t>(), ng);
+            PRIM(rocprim::exclusive_scan, m->x[MX_G_COV64].as<uint64_t>(), m->x[MX_G_OFF].as<uint64_t>(), (uint64_t) 0, ng + 1, rocprim::plus<uint64_t>(), ctx->stream);
             uint64_t tot = 0;
             CK(hipMemcpyAsync(&tot, m->x[MX_G_OFF].as<uint64_t>() + ng, 8, hipMemcpyDeviceToHost, ctx->stream));
             CK(hipStreamSynchronize(ctx->stream));
@@ -249,7 +238,6 @@ static int asm_graph_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint32_t min_
     MultiState *m = ctx->multi;
     if (!m || !m->ec_done) { ctx->err = "oatk_hip_asm_graph_sharded: after oatk_hip_ec_sharded"; return OATK_E_STATE; }
     CK(hipSetDevice(ctx->device));
-    auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };
     if ((rc = mgt_dense(ctx, c, m)) != OATK_OK) return rc;
     const uint32_t *d_cov = m->x[MX_DCOV].as<uint32_t>();
     const uint8_t *d_del = m->x[MX_DDEL].as<uint8_t>();
@@ -260,15 +248,9 @@ static int asm_graph_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint32_t min_
     XENSURE(MX_K1, (n + 1) * 8); XENSURE(MX_K2, (n + 1) * 8); XENSURE(MX_U, (n + 1) * 8); XENSURE(MX_C, (n + 1) * 4); XENSURE(MX_NR, 64);
     if (n) {
         if (n >= 0xFFFFFFFFULL) { ctx->err = "more than 2^32 adjacent pairs on one rank"; return OATK_E_ARG; }
-        hipLaunchKernelGGL(mgt_pair_keep_kernel, blocks(n), dim3(256), 0, ctx->stream, n, (const uint64_t *) keys, d_cov, d_del, min_k_cov, m->x[MX_K1].as<uint64_t>(), 0);
-        size_t tb = 0;
-        CK(rocprim::radix_sort_keys(nullptr, tb, m->x[MX_K1].as<uint64_t>(), m->x[MX_K2].as<uint64_t>(), n, 0, 64, ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::radix_sort_keys(ctx->tmp.p, tb, m->x[MX_K1].as<uint64_t>(), m->x[MX_K2].as<uint64_t>(), n, 0, 64, ctx->stream));
-        tb = 0;
-        CK(rocprim::run_length_encode(nullptr, tb, m->x[MX_K2].as<uint64_t>(), (unsigned int) n, m->x[MX_U].as<uint64_t>(), m->x[MX_C].as<uint32_t>(), m->x[MX_NR].as<uint32_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::run_length_encode(ctx->tmp.p, tb, m->x[MX_K2].as<uint64_t>(), (unsigned int) n, m->x[MX_U].as<uint64_t>(), m->x[MX_C].as<uint32_t>(), m->x[MX_NR].as<uint32_t>(), ctx->stream));
+        hipLaunchKernelGGL(mgt_pair_keep_kernel, grid256(n), dim3(256), 0, ctx->stream, n, (const uint64_t *) keys, d_cov, d_del, min_k_cov, m->x[MX_K1].as<uint64_t>(), 0);
+        if ((rc = prim_sort_runs(ctx, m->x[MX_K1].as<uint64_t>(), m->x[MX_K2].as<uint64_t>(), (void *) nullptr, (void *) nullptr, n, 0, 64, m->x[MX_U].as<uint64_t>(), m->x[MX_C].as<uint32_t>(),
+                                 m->x[MX_NR].as<uint32_t>())) != OATK_OK) return rc;
         uint32_t nrn = 0;
         uint64_t last = 0;
         CK(hipMemcpyAsync(&nrn, m->x[MX_NR].p, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -348,7 +330,6 @@ static int overlap_hist_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint32_t m
     MultiState *m = ctx->multi;
     if (!m || !m->ec_done) { ctx->err = "oatk_hip_overlap_hist_sharded: after oatk_hip_ec_sharded"; return OATK_E_STATE; }
     CK(hipSetDevice(ctx->device));
-    auto blocks = [](uint64_t n) { return dim3((unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1)); };
     if ((rc = mgt_dense(ctx, c, m)) != OATK_OK) return rc;
     const void *keys = nullptr, *dist = nullptr;
     uint64_t n = 0, n_seg = 0;
@@ -359,21 +340,19 @@ static int overlap_hist_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint32_t m
     if (n) {
         if (n >= 0xFFFFFFFFULL) { ctx->err = "more than 2^32 adjacent pairs on one rank"; return OATK_E_ARG; }
         OENSURE(keys2, (n + 1) * 8); OENSURE(dist2, (n + 1) * 4);
-        hipLaunchKernelGGL(mgt_pair_keep_kernel, blocks(n), dim3(256), 0, ctx->stream, n, (const uint64_t *) keys, m->x[MX_DCOV].as<uint32_t>(), m->x[MX_DDEL].as<uint8_t>(), min_cov,
+        hipLaunchKernelGGL(mgt_pair_keep_kernel, grid256(n), dim3(256), 0, ctx->stream, n, (const uint64_t *) keys, m->x[MX_DCOV].as<uint32_t>(), m->x[MX_DDEL].as<uint8_t>(), min_cov,
                            m->x[MX_K1].as<uint64_t>(), min_cov == 0);
-        size_t tb = 0;          // stable: a key's distances stay in (read, slot) order, so a segment is a run of consecutive calls
-        CK(rocprim::radix_sort_pairs(nullptr, tb, m->x[MX_K1].as<uint64_t>(), g->keys2.as<uint64_t>(), (uint32_t *) const_cast<void *>(dist), g->dist2.as<uint32_t>(), n, 0, 64, ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, m->x[MX_K1].as<uint64_t>(), g->keys2.as<uint64_t>(), (uint32_t *) const_cast<void *>(dist), g->dist2.as<uint32_t>(), n, 0, 64, ctx->stream));
-        hipLaunchKernelGGL(mgt_seg_head_kernel, blocks(n), dim3(256), 0, ctx->stream, n, g->keys2.as<uint64_t>(), g->dist2.as<uint32_t>(), m->x[MX_HEAD].as<uint8_t>());
-        hipLaunchKernelGGL(mg_iota_kernel, blocks(n), dim3(256), 0, ctx->stream, m->x[MX_IOTA].as<uint32_t>(), n);
+        // stable: a key's distances stay in (read, slot) order, so a segment is a run of consecutive calls
+        PRIM(rocprim::radix_sort_pairs, m->x[MX_K1].as<uint64_t>(), g->keys2.as<uint64_t>(), (uint32_t *) const_cast<void *>(dist), g->dist2.as<uint32_t>(), n, 0, 64, ctx->stream);
+        hipLaunchKernelGGL(mgt_seg_head_kernel, grid256(n), dim3(256), 0, ctx->stream, n, g->keys2.as<uint64_t>(), g->dist2.as<uint32_t>(), m->x[MX_HEAD].as<uint8_t>());
+        hipLaunchKernelGGL(mg_iota_kernel, grid256(n), dim3(256), 0, ctx->stream, m->x[MX_IOTA].as<uint32_t>(), n);
         hipLaunchKernelGGL(mgt_first_invalid_kernel, dim3(1), dim3(1), 0, ctx->stream, g->keys2.as<uint64_t>(), n, m->x[MX_NR].as<uint64_t>() + 4);
         if ((rc = mg_select_u32(ctx, m, m->x[MX_IOTA].as<uint32_t>(), m->x[MX_HEAD].as<uint8_t>(), n, m->x[MX_HPOS], &n_seg)) != OATK_OK) return rc;
     }
     uint64_t n_valid = 0;
     if (n) { CK(hipMemcpyAsync(&n_valid, m->x[MX_NR].as<uint64_t>() + 4, 8, hipMemcpyDeviceToHost, ctx->stream)); CK(hipStreamSynchronize(ctx->stream)); }
     XENSURE(MX_SEGK, (n_seg + 1) * 8); XENSURE(MX_SEGV, (n_seg + 1) * 8);
-    if (n_seg) hipLaunchKernelGGL(mgt_seg_emit_kernel, blocks(n_seg), dim3(256), 0, ctx->stream, n_seg, n_valid, m->x[MX_HPOS].as<uint32_t>(), g->keys2.as<uint64_t>(), g->dist2.as<uint32_t>(),
+    if (n_seg) hipLaunchKernelGGL(mgt_seg_emit_kernel, grid256(n_seg), dim3(256), 0, ctx->stream, n_seg, n_valid, m->x[MX_HPOS].as<uint32_t>(), g->keys2.as<uint64_t>(), g->dist2.as<uint32_t>(),
                                   m->x[MX_SEGK].as<uint64_t>(), m->x[MX_SEGV].as<uint64_t>());
     uint64_t n_all = 0, chk = 0;
     if ((rc = comm_gather_items(ctx, c, m->x[MX_SEGK].p, n_seg, 8, m->x[MX_SKA], &n_all)) != OATK_OK) return rc;        // rank order = call order
@@ -414,16 +393,8 @@ static int stat_sharded_one(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, cons
     uint32_t n_runs = 0;
     XENSURE(MX_ST_SORT, (n + 1) * 8); XENSURE(MX_ST_U, (n + 1) * 8); XENSURE(MX_ST_C, (n + 1) * 4); XENSURE(MX_ST_NR, 1024 * 8); XENSURE(MX_ST_HIST, (OATK_STAT_MAX_DEPTH + 2) * 8);
     if (n) {
-        size_t tb = 0;
-        CK(rocprim::radix_sort_keys(nullptr, tb, const_cast<uint64_t *>(d_keys), m->x[MX_ST_SORT].as<uint64_t>(), n, 0, 64, ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::radix_sort_keys(ctx->tmp.p, tb, const_cast<uint64_t *>(d_keys), m->x[MX_ST_SORT].as<uint64_t>(), n, 0, 64, ctx->stream));
-        tb = 0;
-        CK(rocprim::run_length_encode(nullptr, tb, m->x[MX_ST_SORT].as<uint64_t>(), (unsigned int) n, m->x[MX_ST_U].as<uint64_t>(), m->x[MX_ST_C].as<uint32_t>(),
-                                      m->x[MX_ST_NR].as<uint32_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::run_length_encode(ctx->tmp.p, tb, m->x[MX_ST_SORT].as<uint64_t>(), (unsigned int) n, m->x[MX_ST_U].as<uint64_t>(), m->x[MX_ST_C].as<uint32_t>(),
-                                      m->x[MX_ST_NR].as<uint32_t>(), ctx->stream));
+        if ((rc = prim_sort_runs(ctx, const_cast<uint64_t *>(d_keys), m->x[MX_ST_SORT].as<uint64_t>(), (void *) nullptr, (void *) nullptr, n, 0, 64, m->x[MX_ST_U].as<uint64_t>(),
+                                 m->x[MX_ST_C].as<uint32_t>(), m->x[MX_ST_NR].as<uint32_t>())) != OATK_OK) return rc;
         CK(hipMemcpyAsync(&n_runs, m->x[MX_ST_NR].p, 4, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
     }
@@ -449,16 +420,9 @@ static int stat_sharded_one(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, cons
     uint32_t n_own = 0;
     CK(hipMemsetAsync(m->x[MX_ST_HIST].p, 0, (OATK_STAT_MAX_DEPTH + 2) * 8, ctx->stream));
     if (nrecv) {
-        size_t tb = 0;
-        CK(rocprim::radix_sort_pairs(nullptr, tb, m->x[MX_ST_RU].as<uint64_t>(), m->x[MX_ST_SU].as<uint64_t>(), m->x[MX_ST_RC].as<uint32_t>(), m->x[MX_ST_SC].as<uint32_t>(), nrecv, 0, 64, ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, m->x[MX_ST_RU].as<uint64_t>(), m->x[MX_ST_SU].as<uint64_t>(), m->x[MX_ST_RC].as<uint32_t>(), m->x[MX_ST_SC].as<uint32_t>(), nrecv, 0, 64, ctx->stream));
-        tb = 0;
-        CK(rocprim::reduce_by_key(nullptr, tb, m->x[MX_ST_SU].as<uint64_t>(), m->x[MX_ST_SC].as<uint32_t>(), (unsigned int) nrecv, m->x[MX_ST_OU].as<uint64_t>(), m->x[MX_ST_OC].as<uint32_t>(),
-                                  m->x[MX_ST_NR].as<uint32_t>() + 1, rocprim::plus<uint32_t>(), rocprim::equal_to<uint64_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::reduce_by_key(ctx->tmp.p, tb, m->x[MX_ST_SU].as<uint64_t>(), m->x[MX_ST_SC].as<uint32_t>(), (unsigned int) nrecv, m->x[MX_ST_OU].as<uint64_t>(), m->x[MX_ST_OC].as<uint32_t>(),
-                                  m->x[MX_ST_NR].as<uint32_t>() + 1, rocprim::plus<uint32_t>(), rocprim::equal_to<uint64_t>(), ctx->stream));
+        PRIM(rocprim::radix_sort_pairs, m->x[MX_ST_RU].as<uint64_t>(), m->x[MX_ST_SU].as<uint64_t>(), m->x[MX_ST_RC].as<uint32_t>(), m->x[MX_ST_SC].as<uint32_t>(), nrecv, 0, 64, ctx->stream);
+        PRIM(rocprim::reduce_by_key, m->x[MX_ST_SU].as<uint64_t>(), m->x[MX_ST_SC].as<uint32_t>(), (unsigned int) nrecv, m->x[MX_ST_OU].as<uint64_t>(), m->x[MX_ST_OC].as<uint32_t>(),
+             m->x[MX_ST_NR].as<uint32_t>() + 1, rocprim::plus<uint32_t>(), rocprim::equal_to<uint64_t>(), ctx->stream);
         CK(hipMemcpyAsync(&n_own, m->x[MX_ST_NR].as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
         unsigned nb = (n_own + 255) / 256;

@@ -93,7 +93,7 @@ static int rc_tri_impl(oatk_hip_ctx *ctx, oatk_comm *c, const oatk_racov_graph_t
         CK(hipMemsetAsync(g->flag.p, 0, (m_scm + 1) * 8, ctx->stream));
         if (m_scm) hipLaunchKernelGGL(rc_tri_uniq_kernel, dim3(rc_grid(m_scm)), dim3(256), 0, ctx->stream, a, m_scm, g->flag.as<uint64_t>());
         uint64_t n_uq = 0;
-        { int rc = rc_scan(ctx, g, g->flag, g->pos, m_scm, &n_uq); if (rc) return rc; }
+        { int rc = prim_scan_total(ctx, g->tmp, g->flag.as<uint64_t>(), g->pos.as<uint64_t>(), m_scm, &n_uq); if (rc) return rc; }
         // two contributions per event, sorted by slot; what the replay needs beside them does not depend on the table it goes on from
         RC_ENSURE(ev_key, nf * 8); RC_ENSURE(ev_key2, nf * 8); RC_ENSURE(ev_val, nf * 8); RC_ENSURE(ev_val2, nf * 8); RC_ENSURE(ev_score, nf * 8);
         RC_ENSURE(t_first, ng * 32); RC_ENSURE(t_last, ng * 32);
@@ -105,17 +105,15 @@ static int rc_tri_impl(oatk_hip_ctx *ctx, oatk_comm *c, const oatk_racov_graph_t
         bad = rc_err(ctx, g);
         if (!bad) {
             const uint64_t nc = 2 * nf;
-            size_t tb = 0;
-            CK(rocprim::radix_sort_pairs(nullptr, tb, g->ev_key.as<uint32_t>(), g->ev_key2.as<uint32_t>(), g->ev_val.as<uint32_t>(), g->ev_val2.as<uint32_t>(), nc, 0, 32, ctx->stream));
-            RC_ENSURE(tmp, tb);
-            CK(rocprim::radix_sort_pairs(g->tmp.p, tb, g->ev_key.as<uint32_t>(), g->ev_key2.as<uint32_t>(), g->ev_val.as<uint32_t>(), g->ev_val2.as<uint32_t>(), nc, 0, 32, ctx->stream));
+            RC_PRIM(rocprim::radix_sort_pairs, g->ev_key.as<uint32_t>(), g->ev_key2.as<uint32_t>(), g->ev_val.as<uint32_t>(),
+                    g->ev_val2.as<uint32_t>(), nc, 0, 32, ctx->stream);
             RC_ENSURE(em_w, (nc + 1) * 8); RC_ENSURE(em_e, (nc + 1) * 8); RC_ENSURE(em_fl, (nc + 1) * 8); RC_ENSURE(em_ef, (nc + 1) * 8);
             CK(hipMemsetAsync(g->em_w.p, 0, (nc + 1) * 8, ctx->stream)); CK(hipMemsetAsync(g->em_fl.p, 0, (nc + 1) * 8, ctx->stream));
             hipLaunchKernelGGL(rc_tri_prep_kernel, dim3(rc_grid(nc)), dim3(256), 0, ctx->stream, nc, g->ev_key2.as<uint32_t>(), g->ev_val2.as<uint32_t>(), g->ev_score.as<double>(),
                                g->em_w.as<uint64_t>(), g->em_fl.as<uint64_t>());
             uint64_t n_one = 0, n_frac = 0;
-            { int rc = rc_scan(ctx, g, g->em_w, g->em_e, nc, &n_one); if (rc) return rc; }
-            { int rc = rc_scan(ctx, g, g->em_fl, g->em_ef, nc, &n_frac); if (rc) return rc; }
+            { int rc = prim_scan_total(ctx, g->tmp, g->em_w.as<uint64_t>(), g->em_e.as<uint64_t>(), nc, &n_one); if (rc) return rc; }
+            { int rc = prim_scan_total(ctx, g->tmp, g->em_fl.as<uint64_t>(), g->em_ef.as<uint64_t>(), nc, &n_frac); if (rc) return rc; }
             RC_ENSURE(em_fpos, (n_frac + 1) * 8);
             hipLaunchKernelGGL(rc_fpos_kernel, dim3(rc_grid(nc)), dim3(256), 0, ctx->stream, nc, g->em_fl.as<uint64_t>(), g->em_ef.as<uint64_t>(), g->em_fpos.as<uint64_t>());
         }

@@ -29,10 +29,7 @@ static int ovl_buffer(oatk_hip_ctx *ctx, int which, const void **d_ptr, uint64_t
     return OATK_OK;
 }
 
-#define OENSURE(buf, bytes)                                                                        \
-    do {                                                                                           \
-        if (!g->buf.ensure((bytes), ctx->stream)) { ctx->err = "hipMalloc failed for ovl." #buf; return OATK_E_NOMEM; } \
-    } while (0)
+#define OENSURE(buf, bytes) ENSURE_IN(g, "ovl.", buf, bytes)
 
 // this batch's adjacent pairs for the tables: canonical key (fillers for slot 0 of a read and for pairs with a corrected member) and
 // distance, in (read, slot) order
@@ -94,38 +91,29 @@ static int ovl_build(oatk_hip_ctx *ctx, const uint64_t *d_keys, const uint32_t *
         OENSURE(keys2, (nocc + 1) * 8); OENSURE(dist2, (nocc + 1) * 4); OENSURE(counts, (nocc + 1) * 4); OENSURE(nruns, 64);
         uint64_t *keys_in = const_cast<uint64_t *>(d_keys);
         uint32_t *dist_in = const_cast<uint32_t *>(d_dist);
-        size_t tb = 0;          // stable: the distances of one key stay in (read, slot) order
+        uint64_t *keys2 = g->keys2.as<uint64_t>(), *ukeys = g->ukeys.as<uint64_t>();
+        uint32_t *counts = g->counts.as<uint32_t>(), *d_nruns = g->nruns.as<uint32_t>();
+        int rc;                 // stable: the distances of one key stay in (read, slot) order
         if (weighted) {
             OENSURE(val2, (nocc + 1) * 8);
-            uint64_t *val_in = const_cast<uint64_t *>(d_val);
-            CK(rocprim::radix_sort_pairs(nullptr, tb, keys_in, g->keys2.as<uint64_t>(), val_in, g->val2.as<uint64_t>(), nocc, 0, 64, ctx->stream));
-            ENSURE(tmp, tb);
-            CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, keys_in, g->keys2.as<uint64_t>(), val_in, g->val2.as<uint64_t>(), nocc, 0, 64, ctx->stream));
-        } else {
-        CK(rocprim::radix_sort_pairs(nullptr, tb, keys_in, g->keys2.as<uint64_t>(), dist_in, g->dist2.as<uint32_t>(), nocc, 0, 64, ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::radix_sort_pairs(ctx->tmp.p, tb, keys_in, g->keys2.as<uint64_t>(), dist_in, g->dist2.as<uint32_t>(), nocc, 0, 64, ctx->stream));
+            rc = prim_sort_runs(ctx, keys_in, keys2, const_cast<uint64_t *>(d_val), g->val2.as<uint64_t>(), nocc, 0, 64, ukeys, counts, d_nruns);
         }
-        tb = 0;
-        CK(rocprim::run_length_encode(nullptr, tb, g->keys2.as<uint64_t>(), (unsigned int) nocc, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(),
-                                      g->nruns.as<uint32_t>(), ctx->stream));
-        ENSURE(tmp, tb);
-        CK(rocprim::run_length_encode(ctx->tmp.p, tb, g->keys2.as<uint64_t>(), (unsigned int) nocc, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(),
-                                      g->nruns.as<uint32_t>(), ctx->stream));
+        else rc = prim_sort_runs(ctx, keys_in, keys2, dist_in, g->dist2.as<uint32_t>(), nocc, 0, 64, ukeys, counts, d_nruns);
+        if (rc) return rc;
         uint32_t n_runs = 0;
         uint64_t last_key = 0, chk = 0;
         CK(hipMemcpyAsync(&n_runs, g->nruns.p, 4, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
         if (n_runs) {
             CK(hipMemcpyAsync(&last_key, g->ukeys.as<uint64_t>() + (n_runs - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
-            { int rc = ec_exclusive_scan_u32(ctx, nullptr, g->counts, g->cnt64, g->runoff, n_runs, &chk); if (rc) return rc; }
+            { int rc = prim_scan_total_u32(ctx, g->counts, g->cnt64, g->runoff, n_runs, &chk); if (rc) return rc; }
             OENSURE(nout, ((uint64_t) n_runs + 1) * 4); OENSURE(o_tail, (uint64_t) n_runs + 8); OENSURE(spill, OVH_SPILL);
             CK(hipMemsetAsync(g->o_tail.p, 0, (uint64_t) n_runs + 8, ctx->stream));
             auto kern = weighted? ovh_kernel_t<true> : ovh_kernel_t<false>;
             hipLaunchKernelGGL(kern, dim3(n_runs), dim3(64), 0, ctx->stream, (uint64_t) n_runs, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(),
                                g->runoff.as<uint64_t>(), g->dist2.as<uint32_t>(), g->val2.as<uint64_t>(), g->nout.as<uint32_t>(), (const uint64_t *) nullptr, (int32_t *) nullptr,
                                (uint32_t *) nullptr, (uint8_t *) nullptr, g->flags.as<uint32_t>(), (const uint32_t *) nullptr, g->spill.as<uint8_t>(), (uint64_t) OVH_SPILL);
-            { int rc = ec_exclusive_scan_u32(ctx, nullptr, g->nout, g->nout64, g->outoff, n_runs, &ne); if (rc) return rc; }
+            { int rc = prim_scan_total_u32(ctx, g->nout, g->nout64, g->outoff, n_runs, &ne); if (rc) return rc; }
             OENSURE(o_dist, (ne + 1) * 4); OENSURE(o_cnt, (ne + 1) * 4);
             hipLaunchKernelGGL(kern, dim3(n_runs), dim3(64), 0, ctx->stream, (uint64_t) n_runs, g->ukeys.as<uint64_t>(), g->counts.as<uint32_t>(),
                                g->runoff.as<uint64_t>(), g->dist2.as<uint32_t>(), g->val2.as<uint64_t>(), (uint32_t *) nullptr, g->outoff.as<uint64_t>(), g->o_dist.as<int32_t>(),

@@ -21,15 +21,14 @@ static void rc_state_free(oatk_hip_ctx *ctx)
     ctx->rc = nullptr;
 }
 
-#define RC_ENSURE(buf, bytes)                                                                        \
-    do {                                                                                           \
-        if (!g->buf.ensure((uint64_t) (bytes) + 64, ctx->stream)) { ctx->err = "hipMalloc failed for racov." #buf; return OATK_E_NOMEM; } \
-    } while (0)
+#define RC_ENSURE(buf, bytes) ENSURE_IN(g, "racov.", buf, (uint64_t) (bytes) + 64)
 #define RC_UPLOAD(buf, src, bytes)                                                                   \
     do {                                                                                           \
         RC_ENSURE(buf, bytes);                                                                       \
         if (bytes) CK(hipMemcpyAsync(g->buf.p, (src), (bytes), hipMemcpyHostToDevice, ctx->stream)); \
     } while (0)
+// a rocPRIM call in this area's own temporary, which outlives the call that grew it like the rest of RcState
+#define RC_PRIM(fn, ...) PRIM_IN(g->tmp, ctx->stream, "hipMalloc failed for racov.tmp", fn, __VA_ARGS__)
 static inline unsigned rc_grid(uint64_t n) { return (unsigned) ((n + 255) / 256 > 0? (n + 255) / 256 : 1); }
 
 // the unitigs' part of the graph, the alignments and (with_chains) the chains into a.  sharded: the handle's reads are one rank's share, and
@@ -95,28 +94,12 @@ static int rc_err(oatk_hip_ctx *ctx, RcState *g)
     return OATK_OK;
 }
 
-// exclusive scan of in[0..n] (in[n] = 0) into out[0..n]; *total = out[n]
-static int rc_scan(oatk_hip_ctx *ctx, RcState *g, DevBuf &in, DevBuf &out, uint64_t n, uint64_t *total)
-{
-    size_t tb = 0;
-    CK(rocprim::exclusive_scan(nullptr, tb, in.as<uint64_t>(), out.as<uint64_t>(), (uint64_t) 0, n + 1, rocprim::plus<uint64_t>(), ctx->stream));
-    RC_ENSURE(tmp, tb);
-    CK(rocprim::exclusive_scan(g->tmp.p, tb, in.as<uint64_t>(), out.as<uint64_t>(), (uint64_t) 0, n + 1, rocprim::plus<uint64_t>(), ctx->stream));
-    CK(hipMemcpyAsync(total, out.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    return OATK_OK;
-}
-
 // every unitig's values sorted ascending (qsort with dbl_cmpfunc: the values are >= 0, no NaN from sound input), then its IQR mean
 static int rc_iqr(oatk_hip_ctx *ctx, RcState *g, const oatk::RcArgs &a, uint64_t m_scm, int drop_zero)
 {
     if (m_scm) {
-        size_t tb = 0;
-        CK(rocprim::segmented_radix_sort_keys(nullptr, tb, g->vals.as<double>(), g->vals2.as<double>(), (unsigned) m_scm, (unsigned) a.n_utg,
-                                              a.utg_off, a.utg_off + 1, 0, 64, ctx->stream));
-        RC_ENSURE(tmp, tb);
-        CK(rocprim::segmented_radix_sort_keys(g->tmp.p, tb, g->vals.as<double>(), g->vals2.as<double>(), (unsigned) m_scm, (unsigned) a.n_utg,
-                                              a.utg_off, a.utg_off + 1, 0, 64, ctx->stream));
+        RC_PRIM(rocprim::segmented_radix_sort_keys, g->vals.as<double>(), g->vals2.as<double>(), (unsigned) m_scm, (unsigned) a.n_utg,
+                a.utg_off, a.utg_off + 1, 0, 64, ctx->stream);
     }
     hipLaunchKernelGGL(oatk::rc_iqr_kernel, dim3(rc_grid(a.n_utg)), dim3(256), 0, ctx->stream, a.n_utg, a.utg_off, g->vals2.as<double>(), drop_zero, g->avg.as<double>());
     return OATK_OK;
@@ -184,7 +167,7 @@ static int rc_utg_impl(oatk_hip_ctx *ctx, oatk_comm *c, const oatk_racov_graph_t
     CK(hipMemsetAsync(g->flag.p, 0, (na + 1) * 8, ctx->stream));
     hipLaunchKernelGGL(rc_head_kernel, dim3(rc_grid(na)), dim3(256), 0, ctx->stream, a, g->flag.as<uint64_t>());
     uint64_t nr = 0;
-    { int rc = rc_scan(ctx, g, g->flag, g->pos, na, &nr); if (rc) return rc; }
+    { int rc = prim_scan_total(ctx, g->tmp, g->flag.as<uint64_t>(), g->pos.as<uint64_t>(), na, &nr); if (rc) return rc; }
     a.n_rd = nr;
     RC_ENSURE(rd_beg, (nr + 1) * 8);
     hipLaunchKernelGGL(rc_runs_kernel, dim3(rc_grid(na + 1)), dim3(256), 0, ctx->stream, a, g->flag.as<uint64_t>(), g->pos.as<uint64_t>(), g->rd_beg.as<uint64_t>());
@@ -198,9 +181,9 @@ static int rc_utg_impl(oatk_hip_ctx *ctx, oatk_comm *c, const oatk_racov_graph_t
     int bad = rc_err(ctx, g);
     uint64_t tot_c = 0, tot_l = 0, tot_u = 0;
     if (!bad) {
-        { int rc = rc_scan(ctx, g, g->need_c, g->cell_off, nr, &tot_c); if (rc) return rc; }
-        { int rc = rc_scan(ctx, g, g->need_l, g->lcs_off, nr, &tot_l); if (rc) return rc; }
-        { int rc = rc_scan(ctx, g, g->need_u, g->u_off, nr, &tot_u); if (rc) return rc; }
+        { int rc = prim_scan_total(ctx, g->tmp, g->need_c.as<uint64_t>(), g->cell_off.as<uint64_t>(), nr, &tot_c); if (rc) return rc; }
+        { int rc = prim_scan_total(ctx, g->tmp, g->need_l.as<uint64_t>(), g->lcs_off.as<uint64_t>(), nr, &tot_l); if (rc) return rc; }
+        { int rc = prim_scan_total(ctx, g->tmp, g->need_u.as<uint64_t>(), g->u_off.as<uint64_t>(), nr, &tot_u); if (rc) return rc; }
         const uint64_t cap = g->cap_cells? g->cap_cells : (1ull << 31);
         if (tot_c > cap) {
             char m[192];
@@ -227,10 +210,8 @@ static int rc_utg_impl(oatk_hip_ctx *ctx, oatk_comm *c, const oatk_racov_graph_t
     RC_ENSURE(blk_a, tot_l * 4);
     hipLaunchKernelGGL(rc_contrib_kernel, dim3(rc_grid(nr)), dim3(256), 0, ctx->stream, a, g->key.as<uint32_t>(), g->val.as<uint32_t>(), g->blk_a.as<uint32_t>());
     if (tot_u) {
-        size_t tb = 0;
-        CK(rocprim::radix_sort_pairs(nullptr, tb, g->key.as<uint32_t>(), g->key2.as<uint32_t>(), g->val.as<uint32_t>(), g->val2.as<uint32_t>(), tot_u, 0, 32, ctx->stream));
-        RC_ENSURE(tmp, tb);
-        CK(rocprim::radix_sort_pairs(g->tmp.p, tb, g->key.as<uint32_t>(), g->key2.as<uint32_t>(), g->val.as<uint32_t>(), g->val2.as<uint32_t>(), tot_u, 0, 32, ctx->stream));
+        RC_PRIM(rocprim::radix_sort_pairs, g->key.as<uint32_t>(), g->key2.as<uint32_t>(), g->val.as<uint32_t>(), g->val2.as<uint32_t>(),
+                tot_u, 0, 32, ctx->stream);
         hipLaunchKernelGGL(rc_segments_kernel, dim3(rc_grid(tot_u)), dim3(256), 0, ctx->stream, tot_u, nu, g->key2.as<uint32_t>(), g->seg_beg.as<uint64_t>(), g->seg_end.as<uint64_t>());
     }
     // the integral addends' prefix sums and the places of the fractional ones (rc_em_kernel)
@@ -239,8 +220,8 @@ static int rc_utg_impl(oatk_hip_ctx *ctx, oatk_comm *c, const oatk_racov_graph_t
     if (tot_u) hipLaunchKernelGGL(rc_em_prep_kernel, dim3(rc_grid(tot_u)), dim3(256), 0, ctx->stream, tot_u, nu, g->key2.as<uint32_t>(), g->val2.as<uint32_t>(),
                                   g->blk_a.as<uint32_t>(), g->ma_n.as<uint32_t>(), g->em_w.as<uint64_t>(), g->em_fl.as<uint64_t>());
     uint64_t tot_w = 0, n_frac = 0;
-    { int rc = rc_scan(ctx, g, g->em_w, g->em_e, tot_u, &tot_w); if (rc) return rc; }
-    { int rc = rc_scan(ctx, g, g->em_fl, g->em_ef, tot_u, &n_frac); if (rc) return rc; }
+    { int rc = prim_scan_total(ctx, g->tmp, g->em_w.as<uint64_t>(), g->em_e.as<uint64_t>(), tot_u, &tot_w); if (rc) return rc; }
+    { int rc = prim_scan_total(ctx, g->tmp, g->em_fl.as<uint64_t>(), g->em_ef.as<uint64_t>(), tot_u, &n_frac); if (rc) return rc; }
     RC_ENSURE(em_fpos, (n_frac + 1) * 8);
     if (tot_u) hipLaunchKernelGGL(rc_fpos_kernel, dim3(rc_grid(tot_u)), dim3(256), 0, ctx->stream, tot_u, g->em_fl.as<uint64_t>(), g->em_ef.as<uint64_t>(), g->em_fpos.as<uint64_t>());
     // the EM (:1983-2011).  Sharded: the ranks' contributions are consecutive stretches of the reference's (read, block, member) order, so
@@ -324,10 +305,8 @@ static int rc_arc_impl(oatk_hip_ctx *ctx, oatk_comm *c, const oatk_racov_graph_t
                            g->ev_bits.as<uint8_t>(), g->ev_score.as<double>());
         bad = rc_err(ctx, g);
         if (!bad) {
-            size_t tb = 0;
-            CK(rocprim::radix_sort_pairs(nullptr, tb, g->ev_key.as<uint64_t>(), g->ev_key2.as<uint64_t>(), g->ev_val.as<uint32_t>(), g->ev_val2.as<uint32_t>(), nf, 0, 64, ctx->stream));
-            RC_ENSURE(tmp, tb);
-            CK(rocprim::radix_sort_pairs(g->tmp.p, tb, g->ev_key.as<uint64_t>(), g->ev_key2.as<uint64_t>(), g->ev_val.as<uint32_t>(), g->ev_val2.as<uint32_t>(), nf, 0, 64, ctx->stream));
+            RC_PRIM(rocprim::radix_sort_pairs, g->ev_key.as<uint64_t>(), g->ev_key2.as<uint64_t>(), g->ev_val.as<uint32_t>(),
+                    g->ev_val2.as<uint32_t>(), nf, 0, 64, ctx->stream);
         }
     }
     { int rc = rc_verdict(ctx, c, bad, who); if (rc) return rc; }               // a missing arc on any rank is everybody's refusal

@@ -112,25 +112,14 @@ static void stat_state_free(oatk_hip_ctx *ctx)
     ctx->stat = nullptr;
 }
 
-#define TENSURE(buf, bytes)                                                                        \
-    do {                                                                                           \
-        if (!t->buf.ensure((bytes), ctx->stream)) { ctx->err = "hipMalloc failed for stat." #buf; return OATK_E_NOMEM; } \
-    } while (0)
+#define TENSURE(buf, bytes) ENSURE_IN(t, "stat.", buf, bytes)
 
 // multiplicities of the values of keys[0..n): histogram and number of distinct values
 static int stat_tabulate(oatk_hip_ctx *ctx, StatState *t, const uint64_t *keys, uint64_t n, int64_t *hist_out, uint64_t *uniq_out, int64_t *no_singleton)
 {
     using namespace oatk;
-    size_t tb = 0;
-    CK(rocprim::radix_sort_keys(nullptr, tb, const_cast<uint64_t *>(keys), t->sorted.as<uint64_t>(), n, 0, 64, ctx->stream));
-    ENSURE(tmp, tb);
-    CK(rocprim::radix_sort_keys(ctx->tmp.p, tb, const_cast<uint64_t *>(keys), t->sorted.as<uint64_t>(), n, 0, 64, ctx->stream));
-    tb = 0;
-    CK(rocprim::run_length_encode(nullptr, tb, t->sorted.as<uint64_t>(), (unsigned int) n, t->uniq.as<uint64_t>(), t->counts.as<uint32_t>(),
-                                  t->nruns.as<uint32_t>(), ctx->stream));
-    ENSURE(tmp, tb);
-    CK(rocprim::run_length_encode(ctx->tmp.p, tb, t->sorted.as<uint64_t>(), (unsigned int) n, t->uniq.as<uint64_t>(), t->counts.as<uint32_t>(),
-                                  t->nruns.as<uint32_t>(), ctx->stream));
+    { int rc = prim_sort_runs(ctx, const_cast<uint64_t *>(keys), t->sorted.as<uint64_t>(), (void *) nullptr, (void *) nullptr, n, 0, 64, t->uniq.as<uint64_t>(), t->counts.as<uint32_t>(),
+                              t->nruns.as<uint32_t>()); if (rc) return rc; }
     uint32_t n_runs = 0;
     CK(hipMemcpyAsync(&n_runs, t->nruns.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     CK(hipMemsetAsync(t->hist.p, 0, (OATK_STAT_MAX_DEPTH + 1) * 8, ctx->stream));
