@@ -132,7 +132,8 @@ extern "C" int oatk_hip_debug_ec_tiers(oatk_hip_ctx *ctx, int cap_t0, int cap_t1
 
 // wf_ed_core alone (include/oatk_hip_ec.h): pack the codes sixteen to a word the way the solver holds its strings, one wave per job
 static int debug_ed_impl(oatk_hip_ctx *ctx, uint64_t n_jobs, const uint8_t *t_codes, const uint64_t *t_off, const uint8_t *q_codes, const uint64_t *q_off,
-                         const int32_t *bw, const int32_t *step_ql, const uint64_t *step_off, int32_t *out3, bool myers, float *kernel_ms, int wg_R = 0)
+                         const int32_t *bw, const int32_t *step_ql, const uint64_t *step_off, int32_t *out3, bool myers, float *kernel_ms, int wg_R = 0,
+                         int regroup = 1, uint32_t *turns = nullptr)
 {
     using namespace oatk;
     if (!ctx) return OATK_E_NODEV;
@@ -160,7 +161,7 @@ static int debug_ed_impl(oatk_hip_ctx *ctx, uint64_t n_jobs, const uint8_t *t_co
     };
     const std::vector<uint32_t> tw = pack(t_codes, t_off, tw_off, n_jobs), qw = pack(q_codes, q_off, qw_off, n_jobs);
     const uint64_t n_steps = step_off[n_jobs];
-    DevBuf d_tw, d_qw, d_two, d_qwo, d_tl, d_bw, d_sq, d_so, d_k, d_ko, d_out, d_slab;
+    DevBuf d_tw, d_qw, d_two, d_qwo, d_tl, d_bw, d_sq, d_so, d_k, d_ko, d_out, d_slab, d_turns;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (kernel_ms) { *kernel_ms = 0.f; (void) hipEventCreate(&ev0); (void) hipEventCreate(&ev1); }
     int32_t max_t = 0;
@@ -179,6 +180,7 @@ static int debug_ed_impl(oatk_hip_ctx *ctx, uint64_t n_jobs, const uint8_t *t_co
     up(d_two, tw_off.data(), (n_jobs + 1) * 8); up(d_qwo, qw_off.data(), (n_jobs + 1) * 8); up(d_ko, k_off.data(), (n_jobs + 1) * 8);
     up(d_tl, tl.data(), n_jobs * 4); up(d_bw, bw, n_jobs * 4); up(d_sq, step_ql, n_steps * 4); up(d_so, step_off, (n_jobs + 1) * 8);
     if (!rc && (!d_k.ensure(k_off[n_jobs] * 4 + 16, ctx->stream) || !d_out.ensure(n_steps * 12 + 16, ctx->stream))) rc = OATK_E_NOMEM;
+    if (!rc && turns && !d_turns.ensure(n_jobs * 4 + 16, ctx->stream)) rc = OATK_E_NOMEM;
     if (!rc && myers) {
         if (!d_slab.ensure(n_waves * slab_words * 8 + 64, ctx->stream) || !d_out.ensure(n_jobs * 12 + 16, ctx->stream)) rc = OATK_E_NOMEM;
         up(d_sq, ql_last.data(), n_jobs * 4);                        // (one query length per job: the last one asked for)
@@ -207,10 +209,11 @@ static int debug_ed_impl(oatk_hip_ctx *ctx, uint64_t n_jobs, const uint8_t *t_co
         } else
         hipLaunchKernelGGL(ecw_wf_ed_kernel, dim3((unsigned) n_jobs), dim3(64), 0, ctx->stream, d_tw.as<uint32_t>(), d_two.as<uint64_t>(), d_tl.as<int32_t>(),
                            d_qw.as<uint32_t>(), d_qwo.as<uint64_t>(), d_bw.as<int32_t>(), d_sq.as<int32_t>(), d_so.as<uint64_t>(), d_k.as<int32_t>(),
-                           d_ko.as<uint64_t>(), d_out.as<int32_t>());
+                           d_ko.as<uint64_t>(), d_out.as<int32_t>(), (int32_t) regroup, turns? d_turns.as<uint32_t>() : (uint32_t *) nullptr);
         if (ev1) (void) hipEventRecord(ev1, ctx->stream);
         const uint64_t n_out = myers? n_jobs : n_steps;
         if (n_out && (he = hipMemcpyAsync(out3, d_out.p, n_out * 12, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = OATK_E_NODEV;
+        if (!rc && turns && (he = hipMemcpyAsync(turns, d_turns.p, n_jobs * 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = OATK_E_NODEV;
         if ((he = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = OATK_E_NODEV;
         if (!rc && (he = hipGetLastError()) != hipSuccess) rc = OATK_E_NODEV;
     }
@@ -231,6 +234,44 @@ extern "C" int oatk_hip_debug_wf_ed(oatk_hip_ctx *ctx, uint64_t n_jobs, const ui
     const int rc = debug_ed_impl(ctx, n_jobs, t_codes, t_off, q_codes, q_off, bw, step_ql, step_off, out3, false, timed? &ms : nullptr);
     if (timed) fprintf(stderr, "[wf_ed_wg] R 0: %llu jobs, kernel %.3f ms\n", (unsigned long long) n_jobs, ms);
     return rc;
+}
+
+// ecw_step with its lanes regrouped (regroup != 0, what ships) or not, and the extension turns every job took (include/oatk_hip_ec.h)
+extern "C" int oatk_hip_debug_wf_ed_turns(oatk_hip_ctx *ctx, int regroup, uint64_t n_jobs, const uint8_t *t_codes, const uint64_t *t_off, const uint8_t *q_codes, const uint64_t *q_off,
+                                          const int32_t *bw, const int32_t *step_ql, const uint64_t *step_off, int32_t *out3, uint32_t *turns)
+{
+    if (!turns) { if (ctx) ctx->err = "oatk_hip_debug_wf_ed_turns: turns is null"; return OATK_E_ARG; }
+    return debug_ed_impl(ctx, n_jobs, t_codes, t_off, q_codes, q_off, bw, step_ql, step_off, out3, false, nullptr, 0, regroup != 0, turns);
+}
+
+// the refreshed table's coverage, forward counts and marks from sorted (key, occurrence) pairs on their own (include/oatk_hip_ec.h)
+extern "C" int oatk_hip_debug_cov_runs(oatk_hip_ctx *ctx, int runs, uint64_t n, const uint32_t *key_sorted, const uint64_t *occ, uint64_t nv, uint32_t *cov, uint32_t *fwd, uint8_t *del)
+{
+    using namespace oatk;
+    if (!ctx) return OATK_E_NODEV;
+    if (!nv || n >= 0xFFFFFFFFULL) { ctx->err = "oatk_hip_debug_cov_runs: no keys, or too many entries"; return OATK_E_ARG; }
+    for (uint64_t i = 0; i < n; ++i)
+        if (key_sorted[i] >= nv || (i && key_sorted[i] < key_sorted[i - 1])) { ctx->err = "oatk_hip_debug_cov_runs: keys must ascend and lie below nv"; return OATK_E_ARG; }
+    CK(hipSetDevice(ctx->device));
+    DevBuf d_key, d_occ, d_flag, d_cov, d_fwd, d_del;
+    if (!d_key.ensure(n * 4 + 16, ctx->stream) || !d_occ.ensure(n * 8 + 16, ctx->stream) || !d_flag.ensure(n * 4 + 16, ctx->stream) || !d_cov.ensure(nv * 4 + 16, ctx->stream) ||
+        !d_fwd.ensure(nv * 4 + 16, ctx->stream) || !d_del.ensure(nv + 16, ctx->stream)) { ctx->err = "oatk_hip_debug_cov_runs: hipMalloc failed"; return OATK_E_NOMEM; }
+    if (n) { CK(hipMemcpyAsync(d_key.p, key_sorted, n * 4, hipMemcpyHostToDevice, ctx->stream)); CK(hipMemcpyAsync(d_occ.p, occ, n * 8, hipMemcpyHostToDevice, ctx->stream)); }
+    CK(hipMemsetAsync(d_cov.p, 0, nv * 4, ctx->stream));
+    CK(hipMemsetAsync(d_fwd.p, 0, nv * 4, ctx->stream));
+    if (n && runs) hipLaunchKernelGGL(ec_cov_runs_kernel, grid256(n), dim3(256), 0, ctx->stream, n, d_key.as<uint32_t>(), d_occ.as<uint64_t>(), d_cov.as<uint32_t>(), d_fwd.as<uint32_t>());
+    else if (n) {
+        hipLaunchKernelGGL(ec_fwd_flag_kernel, grid256(n), dim3(256), 0, ctx->stream, n, d_occ.as<uint64_t>(), d_flag.as<uint32_t>());
+        PRIM(rocprim::inclusive_scan, d_flag.as<uint32_t>(), d_flag.as<uint32_t>(), n, rocprim::plus<uint32_t>(), ctx->stream);
+        hipLaunchKernelGGL(ec_cov_sorted_kernel, grid256(n), dim3(256), 0, ctx->stream, n, d_key.as<uint32_t>(), d_flag.as<uint32_t>(), d_cov.as<uint32_t>(), d_fwd.as<uint32_t>());
+    }
+    hipLaunchKernelGGL(ec_del_kernel, grid256(nv), dim3(256), 0, ctx->stream, nv, d_fwd.as<uint32_t>(), d_del.as<uint8_t>());
+    CK(hipMemcpyAsync(cov, d_cov.p, nv * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipMemcpyAsync(fwd, d_fwd.p, nv * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipMemcpyAsync(del, d_del.p, nv, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    CK(hipGetLastError());
+    return OATK_OK;
 }
 
 // the same through the workgroup solver's step (ec_heavy.hpp: ech_step, R = 1, 2 or 6 diagonals per lane); a job whose diagonals do not fit is refused
@@ -681,6 +722,12 @@ struct EcKnobs {
                                   // descriptors the one walk stages (ec_stage_blocks_wave_kernel, ec_fill_work_kernel) (A/B, tests)
     bool light_packed = true;     // OATK_DEBUG_EC_LIGHT_PACKED=0: the light graph's pairs sorted as 64-bit keys on vertex ids (ec_light_pairs), not on candidate ranks (A/B, tests)
     bool light_pairs = true;      // OATK_DEBUG_EC_LIGHT_PAIRS=0: in front of the sort on ranks, the pairs by a wave per read, a scan and a compaction instead of a lane per entry (A/B, tests)
+    bool regroup = true;          // OATK_DEBUG_EC_REGROUP=0: the wave solver's alignment keeps its lanes on the diagonals they started a step on (ec_wave.hpp: ecw_step) (A/B, tests)
+    int32_t batch = ECW_BATCH;    // OATK_DEBUG_EC_BATCH: blocks a first-tier wave takes from its queue at a time, 1 .. 64 (A/B, tests)
+    bool assemble_pairs = true;   // OATK_DEBUG_EC_ASSEMBLE_PAIRS=0: the corrected chains by a wave per read (ec_assemble_seg_kernel) instead of two reads to a wave where both have at most 32
+                                  // chain entries and blocks (ec_assemble_pair_kernel) (A/B, tests)
+    bool refresh_runs = true;     // OATK_DEBUG_EC_REFRESH_RUNS=0: coverage and forward counts of the refreshed table from flags, their prefix sums and a search per run end
+                                  // (ec_fwd_flag_kernel, a scan, ec_cov_sorted_kernel) instead of one pass over the sorted runs (ec_cov_runs_kernel) (A/B, tests)
     bool light_wide = false;      // OATK_DEBUG_EC_LIGHT_KEYBITS=64: packed keys of 64 bits whatever the number of candidates (tests: the form large candidate sets take)
 };
 static EcKnobs ec_knobs_read()
@@ -700,6 +747,11 @@ static EcKnobs ec_knobs_read()
     { const char *e = getenv("OATK_DEBUG_EC_QUEUE_SORT"); k.queue_sort = !(e && e[0] == '0' && !e[1]); }
     { const char *e = getenv("OATK_DEBUG_EC_LIGHT_PACKED"); k.light_packed = !(e && e[0] == '0' && !e[1]); }
     { const char *e = getenv("OATK_DEBUG_EC_LIGHT_PAIRS"); k.light_pairs = !(e && e[0] == '0' && !e[1]); }
+    { const char *e = getenv("OATK_DEBUG_EC_REGROUP"); k.regroup = !(e && e[0] == '0' && !e[1]); }
+    k.batch = num("OATK_DEBUG_EC_BATCH", 1, ECW_BATCH);
+    if (k.batch > 64) k.batch = 64;                    // (lane i holds block i of a batch)
+    { const char *e = getenv("OATK_DEBUG_EC_ASSEMBLE_PAIRS"); k.assemble_pairs = !(e && e[0] == '0' && !e[1]); }
+    { const char *e = getenv("OATK_DEBUG_EC_REFRESH_RUNS"); k.refresh_runs = !(e && e[0] == '0' && !e[1]); }
     { const char *e = getenv("OATK_DEBUG_EC_LIGHT_KEYBITS"); k.light_wide = e && !strcmp(e, "64"); }
     return k;
 }
@@ -967,21 +1019,21 @@ static int ec_queue_sort(oatk_hip_ctx *ctx, EcState *e, const uint32_t *list, ui
 }
 // blocks a wave of a larger tier takes from its queue at a time: consecutive blocks of a sorted list share a wave only in a batch, and a few hundred long blocks
 // must still have a wave each (r04e)
-static int32_t ec_routed_batch(uint64_t n_todo, uint64_t waves)
+static int32_t ec_routed_batch(uint64_t n_todo, uint64_t waves, int32_t cap)
 {
     const uint64_t b = waves? n_todo / (16 * waves) : 1;
-    return (int32_t) (b < 1? 1 : (b > ECW_BATCH? ECW_BATCH : b));
+    return (int32_t) (b < 1? 1 : (b > (uint64_t) cap? (uint64_t) cap : b));
 }
-// OATK_DEBUG_EC_STAGES: what the launches of ec_wave_kernel reused (EcwArgs::memo_stat: two counters per launch behind the cursor's 64)
+// OATK_DEBUG_EC_STAGES: what the launches of ec_wave_kernel reused and how many turns their alignments took (EcwArgs::memo_stat: three counters per launch behind the cursor's 64)
 struct EcMemoLog { int tier; unsigned long long n; int32_t batch; int slot; };
 static int ec_memo_report(oatk_hip_ctx *ctx, EcState *e, const std::vector<EcMemoLog> &log)
 {
     if (log.empty()) return OATK_OK;
-    unsigned long long c[128];
+    unsigned long long c[192];
     CK(hipMemcpyAsync(c, (unsigned long long *) e->cursor.p + 64, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
     for (const EcMemoLog &l : log)
-        fprintf(stderr, "[ec stages] wave solver, tier %d, %llu blocks: batch %d, %llu levels reused, %llu blocks started at their sink\n", l.tier, l.n, (int) l.batch, c[2 * l.slot], c[2 * l.slot + 1]);
+        fprintf(stderr, "[ec stages] wave solver, tier %d, %llu blocks: batch %d, %llu levels reused, %llu blocks started at their sink, %llu extension turns\n", l.tier, l.n, (int) l.batch, c[3 * l.slot], c[3 * l.slot + 1], c[3 * l.slot + 2]);
     return OATK_OK;
 }
 
@@ -1209,13 +1261,13 @@ static int ec_solve_classes(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, co
     if (T0.usable && n_work) {
         EcwArgs a = base;
         ec_set_caps(a, T0);
-        a.todo = nullptr, a.n_todo = 0, a.next = cur + qslot++, a.skip_l = T0.cap_t, a.batch = ECW_BATCH;
+        a.todo = nullptr, a.n_todo = 0, a.next = cur + qslot++, a.skip_l = T0.cap_t, a.batch = kn.batch;
         if (kn.queue_sort && n_work > 1) {          // (where the graph branches a walk ends at the first frame, and the kernel reuses nothing behind it)
             { int rc = ec_queue_room(ctx, e, n_work); if (rc) return rc; }
             { int rc = ec_queue_sort(ctx, e, nullptr, n_work, ctx->stream, ctx->tmp, &a.todo); if (rc) return rc; }
             a.n_todo = n_work;
         }
-        if (kn.stages) a.memo_stat = cur + 64 + 2 * mlog.size(), mlog.push_back(EcMemoLog{0, (unsigned long long) n_work, a.batch, (int) mlog.size()});
+        if (kn.stages) a.memo_stat = cur + 64 + 3 * mlog.size(), mlog.push_back(EcMemoLog{0, (unsigned long long) n_work, a.batch, (int) mlog.size()});
         // (a small block inside a repeat tries tens of thousands of arcs on a handful of diagonals -- 70 ms of ONE wave on the config-1 surrogate with everything else waiting
         //  for this launch: past the arc budget it is left to the classes and, past their step budget, to the second stage)
         a.arc_budget = EC_ARC_BUDGET;
@@ -1277,7 +1329,7 @@ static int ec_solve_tiers(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, cons
         ec_set_caps(a, t);
         a.todo = todo, a.n_todo = n_todo, a.next = queue;
         a.skip_l = routed && tier == 0? t.cap_t : 0x7FFFFFFF;
-        a.batch = ECW_BATCH;                                       // (a larger tier: by its blocks and waves, below)
+        a.batch = kn.batch;                                        // (a larger tier: by its blocks and waves, below)
         // a block outgrows an LDS tier by the depth of its search or by its frames (its length was checked before): the hybrid tier, without such limits, takes it
         const int nx = tier < LAST - 1 && T[LAST - 1].usable? LAST - 1 : next_usable(tier);
         a.todo_out = list[nx], a.todo_cnt = cur + nx;
@@ -1290,7 +1342,7 @@ static int ec_solve_tiers(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, cons
         if (tier > 0) {                                            // (241 long blocks in batches of sixteen were sixteen waves' work: r04e)
             uint64_t w1 = waves < n_items? waves : n_items;
             if (max_waves && w1 > max_waves) w1 = max_waves;
-            a.batch = ec_routed_batch(n_items, w1);
+            a.batch = ec_routed_batch(n_items, w1, kn.batch);
         }
         // the queue in source order: every block for the first tier, a routed list for a larger one where its waves take batches (a wave forgets between batches:
         // a list taken block by block gains nothing).  Sorted on the launch's own stream: the first tier does not wait for a side stream's list, and its own sort,
@@ -1306,7 +1358,7 @@ static int ec_solve_tiers(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, cons
         if (waves > groups) waves = groups;
         if (max_waves && waves > max_waves) waves = max_waves;
         if (!waves) return OATK_OK;
-        if (kn.stages && mlog.size() < 64) a.memo_stat = cur + 64 + 2 * mlog.size(), mlog.push_back(EcMemoLog{tier, (unsigned long long) n_items, a.batch, (int) mlog.size()});
+        if (kn.stages && mlog.size() < 64) a.memo_stat = cur + 64 + 3 * mlog.size(), mlog.push_back(EcMemoLog{tier, (unsigned long long) n_items, a.batch, (int) mlog.size()});
         if (t.hybrid) {
             void *p = nullptr;
             int rc = ec_slab_buf(ctx, e, hyb_k, (waves + ECW_WPB) * t.slab + 64, st, "the hybrid tier", "slabs", &p); if (rc) return rc;
@@ -1453,16 +1505,16 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     // classes with budgets and the second stage run: the config-1 surrogate has 304, and its searches are what they were built for (0.23 s against 3.2).
     const bool heavy = kn.heavy < 0? graph_branches : kn.heavy != 0;
     uint64_t pool_cap = 2 * nocc + (uint64_t) 16384 * ECW_POOL_CHUNK + 4096;
-    EENSURE(cursor, 512 + 128 * 8); EENSURE(stats, 16 * 8);              // (behind the 64 counters: two per launch of the wave solver, OATK_DEBUG_EC_STAGES)
+    EENSURE(cursor, 512 + 192 * 8); EENSURE(stats, 16 * 8);              // (behind the 64 counters: three per launch of the wave solver, OATK_DEBUG_EC_STAGES)
     uint64_t n_big = 0;
     uint32_t max_hl = 0;                 // the longest read of the batch, once the slab tier has needed it
     for (;;) {
         EENSURE(path_pool, pool_cap * 8);
-        CK(hipMemsetAsync(e->cursor.p, 0, 512 + 128 * 8, ctx->stream));
+        CK(hipMemsetAsync(e->cursor.p, 0, 512 + 192 * 8, ctx->stream));
         EcwArgs base = {};               // what every launch shares; each sets the rest of its own
         base.lv = lv, base.rd = rd, base.work = e->work.as<EcWork>(), base.n_work = n_work, base.max_edist = max_edist;
         base.out = e->out.as<EcBlockOut>(), base.path_pool = e->path_pool.as<uint64_t>(), base.pool_cap = pool_cap;
-        base.memo = kn.memo;
+        base.memo = kn.memo, base.regroup = kn.regroup;
         base.pool_cursor = (unsigned long long *) e->cursor.p;       // [0] pool, then the lists' and work queues' counters; [63] blocks that outgrew the slabs
         if (keep_seq) {
             CK(hipMemsetAsync(e->qend.p, 0, (n_work + 1) * 4, ctx->stream));
@@ -1504,6 +1556,7 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     aa.new_off = e->new_off.as<uint64_t>(), aa.new_k_mer = e->new_k.as<uint64_t>(), aa.new_m_pos = e->new_m.as<uint32_t>(), aa.new_s_mer = e->new_s.as<uint64_t>();
     aa.key_id = e->key_id.as<uint32_t>(), aa.val_occ = e->val_occ.as<uint64_t>(), aa.sid0 = ctx->sid0;
     if (kn.assemble_walk) hipLaunchKernelGGL(ec_assemble_wave_kernel<1>, rblocks, dim3(256), 0, ctx->stream, aa);
+    else if (kn.assemble_pairs) hipLaunchKernelGGL(ec_assemble_pair_kernel, dim3((unsigned) ((nr + 7) / 8 > 0? (nr + 7) / 8 : 1)), dim3(256), 0, ctx->stream, aa);      // four waves, two reads each
     else hipLaunchKernelGGL(ec_assemble_seg_kernel, rblocks, dim3(256), 0, ctx->stream, aa);
 
     // ---- update_syncmer_db ----
@@ -1515,11 +1568,15 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
         while (id_bits < 32 && (nv - 1) >> id_bits) ++id_bits;
         // stable: occurrences of one syncmer stay in (sid, idx) order (syncerr.c:796-805)
         PRIM(rocprim::radix_sort_pairs, e->key_id.as<uint32_t>(), e->key_sorted.as<uint32_t>(), e->val_occ.as<uint64_t>(), e->occ.as<uint64_t>(), tot, 0, id_bits, ctx->stream);
-        // coverage and forward-strand counts per syncmer from the sorted lists (key_id is free again: it carries the flags and their prefix sums)
+        // coverage and forward-strand counts per syncmer from the sorted lists: one pass over the runs (cov and fwd are zero: runs that cross a wave's tile add up), or
+        // (key_id is free again: it carries the flags and their prefix sums) the three passes it replaced
+        if (kn.refresh_runs) hipLaunchKernelGGL(ec_cov_runs_kernel, grid256(tot), dim3(256), 0, ctx->stream, tot, e->key_sorted.as<uint32_t>(), e->occ.as<uint64_t>(), e->cov.as<uint32_t>(), e->fwd.as<uint32_t>());
+        else {
         hipLaunchKernelGGL(ec_fwd_flag_kernel, grid256(tot), dim3(256), 0, ctx->stream, tot, e->occ.as<uint64_t>(), e->key_id.as<uint32_t>());
         PRIM(rocprim::inclusive_scan, e->key_id.as<uint32_t>(), e->key_id.as<uint32_t>(), tot, rocprim::plus<uint32_t>(), ctx->stream);
         hipLaunchKernelGGL(ec_cov_sorted_kernel, grid256(tot), dim3(256), 0, ctx->stream, tot, e->key_sorted.as<uint32_t>(), e->key_id.as<uint32_t>(),
                            e->cov.as<uint32_t>(), e->fwd.as<uint32_t>());
+        }
     }
     hipLaunchKernelGGL(ec_del_kernel, grid256(nv), dim3(256), 0, ctx->stream, nv, e->fwd.as<uint32_t>(), e->scm_del.as<uint8_t>());
     uint64_t chk = 0;

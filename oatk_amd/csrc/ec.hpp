@@ -778,6 +778,75 @@ __device__ __forceinline__ uint32_t ecr_incl_sum(uint32_t v)
 // interior's place among the path entries; a lane then finds the block its chain entry belongs to by comparing its index with the blocks' boundaries and
 // writes the entry if it stays, and the path interiors of all solved blocks of the read are copied together, 64 entries at a time.  Reads with more than 64
 // syncmers take ec_assemble_read_serial, as in ec_assemble_wave_kernel<1>, which this replaces (OATK_DEBUG_EC_ASSEMBLE_WALK=1 runs that one).
+// one read by the whole wave (r and everything read through it are wave-uniform)
+__device__ __forceinline__ void ec_assemble_seg_read(const EcAssembleArgs &a, uint64_t r, int lane)
+{
+    const uint64_t o = a.rd.scm_off[r], b0 = a.blk_off[r], w0 = a.new_off[r];
+    const int32_t n = ecr_s((int32_t) (a.rd.scm_off[r + 1] - o));
+    const uint64_t nb64 = a.blk_off[r + 1] - b0;
+    const int32_t nb = ecr_s(nb64 > 64? 65 : (int32_t) nb64);
+    const uint32_t room = (uint32_t) ecr_s((int32_t) (uint32_t) (a.new_off[r + 1] - w0));      // new_n[r]: nothing is written beyond it
+    const bool keep_all = ecr_s((int32_t) a.keep_all[r]) != 0;
+    if (n > 64 || nb > 64 || (nb == 0 && !keep_all)) {
+        if (lane == 0) ec_assemble_read_serial(a, r);
+        return;
+    }
+    const bool in = lane < n;
+    const uint64_t km = in? a.rd.k_mer[o + lane] : 0;
+    const uint32_t mp = in? a.rd.m_pos[o + lane] : 0;
+    const uint64_t my_s = in? a.old_s_mer[o + lane] : 0;    // a syncmer's s-mer is the same at every occurrence (count.hpp: check_smer_kernel)
+    const uint64_t sid = (a.sid0 + r) << 32;
+    auto write = [&](uint32_t idx, uint64_t kk, uint32_t m, uint64_t sv) {          // entry idx of the corrected chain
+        if (idx >= room) return;
+        const uint64_t w = w0 + idx;
+        a.new_k_mer[w] = kk, a.new_m_pos[w] = m, a.new_s_mer[w] = sv;
+        a.key_id[w] = (uint32_t) (kk >> 1), a.val_occ[w] = sid | (uint64_t) idx << 1 | (m & 1u);                  // syncerr.c:796-805
+    };
+    if (nb == 0) {                                   // no good syncmer: the read keeps its arrays (syncerr.c:562-572)
+        if (in) write((uint32_t) lane, km, mp, my_s);
+        return;
+    }
+    const bool isb = lane < nb;
+    EcSeg d;
+    d.beg = 0, d.end_fl = 0;
+    uint32_t status = EC_FAILURE, np = 0;
+    uint64_t path_off = 0;
+    if (isb) d = a.seg[b0 + lane], status = a.out[b0 + lane].status, np = a.out[b0 + lane].np, path_off = a.out[b0 + lane].path_off;
+    const uint32_t end = d.end_fl >> 2, prev = wave_prev(end), prev_end = lane == 0? 0u : prev;
+    const bool solved = isb && status == EC_SUCCESS;
+    const uint32_t front = isb? ec_seg_front(d, prev_end) : 0u, body = isb? ec_seg_body(d, status, np) : 0u, pc = solved? body : 0u;
+    const uint32_t at_incl = ecr_incl_sum(front + body), pt_incl = ecr_incl_sum(pc);
+    const uint32_t at = at_incl - (front + body), pt = pt_incl - pc;          // where block `lane`'s front starts; its path interior's place among the path entries
+    const uint32_t n_path = ecr_u32(pt_incl, 63);
+    // originals: entry `lane` lies in the stretch [prev_end(i), end(i)) of exactly one block i.  It stays if it is in front of the block (up to the anchor), or
+    // if the block is not corrected; its place is its distance from the stretch's start (front and body are adjacent in the chain, too)
+    {
+        const uint32_t meta = d.beg | (d.end_fl & EC_SEG_R) << 8 | (uint32_t) solved << 9;
+        const uint32_t base = at - prev_end;
+        uint32_t my_meta = 0, my_base = 0;
+        for (int32_t i = 0; i < nb; ++i) {
+            const uint32_t pe = ecr_u32(prev_end, i), mi = ecr_u32(meta, i), bi = ecr_u32(base, i);
+            if ((uint32_t) lane >= pe) my_meta = mi, my_base = bi;
+        }
+        const bool stays = !(my_meta >> 9 & 1u) || (!(my_meta >> 8 & 1u) && (uint32_t) lane <= (my_meta & 0xFFu));
+        if (in && stays) write(my_base + (uint32_t) lane, km, mp, my_s);
+    }
+    // path interiors: entry t of all of them belongs to the last block whose interiors start at or before t
+    for (uint32_t t0 = 0; t0 < n_path; t0 += 64) {
+        const uint32_t t = t0 + (uint32_t) lane;
+        int32_t bi = 0;
+        for (int32_t i = 0; i < nb; ++i) if (t >= ecr_u32(pt, i)) bi = i;
+        const uint32_t q = t - (uint32_t) __shfl((int32_t) pt, bi), dst = (uint32_t) __shfl((int32_t) (at + front), bi);
+        const int32_t bnp = __shfl((int32_t) np, bi);
+        const bool br = __shfl((int32_t) (d.end_fl & EC_SEG_R), bi) != 0;
+        const uint64_t poff = (uint64_t) (uint32_t) __shfl((int32_t) (uint32_t) (path_off >> 32), bi) << 32 | (uint32_t) __shfl((int32_t) (uint32_t) path_off, bi);
+        if (t < n_path) {
+            const uint64_t p = br? a.path_pool[poff + (uint32_t) (bnp - 1) - q] : a.path_pool[poff + 1 + q];
+            const uint64_t kk = (p & ~1ULL) | 1ULL;
+            write(dst + q, kk, br? 0xFFFFFFFFu ^ (uint32_t) (p & 1ULL) : 0xFFFFFFFEu | (uint32_t) (p & 1ULL), a.scm_s[kk >> 1]);
+        }
+    }
+}
 __global__ __launch_bounds__(256) void ec_assemble_seg_kernel(EcAssembleArgs a)
 {
     const uint64_t r0 = ((uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6)) * ECR_RPW;
@@ -787,70 +856,104 @@ __global__ __launch_bounds__(256) void ec_assemble_seg_kernel(EcAssembleArgs a)
     for (int k = 0; k < ECR_RPW; ++k) {
         const uint64_t r = r0 + k;
         if (r >= a.rd.n_reads) break;
-        const uint64_t o = a.rd.scm_off[r], b0 = a.blk_off[r], w0 = a.new_off[r];
-        const int32_t n = ecr_s((int32_t) (a.rd.scm_off[r + 1] - o));
-        const uint64_t nb64 = a.blk_off[r + 1] - b0;
-        const int32_t nb = ecr_s(nb64 > 64? 65 : (int32_t) nb64);
-        const uint32_t room = (uint32_t) ecr_s((int32_t) (uint32_t) (a.new_off[r + 1] - w0));      // new_n[r]: nothing is written beyond it
-        const bool keep_all = ecr_s((int32_t) a.keep_all[r]) != 0;
-        if (n > 64 || nb > 64 || (nb == 0 && !keep_all)) {
-            if (lane == 0) ec_assemble_read_serial(a, r);
-            continue;
+        ec_assemble_seg_read(a, r, lane);
+    }
+}
+
+// inclusive sums over the two halves of a wave, each on its own (rows of sixteen, then row_bcast 15 into rows 1 and 3); every lane must be active
+__device__ __forceinline__ uint32_t ecr_incl_sum32(uint32_t v)
+{
+    v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int32_t) v, 0x111, 0xf, 0xf, false);
+    v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int32_t) v, 0x112, 0xf, 0xf, false);
+    v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int32_t) v, 0x114, 0xf, 0xf, false);
+    v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int32_t) v, 0x118, 0xf, 0xf, false);
+    v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int32_t) v, 0x142, 0xa, 0xf, false);
+    return v;
+}
+
+// Two reads to a wave (r20).  A read of config 3 has 21 chain entries (99.9 % have at most 32), so a wave per read ran a third full and the kernel's time was its
+// waves times a chain of dependent loads.  Wave w takes reads 2 w and 2 w + 1: when both have at most 32 chain entries and at most 32 blocks (and are not the
+// block-less kind that the serial routine takes), lanes 0 - 31 hold the first and lanes 32 - 63 the second, entry l and block l in lane l of the half -- the prefix
+// sums are 32-lane sums, the per-block broadcasts read lane i and lane 32 + i and a lane takes its half's, and the loops run as long as the longer half needs.
+// Any other pair is two passes of ec_assemble_seg_read by the same wave.  Which reads share a wave is a function of their counts alone, and a read's entries go
+// to the same places either way.  OATK_DEBUG_EC_ASSEMBLE_PAIRS=0 launches ec_assemble_seg_kernel, a wave per read.
+__global__ __launch_bounds__(256) void ec_assemble_pair_kernel(EcAssembleArgs a)
+{
+    const uint64_t rp = ((uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6)) * 2;
+    const int lane = threadIdx.x & 63, h = lane >> 5, l = lane & 31;
+    if (rp >= a.rd.n_reads) return;
+    bool ok = rp + 1 < a.rd.n_reads;
+    if (ok) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const uint64_t n64 = a.rd.scm_off[rp + k + 1] - a.rd.scm_off[rp + k], nb64 = a.blk_off[rp + k + 1] - a.blk_off[rp + k];
+            ok = ok && n64 <= 32 && nb64 <= 32 && (nb64 > 0 || a.keep_all[rp + k] != 0);
         }
-        const bool in = lane < n;
-        const uint64_t km = in? a.rd.k_mer[o + lane] : 0;
-        const uint32_t mp = in? a.rd.m_pos[o + lane] : 0;
-        const uint64_t my_s = in? a.old_s_mer[o + lane] : 0;    // a syncmer's s-mer is the same at every occurrence (count.hpp: check_smer_kernel)
-        const uint64_t sid = (a.sid0 + r) << 32;
-        auto write = [&](uint32_t idx, uint64_t kk, uint32_t m, uint64_t sv) {          // entry idx of the corrected chain
-            if (idx >= room) return;
-            const uint64_t w = w0 + idx;
-            a.new_k_mer[w] = kk, a.new_m_pos[w] = m, a.new_s_mer[w] = sv;
-            a.key_id[w] = (uint32_t) (kk >> 1), a.val_occ[w] = sid | (uint64_t) idx << 1 | (m & 1u);                  // syncerr.c:796-805
-        };
-        if (nb == 0) {                                   // no good syncmer: the read keeps its arrays (syncerr.c:562-572)
-            if (in) write((uint32_t) lane, km, mp, my_s);
-            continue;
+    }
+    if (!ecr_s((int32_t) ok)) {
+        ec_assemble_seg_read(a, rp, lane);
+        if (rp + 1 < a.rd.n_reads) ec_assemble_seg_read(a, rp + 1, lane);
+        return;
+    }
+    const uint64_t r = rp + (uint64_t) h;              // this half's read; what follows is uniform within a half
+    const uint64_t o = a.rd.scm_off[r], b0 = a.blk_off[r], w0 = a.new_off[r];
+    const int32_t n = (int32_t) (a.rd.scm_off[r + 1] - o), nb = (int32_t) (a.blk_off[r + 1] - b0);
+    const uint32_t room = (uint32_t) (a.new_off[r + 1] - w0);
+    const int32_t nb_max = ecr_s(__builtin_amdgcn_readlane(nb, 0) > __builtin_amdgcn_readlane(nb, 32)? __builtin_amdgcn_readlane(nb, 0) : __builtin_amdgcn_readlane(nb, 32));
+    const bool in = l < n;
+    const uint64_t km = in? a.rd.k_mer[o + l] : 0;
+    const uint32_t mp = in? a.rd.m_pos[o + l] : 0;
+    const uint64_t my_s = in? a.old_s_mer[o + l] : 0;
+    const uint64_t sid = (a.sid0 + r) << 32;
+    auto write = [&](uint32_t idx, uint64_t kk, uint32_t m, uint64_t sv) {
+        if (idx >= room) return;
+        const uint64_t w = w0 + idx;
+        a.new_k_mer[w] = kk, a.new_m_pos[w] = m, a.new_s_mer[w] = sv;
+        a.key_id[w] = (uint32_t) (kk >> 1), a.val_occ[w] = sid | (uint64_t) idx << 1 | (m & 1u);
+    };
+    const bool isb = l < nb;
+    EcSeg d;
+    d.beg = 0, d.end_fl = 0;
+    uint32_t status = EC_FAILURE, np = 0;
+    uint64_t path_off = 0;
+    if (isb) d = a.seg[b0 + l], status = a.out[b0 + l].status, np = a.out[b0 + l].np, path_off = a.out[b0 + l].path_off;
+    const uint32_t end = d.end_fl >> 2, prev = wave_prev(end), prev_end = l == 0? 0u : prev;
+    const bool solved = isb && status == EC_SUCCESS;
+    const uint32_t front = isb? ec_seg_front(d, prev_end) : 0u, body = isb? ec_seg_body(d, status, np) : 0u, pc = solved? body : 0u;
+    const uint32_t at_incl = ecr_incl_sum32(front + body), pt_incl = ecr_incl_sum32(pc);
+    const uint32_t at = at_incl - (front + body), pt = pt_incl - pc;
+    const uint32_t np0 = ecr_u32(pt_incl, 31), np1 = ecr_u32(pt_incl, 63);
+    const uint32_t n_path = h? np1 : np0, n_path_max = np0 > np1? np0 : np1;
+    // originals (a half without a block keeps its chain: my_meta and my_base stay 0, every entry stays where it is)
+    {
+        const uint32_t meta = d.beg | (d.end_fl & EC_SEG_R) << 8 | (uint32_t) solved << 9;
+        const uint32_t base = at - prev_end;
+        uint32_t my_meta = 0, my_base = 0;
+        for (int32_t i = 0; i < nb_max; ++i) {
+            const uint32_t pe = h? ecr_u32(prev_end, 32 + i) : ecr_u32(prev_end, i), mi = h? ecr_u32(meta, 32 + i) : ecr_u32(meta, i),
+                           bi = h? ecr_u32(base, 32 + i) : ecr_u32(base, i);
+            if (i < nb && (uint32_t) l >= pe) my_meta = mi, my_base = bi;
         }
-        const bool isb = lane < nb;
-        EcSeg d;
-        d.beg = 0, d.end_fl = 0;
-        uint32_t status = EC_FAILURE, np = 0;
-        uint64_t path_off = 0;
-        if (isb) d = a.seg[b0 + lane], status = a.out[b0 + lane].status, np = a.out[b0 + lane].np, path_off = a.out[b0 + lane].path_off;
-        const uint32_t end = d.end_fl >> 2, prev = wave_prev(end), prev_end = lane == 0? 0u : prev;
-        const bool solved = isb && status == EC_SUCCESS;
-        const uint32_t front = isb? ec_seg_front(d, prev_end) : 0u, body = isb? ec_seg_body(d, status, np) : 0u, pc = solved? body : 0u;
-        const uint32_t at_incl = ecr_incl_sum(front + body), pt_incl = ecr_incl_sum(pc);
-        const uint32_t at = at_incl - (front + body), pt = pt_incl - pc;          // where block `lane`'s front starts; its path interior's place among the path entries
-        const uint32_t n_path = ecr_u32(pt_incl, 63);
-        // originals: entry `lane` lies in the stretch [prev_end(i), end(i)) of exactly one block i.  It stays if it is in front of the block (up to the anchor), or
-        // if the block is not corrected; its place is its distance from the stretch's start (front and body are adjacent in the chain, too)
-        {
-            const uint32_t meta = d.beg | (d.end_fl & EC_SEG_R) << 8 | (uint32_t) solved << 9;
-            const uint32_t base = at - prev_end;
-            uint32_t my_meta = 0, my_base = 0;
-            for (int32_t i = 0; i < nb; ++i) {
-                const uint32_t pe = ecr_u32(prev_end, i), mi = ecr_u32(meta, i), bi = ecr_u32(base, i);
-                if ((uint32_t) lane >= pe) my_meta = mi, my_base = bi;
-            }
-            const bool stays = !(my_meta >> 9 & 1u) || (!(my_meta >> 8 & 1u) && (uint32_t) lane <= (my_meta & 0xFFu));
-            if (in && stays) write(my_base + (uint32_t) lane, km, mp, my_s);
+        const bool stays = !(my_meta >> 9 & 1u) || (!(my_meta >> 8 & 1u) && (uint32_t) l <= (my_meta & 0xFFu));
+        if (in && stays) write(my_base + (uint32_t) l, km, mp, my_s);
+    }
+    // path interiors, 32 entries of each half at a time
+    for (uint32_t t0 = 0; t0 < n_path_max; t0 += 32) {
+        const uint32_t t = t0 + (uint32_t) l;
+        int32_t bi = 0;
+        for (int32_t i = 0; i < nb_max; ++i) {
+            const uint32_t pti = h? ecr_u32(pt, 32 + i) : ecr_u32(pt, i);
+            if (i < nb && t >= pti) bi = i;
         }
-        // path interiors: entry t of all of them belongs to the last block whose interiors start at or before t
-        for (uint32_t t0 = 0; t0 < n_path; t0 += 64) {
-            const uint32_t t = t0 + (uint32_t) lane;
-            int32_t bi = 0;
-            for (int32_t i = 0; i < nb; ++i) if (t >= ecr_u32(pt, i)) bi = i;
-            const uint32_t q = t - (uint32_t) __shfl((int32_t) pt, bi), dst = (uint32_t) __shfl((int32_t) (at + front), bi);
-            const int32_t bnp = __shfl((int32_t) np, bi);
-            const bool br = __shfl((int32_t) (d.end_fl & EC_SEG_R), bi) != 0;
-            const uint64_t poff = (uint64_t) (uint32_t) __shfl((int32_t) (uint32_t) (path_off >> 32), bi) << 32 | (uint32_t) __shfl((int32_t) (uint32_t) path_off, bi);
-            if (t < n_path) {
-                const uint64_t p = br? a.path_pool[poff + (uint32_t) (bnp - 1) - q] : a.path_pool[poff + 1 + q];
-                const uint64_t kk = (p & ~1ULL) | 1ULL;
-                write(dst + q, kk, br? 0xFFFFFFFFu ^ (uint32_t) (p & 1ULL) : 0xFFFFFFFEu | (uint32_t) (p & 1ULL), a.scm_s[kk >> 1]);
-            }
+        const int src = (h << 5) + bi;
+        const uint32_t q = t - (uint32_t) __shfl((int32_t) pt, src), dst = (uint32_t) __shfl((int32_t) (at + front), src);
+        const int32_t bnp = __shfl((int32_t) np, src);
+        const bool br = __shfl((int32_t) (d.end_fl & EC_SEG_R), src) != 0;
+        const uint64_t poff = (uint64_t) (uint32_t) __shfl((int32_t) (uint32_t) (path_off >> 32), src) << 32 | (uint32_t) __shfl((int32_t) (uint32_t) path_off, src);
+        if (t < n_path) {
+            const uint64_t p = br? a.path_pool[poff + (uint32_t) (bnp - 1) - q] : a.path_pool[poff + 1 + q];
+            const uint64_t kk = (p & ~1ULL) | 1ULL;
+            write(dst + q, kk, br? 0xFFFFFFFFu ^ (uint32_t) (p & 1ULL) : 0xFFFFFFFEu | (uint32_t) (p & 1ULL), a.scm_s[kk >> 1]);
         }
     }
 }
@@ -874,6 +977,28 @@ __global__ void ec_cov_sorted_kernel(uint64_t tot, const uint32_t *key_sorted, c
     }
     cov[k] = (uint32_t) (i - lo + 1);
     fwd[k] = fwd_incl[i] - (lo? fwd_incl[lo - 1] : 0u);
+}
+
+// The same in one pass (r20): a lane per entry, and a wave finds the runs of equal keys in its 64 entries with two ballots.  The lane at a run's head counts the run's entries
+// and its forward strands in the ballots; a run that begins behind the wave's first lane and ends in front of its last valid one belongs to nobody else and is stored, the
+// (at most two) runs that may go on in a neighbouring wave are added atomically -- cov and fwd are zero before the pass, and sums of integers do not depend on their order
+__global__ __launch_bounds__(256) void ec_cov_runs_kernel(uint64_t tot, const uint32_t *key_sorted, const uint64_t *occ, uint32_t *cov, uint32_t *fwd)
+{
+    const uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool valid = i < tot;
+    const uint32_t k = valid? key_sorted[i] : 0u;
+    const bool f = valid && !(occ[valid? i : 0] & 1ULL);
+    const uint32_t prev = (uint32_t) __shfl_up((int) k, 1);
+    const bool head = valid && (lane == 0 || prev != k);
+    const uint64_t heads = __ballot(head), fw = __ballot(f), vm = __ballot(valid);
+    if (!head) return;
+    const uint64_t above = lane == 63? 0ULL : heads & ~((2ULL << lane) - 1ULL);         // heads behind this one
+    const int end = above? __builtin_ctzll(above) : __builtin_popcountll(vm);           // one past the run's last lane here (the valid lanes are the low ones)
+    const uint64_t m = (end == 64? ~0ULL : (1ULL << end) - 1ULL) & ~((1ULL << lane) - 1ULL);
+    const uint32_t c = (uint32_t) (end - lane), fc = (uint32_t) __builtin_popcountll(fw & m);
+    if (lane > 0 && above) cov[k] = c, fwd[k] = fc;
+    else atomicAdd(cov + k, c), atomicAdd(fwd + k, fc);
 }
 
 __global__ void ec_del_kernel(uint64_t n, const uint32_t *fwd, uint8_t *del)

@@ -119,6 +119,7 @@ struct EcwScratch {
     uint8_t *frames;              // DFS frame arena
     int32_t cap_t, cap_c, cap_w, cap_path, cap_f;
     int32_t arc_budget;           // arcs after which a block is given up here (0: never): a search inside a repeat tries tens of thousands (round 6)
+    int32_t regroup;              // ecw_step: all 64 lanes join the last diagonal alive (0: OATK_DEBUG_EC_REGROUP=0, the lanes stay where the step put them)
 };
 
 struct EcwFrame {                 // state at the entry of one DFS level (syncerr.c:158-171), followed by k[n]
@@ -132,8 +133,10 @@ struct EcwWave {                  // the working wavefront: diagonals d0 .. d0 +
 };
 
 // one wavefront step (levdist.c:156-224, extension mode, no traceback); returns 1 when an end was reached
+// regroup: once ONE diagonal of up to 64 is left alive, every lane compares for it (below); turns: the extension turns taken are added up (OATK_DEBUG_EC_STAGES, and the debug entry
+// point: one scalar add a turn, which measured nothing at config 3 -- DESIGN.md 7, r20)
 __device__ int ecw_step(const uint32_t *ts, int32_t tl, const uint32_t *qs, int32_t ql, int32_t bw, EcwWave &wv, int32_t *buf_a, int32_t *buf_b,
-                        int32_t &t_end, int32_t &q_end)
+                        int32_t &t_end, int32_t &q_end, int32_t regroup, uint32_t &turns)
 {
     const int lane = threadIdx.x & 63;
     const int32_t n = wv.n, d0 = wv.d0;
@@ -143,6 +146,7 @@ __device__ int ecw_step(const uint32_t *ts, int32_t tl, const uint32_t *qs, int3
     if (n <= 32) lg = n <= 1? 6 : __builtin_clz((uint32_t) (n - 1)) - 26;      // 64 / next_pow2(n)
     const int G = 1 << lg, c = lane & (G - 1), gbase = lane & ~(G - 1);
     const uint64_t gmask = G == 64? ~0ULL : (1ULL << G) - 1ULL;
+    const int lone = regroup && G < 64? G : -1;        // lanes alive when one group is (-1: never looked for)
     // More than 64 diagonals (a long block late in a failing path: up to 2 bw + 1 = several hundred): one lane per diagonal, and FOUR rounds of 64 diagonals
     // side by side -- the rounds are independent chains of LDS round trips (wavefront entry, two windows of each string, the comparison), and one after the
     // other they left the wave waiting for LDS most of the time: a long block of the config-1 surrogate took 2.5 s, forty times a CPU core (r04g).  What
@@ -161,6 +165,7 @@ __device__ int ecw_step(const uint32_t *ts, int32_t tl, const uint32_t *qs, int3
                 lim[u] = (ql - dd[u] < tl? ql - dd[u] : tl) - 1;
             }
             while (__ballot(act[0] | act[1] | act[2] | act[3])) {
+                ++turns;
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int32_t r = lim[u] - kk[u];
@@ -214,7 +219,35 @@ __device__ int ecw_step(const uint32_t *ts, int32_t tl, const uint32_t *qs, int3
                 const int32_t adv = gb? (first << 4) + mm : G << 4;
                 kk += act? adv : 0;
                 act = act && gb == 0;
-                if (!__ballot(act)) break;
+                ++turns;
+                const uint64_t alive = __ballot(act);
+                if (!alive) break;
+                // After an error all diagonals but one die inside their first window, and the one that lives then went on at G windows a turn beside
+                // 64 - G idle lanes.  Its group is alive as a whole (act is the group's), so G lanes alive means one group: the wave carries on for it
+                // alone, 1024 bases a turn, on a wave-uniform k -- the furthest match of a diagonal does not depend on which lanes compared what.
+                if (ECW_RARE(__builtin_popcountll(alive) == lone)) {
+                    const int ld = __builtin_ctzll(alive);          // the group's first lane: the one that answers for the diagonal below
+                    int32_t k1 = (int32_t) ecw_lane((uint32_t) kk, ld);
+                    const int32_t d1 = (int32_t) ecw_lane((uint32_t) dd, ld), l1 = (int32_t) ecw_lane((uint32_t) lim, ld), o1 = lane << 4;
+                    for (;;) {
+                        const int32_t r1 = l1 - k1 - o1;
+                        const int32_t oo1 = r1 > 0? o1 : 0;
+                        const uint32_t x1 = ecw_win16(ts, k1 + 1 + oo1) ^ ecw_win16(qs, k1 + d1 + 1 + oo1);
+                        int32_t m1 = x1? __builtin_ctz(x1) >> 1 : 16;
+                        m1 = m1 < r1? m1 : r1;
+                        m1 = r1 > 0? m1 : 0;
+                        const uint64_t gb1 = __ballot(m1 != 16);
+                        ++turns;
+                        if (gb1) {
+                            const int f1 = __builtin_ctzll(gb1);
+                            k1 += (f1 << 4) + (int32_t) ecw_lane((uint32_t) m1, f1);
+                            break;
+                        }
+                        k1 += 1024;
+                    }
+                    kk = lane == ld? k1 : kk;
+                    break;
+                }
             }
         }
         const bool reached = act0 && (kk + dd == ql - 1 || kk == tl - 1);
@@ -265,7 +298,7 @@ __device__ int ecw_step(const uint32_t *ts, int32_t tl, const uint32_t *qs, int3
 // exactly as the DFS keeps it from one appended k-mer to the next (include/oatk_hip_ec.h: oatk_hip_debug_wf_ed)
 __global__ __launch_bounds__(64) void ecw_wf_ed_kernel(const uint32_t *tw, const uint64_t *tw_off, const int32_t *tl, const uint32_t *qw, const uint64_t *qw_off,
                                                        const int32_t *bw, const int32_t *step_ql, const uint64_t *step_off, int32_t *kbuf, const uint64_t *k_off,
-                                                       int32_t *out3)
+                                                       int32_t *out3, int32_t regroup, uint32_t *turns_out)
 {
     const uint64_t j = blockIdx.x;
     const uint32_t *ts = tw + tw_off[j], *qs = qw + qw_off[j];
@@ -276,15 +309,17 @@ __global__ __launch_bounds__(64) void ecw_wf_ed_kernel(const uint32_t *tw, const
     if (threadIdx.x == 0) ka[0] = -1;
     ecw_sync();
     int32_t score = 0, t_end = -1, q_end = -1;
+    uint32_t turns = 0;
     for (uint64_t s = step_off[j]; s < step_off[j + 1]; ++s) {
         const int32_t ql = step_ql[s];
         for (;;) {
-            if (ecw_step(ts, tlen, qs, ql, band, wv, ka, kb, t_end, q_end)) break;
+            if (ecw_step(ts, tlen, qs, ql, band, wv, ka, kb, t_end, q_end, regroup, turns)) break;
             ++score;
             if (band >= 0 && score > band) break;
         }
         if (threadIdx.x == 0) out3[3 * s] = score, out3[3 * s + 1] = t_end + 1, out3[3 * s + 2] = q_end + 1;
     }
+    if (turns_out && threadIdx.x == 0) turns_out[j] = turns;          // (oatk_hip_debug_wf_ed_turns)
 }
 
 #ifdef OATK_EXPERIMENTS            // (tools/experiments/: built into a library of its own, not into liboatk_hip.so)
@@ -381,6 +416,7 @@ struct EcwMemo {
     int32_t ff_cl0, ff_clp;       // c_len after level 0, and before level ff_d
     int32_t mode;                 // 0: off (OATK_DEBUG_EC_MEMO=0), 1: levels only, 2: levels and the start at the sink
     uint32_t n_reuse, n_ff;       // levels not appended again, blocks started at their sink (OATK_DEBUG_EC_STAGES)
+    uint32_t n_turns;             // extension turns of ecw_step, counted beside them
     __device__ __forceinline__ void reset() { src = ff_end = EC_NONE, depth = 0, ff_d = 0, ff_arc = 0, ff_cl0 = ff_clp = 0; }
 };
 
@@ -565,7 +601,7 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
         // wf_ed_core (levdist.c:265-310)
         for (;;) {
             ++wf_steps, wf_diag += (uint64_t) wv.n;
-            if (ecw_step(s.ts, tl, s.cs, c_len, bw, wv, s.ka, s.kb, t_end, q_end)) break;
+            if (ecw_step(s.ts, tl, s.cs, c_len, bw, wv, s.ka, s.kb, t_end, q_end, s.regroup, mm.n_turns)) break;
             ++score;
             if (ECW_RARE(score > bw)) break;
         }
@@ -635,7 +671,8 @@ __device__ bool ecw_solve_block(const EcLive &lv, const EcReads &rd, const EcWor
 #define ECW_WPB 2                 // waves per workgroup of the LDS tiers (independent of each other: ecw_sync)
 #endif
 #ifndef ECW_BATCH
-#define ECW_BATCH 16              // blocks taken from the queue per atomic (config 3: 8 -> 14.13 ms, 16 -> 13.83, 32 -> 13.86)
+#define ECW_BATCH 32              // blocks taken from the queue per atomic, and how long a wave's memo lives (config 3, r20: 16 -> 11.65 ms, 32 -> 11.48, 64 -> 11.51;
+                                  // before the memo, r04: 8 -> 14.13, 16 -> 13.83, 32 -> 13.86).  At most 64: lane i holds block i of a batch
 #endif
 #define ECW_POOL_CHUNK 512        // path-pool entries taken per atomic
 
@@ -663,7 +700,8 @@ struct EcwArgs {
     int32_t batch;                // blocks taken from the queue per atomic: ECW_BATCH where the blocks are millions and small, 1 where they are few and long
     int32_t arc_budget;           // first tier: arcs after which a block is left to the classes behind it (0: never)
     int32_t memo;                 // EcwMemo::mode
-    unsigned long long *memo_stat; // OATK_DEBUG_EC_STAGES: [0] levels reused, [1] blocks started at their sink, added once per wave (null: not counted)
+    int32_t regroup;              // EcwScratch::regroup
+    unsigned long long *memo_stat; // OATK_DEBUG_EC_STAGES: [0] levels reused, [1] blocks started at their sink, [2] extension turns, added once per wave (null: not counted)
     // oatk_hip_ec_keep_seq (the KEEP instantiations of the solver kernels; null otherwise): what a corrected read's sequence needs of a block besides its path
     uint32_t *seq_qend;           // [n_work] q_end of the optimum alignment = bases of the optimum consensus that replace the block (syncerr.c:247-248); 0 = not replaced
     uint32_t *seq_slots;          // the optimum consensus itself, sixteen bases to a word as the solver holds it: block i at word seq_slot_off[i]
@@ -787,6 +825,7 @@ __global__ __launch_bounds__(64 * WPB) void ec_wave_kernel(EcwArgs a)
     EcwScratch s;
     s.cap_t = a.cap_t, s.cap_c = a.cap_c, s.cap_w = a.cap_w, s.cap_path = a.cap_path, s.cap_f = a.cap_f;
     s.arc_budget = MODE == 0? a.arc_budget : 0;
+    s.regroup = a.regroup;
     uint32_t *const p0 = BIG? (uint32_t *) (a.slabs + (uint64_t) wave * a.slab_bytes)
                             : ecw_lds + (WPB > 1? ecw_uniu(threadIdx.x >> 6) * (MODE == 2? ecw_lds_words_hybrid(a.cap_t, a.cap_c, a.cap_w)
                                                                                                       : ecw_scratch_words(a.cap_t, a.cap_c, a.cap_w, a.cap_path, a.cap_f, false)) : 0u);
@@ -807,7 +846,7 @@ __global__ __launch_bounds__(64 * WPB) void ec_wave_kernel(EcwArgs a)
     const uint64_t total = a.todo? a.n_todo : a.n_work;
     uint64_t pool_at = 0, pool_end = 0;                // this wave's chunk of the path pool
     EcwMemo mm;
-    mm.mode = a.memo, mm.n_reuse = mm.n_ff = 0;
+    mm.mode = a.memo, mm.n_reuse = mm.n_ff = mm.n_turns = 0;
     for (;;) {
         unsigned long long t0 = 0;
         if (lane == 0) t0 = atomicAdd(a.next, (unsigned long long) a.batch);
@@ -863,9 +902,10 @@ __global__ __launch_bounds__(64 * WPB) void ec_wave_kernel(EcwArgs a)
             ecw_sync();
         }
     }
-    if (a.memo_stat && lane == 0 && (mm.n_reuse | mm.n_ff)) {
+    if (a.memo_stat && lane == 0 && (mm.n_reuse | mm.n_ff | mm.n_turns)) {
         atomicAdd(a.memo_stat, (unsigned long long) mm.n_reuse);
         atomicAdd(a.memo_stat + 1, (unsigned long long) mm.n_ff);
+        atomicAdd(a.memo_stat + 2, (unsigned long long) mm.n_turns);
     }
 }
 

@@ -247,7 +247,20 @@ class HipSyncasm:
         self._check(self.L.oatk_hip_ec_stats(self.h, st.ctypes.data), "oatk_hip_ec_stats")
         return st
 
-    def wf_ed(self, jobs, wg=0):
+    def cov_runs(self, key_sorted, occ, nv, runs=True):
+        """the refreshed table's (cov, fwd, del) from sorted (key, occurrence) pairs (oatk_hip_debug_cov_runs): in one pass over the runs (what ships) or, runs=False, the three passes it replaced"""
+        key, oc = np.ascontiguousarray(key_sorted, np.uint32), np.ascontiguousarray(occ, np.uint64)
+        cov, fwd, dl = np.zeros(nv, np.uint32), np.zeros(nv, np.uint32), np.zeros(nv, np.uint8)
+        self._check(self.L.oatk_hip_debug_cov_runs(self.h, int(bool(runs)), len(key), key.ctypes.data, oc.ctypes.data, nv, cov.ctypes.data, fwd.ctypes.data, dl.ctypes.data), "oatk_hip_debug_cov_runs")
+        return cov, fwd, dl
+
+    def wf_ed_turns(self, jobs, regroup=True):
+        """wf_ed through the wave solver's step with its lanes following the last diagonal alive (regroup, what ships) or not (oatk_hip_debug_wf_ed_turns):
+        returns (results as wf_ed gives them, extension turns per job)"""
+        turns = np.zeros(len(jobs), np.uint32)
+        return self.wf_ed(jobs, turns=turns, regroup=regroup), [int(t) for t in turns]
+
+    def wf_ed(self, jobs, wg=0, turns=None, regroup=True):
         """the device edit distance on its own (oatk_hip_debug_wf_ed; wg = 1, 2 or 6: through the step of the workgroup solver, oatk_hip_debug_wf_ed_wg): jobs = [(target, query, bw, [ql, ...]), ...] with target / query as
         bytes over ACGT (any case); returns, per job, the list of (score, t_end, q_end) after each query length -- what wf_ed_core
         (levdist.c:265-312, extension mode) leaves in a wf_config_t that is resumed with a longer and longer query"""
@@ -268,6 +281,9 @@ class HipSyncasm:
         if wg:
             self._check(self.L.oatk_hip_debug_wf_ed_wg(self.h, wg, len(jobs), tc.ctypes.data, t_off.ctypes.data, qc.ctypes.data, q_off.ctypes.data, bw.ctypes.data,
                                                        ql.ctypes.data, s_off.ctypes.data, out.ctypes.data), "oatk_hip_debug_wf_ed_wg")
+        elif turns is not None:
+            self._check(self.L.oatk_hip_debug_wf_ed_turns(self.h, int(bool(regroup)), len(jobs), tc.ctypes.data, t_off.ctypes.data, qc.ctypes.data, q_off.ctypes.data, bw.ctypes.data,
+                                                          ql.ctypes.data, s_off.ctypes.data, out.ctypes.data, turns.ctypes.data), "oatk_hip_debug_wf_ed_turns")
         else:
             self._check(self.L.oatk_hip_debug_wf_ed(self.h, len(jobs), tc.ctypes.data, t_off.ctypes.data, qc.ctypes.data, q_off.ctypes.data, bw.ctypes.data,
                                                     ql.ctypes.data, s_off.ctypes.data, out.ctypes.data), "oatk_hip_debug_wf_ed")
