@@ -25,10 +25,11 @@
 //    barriers, placed so that the s-mer hashing of the next tile (registers only) overlaps with the slower waves' decisions on this one.
 //  * two forms: two waves per workgroup on a 2048-slot ring (tiles of 1024 positions; K - S <= 1023) and four waves on 4096 slots.  A read's last tile
 //    costs a tile's time however little of it lies inside the read, and two waves meet at a barrier sooner than four (r03p).
-//  * what bounds it: 13.6 KB of LDS and 80 registers let eleven two-wave workgroups onto a CU; 72 VALU wave-instructions per position, 39 of them
-//    the rolling canonical s-mer and hash64, at 0.95 of the issue ceiling of that opcode mix.  Ring addresses alternate between two values per
-//    lane (a tile is half the ring) and are toggled, not recomputed; end-of-read special cases are decided per wave, not per lane.
-//    DESIGN.md 5 has the measurements.
+//  * what bounds it: 13.6 KB of LDS and 80 registers let eleven two-wave workgroups onto a CU; instruction issue, at the ceiling of its opcode mix.  An
+//    ordinary tile (an inside wave, no repeat mode, no candidate) is 344 VALU wave-instructions per wave -- 43 per position -- of which 241 are the eight
+//    hashes (the canonical s-mer as two bit fields per strand, and hash64); 51 per position over a whole batch, read ends, candidates and ties included.
+//    Ring addresses alternate between two values per lane (a tile is half the ring) and are toggled, not recomputed; end-of-read special cases and
+//    repeat mode are decided per wave on scalars, not per lane.  DESIGN.md 5 has the measurements and the per-purpose table (r21).
 //  * selected syncmers leave as (sid|ordinal|rev, s-mer code, pos) records; their 251-byte k-mers are hashed
 //    afterwards by kmer_hash_kernel (one lane per syncmer) instead of by a lone lane inside this kernel.
 #pragma once
@@ -58,6 +59,7 @@ static inline int syncmer_fast_ring(int K, int S)
 #define OATK_DPP_ROW_SHR(n) (0x110 + (n))
 #define OATK_DPP_ROW_BCAST15 0x142
 #define OATK_DPP_ROW_BCAST31 0x143
+#define OATK_ICMP_ULE 37                  // llvm::CmpInst::ICMP_ULE, for __builtin_amdgcn_uicmp
 
 template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ uint32_t dpp_u32(uint32_t old, uint32_t src)
@@ -70,7 +72,8 @@ __device__ __forceinline__ uint32_t dpp_u32(uint32_t old, uint32_t src)
 // v_cndmask each: fourteen instructions per direction.)
 __device__ __forceinline__ uint32_t wave_prefix_min_u32(uint32_t v)
 {
-    uint32_t p = v, t;                // (old = the identity of min: the compiler folds shift and minimum into one v_min_u32_dpp)
+    uint32_t p = v, t;                // (old = the identity of min: the compiler folds shift and minimum into one v_min_u32_dpp -- where both stand in one basic block, see
+                                      //  the ring stores in the kernel.  With old = p, as wave_incl_max_dpp has it, no step of this unsigned minimum is folded: r21)
     t = dpp_u32<OATK_DPP_ROW_SHR(1)>(0xFFFFFFFFu, p); p = t < p? t : p;
     t = dpp_u32<OATK_DPP_ROW_SHR(2)>(0xFFFFFFFFu, p); p = t < p? t : p;
     t = dpp_u32<OATK_DPP_ROW_SHR(4)>(0xFFFFFFFFu, p); p = t < p? t : p;
@@ -146,6 +149,7 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
     struct __attribute__((packed, aligned(4))) Words3 { uint32_t a, b, c; };
     const uint32_t bsel = (tid & 1u)? 0x06070001u : 0x04050607u;    // {S0 = word k, S1 = word k + 1}: bytes of the MSB-first string from bit 16 / bit 0 on
     const uint32_t last_w = (hl - 1u) >> 4;     // (two words of slack lie behind every read's string)
+    const uint32_t lane_w4 = (uint32_t) ((((int32_t) (tid * C) - 32) >> 4) * 4);    // byte offset of the lane's first word against the tile's (negative in the first four lanes)
     uint32_t rw0, rw1, rw2;                     // this tile's raw words: bases (i0 - 32) & ~15 ...
     {
         const int32_t wi0 = ((int32_t) (tid * C) - 32) >> 4;         // negative for the first four lanes: those bases lie before the read
@@ -203,7 +207,7 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
     // order, so an entry's index is its ordinal.  Records are written when the read is done: one slot atomic per read instead of
     // one per wave and tile, and the k-mer codes are computed by 256 lanes at once instead of by lone lanes between two barriers.
     uint32_t pend_kinds = 0, pend_rank = 0, pend_wtot = 0, pend_par = 0, pend_any = 0;
-    int32_t pend_i0 = 0;
+    uint32_t pend_I0 = 0;                       // the pending tile's first position (scalar; the lane's own is worked out where a syncmer is written)
     auto flush = [&]() __attribute__((always_inline)) {      // call after a barrier that follows the tile
         if (!pend_any) return;
         uint32_t before = 0, tot = 0;
@@ -217,6 +221,7 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
             if (tid == 0) s_gb = atomicAdd(&a.shard_cnt[blockIdx.x & (OATK_REC_SHARDS - 1)], tot);
             __syncthreads();
             uint32_t rank = before + pend_rank, kk = pend_kinds;
+            const int32_t pend_i0 = (int32_t) (pend_I0 + tid * C);
             while (kk) {
                 const int o = __builtin_ctz(kk) >> 1;
                 const uint32_t kind = (pend_kinds >> (2 * o)) & 3u;
@@ -227,6 +232,7 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
             __syncthreads();
         } else if (pend_wtot) {
             uint32_t idx = sl_n + before + pend_rank, kk = pend_kinds;
+            const int32_t pend_i0 = (int32_t) (pend_I0 + tid * C);
             while (kk) {
                 const int o = __builtin_ctz(kk) >> 1;
                 sl_e[idx] = (uint32_t) (pend_i0 + o) | ((pend_kinds >> (2 * o)) & 3u) << 30;
@@ -241,23 +247,31 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
     };
 
     // Ring addresses.  A tile advances every lane by T positions = HALF the ring (and half the chunk ring), so each address a lane
-    // uses alternates between two values: a chunk-ring byte offset flips one bit, a top-word index is mirrored in the sum of its two
-    // values (the pad words make it more than a bit flip).  Twelve registers updated by one instruction each per tile instead of
+    // uses alternates between two values: a chunk-ring byte offset flips one bit, a top-word byte offset is mirrored in the sum of its two
+    // values (the pad words make it more than a bit flip).  Ten registers updated by one instruction each per tile instead of
     // ~40 instructions of shifts, masks and adds; which ranges hold a whole block in their middle does not change at all.
     static_assert(2 * T == R, "the address toggling below needs tile = half the ring");
-    struct RangeAddr { uint32_t lo, hi, mid; bool whole; };
+    // (mid: the last chunk of the whole block between lo's block and hi's; a range without one reads pre32[hi] a second time -- a value that is in the minimum
+    //  already, so no lane selects anything, and all three addresses toggle alike.  Until r21 a `whole` flag per range chose between the word and MAX: a
+    //  v_cndmask per range and tile, and three lane masks held across the loop.)
+    struct RangeAddr { uint32_t lo, hi, mid; };
     auto range_addr = [&](int32_t lo, int32_t hi) -> RangeAddr {
-        return RangeAddr{rch(lo) * 4u, rch(hi) * 4u, rch(((lo >> 6) + 1) * 64 + 63) * 4u, (hi >> 6) - (lo >> 6) == 2};
+        const bool whole = (hi >> 6) - (lo >> 6) == 2;
+        return RangeAddr{rch(lo) * 4u, rch(hi) * 4u, rch(whole? ((lo >> 6) + 1) * 64 + 63 : hi) * 4u};
     };
     const int32_t ch_0 = (int32_t) tid, ca0_0 = ((int32_t) (tid * C) - w) >> 3;       // tile 0: the lane's chunk, the chunk of its first window start
-    RangeAddr rB = range_addr(ch_0 - D, ch_0 - 1), rF0 = range_addr(ca0_0 + 1, ca0_0 + D), rF1 = range_addr(ca0_0 + 2, ca0_0 + 1 + D);
+    // The Close range [ch - D, ch - 1] IS one of the two Open ranges: with w = 8 q + r (D = q - 1) the first window of the lane's chunk starts in chunk
+    // ca0 = ch - q - (r? 1 : 0), so [ca0 + 2, ca0 + 1 + D] = [ch - q + 1, ch - 1] when r > 0 and [ca0 + 1, ca0 + D] is that range when r = 0.  (Until r21 it had three
+    // addresses, three reads and a minimum of its own per tile.)
+    RangeAddr rF0 = range_addr(ca0_0 + 1, ca0_0 + D), rF1 = range_addr(ca0_0 + 2, ca0_0 + 1 + D);
     uint32_t o_cs = rch(ch_0) * 4u;
-    uint32_t m_own = mi((int32_t) (tid * C)), m_fa = mi(ca0_0 * C), m_fb = mi((ca0_0 + 1) * C);      // (indices of 8-aligned positions)
-    const uint32_t m_own_sum = m_own + mi((int32_t) (tid * C) + T), m_fa_sum = m_fa + mi(ca0_0 * C + T), m_fb_sum = m_fb + mi((ca0_0 + 1) * C + T);
+    // (BYTE offsets of 8-aligned positions: as word indices each cost a shift per tile where it was used)
+    uint32_t m_own = mi((int32_t) (tid * C)) * 4u, m_fa = mi(ca0_0 * C) * 4u, m_fb = mi((ca0_0 + 1) * C) * 4u;
+    const uint32_t m_own_sum = m_own + mi((int32_t) (tid * C) + T) * 4u, m_fa_sum = m_fa + mi(ca0_0 * C + T) * 4u, m_fb_sum = m_fb + mi((ca0_0 + 1) * C + T) * 4u;
     auto next_tile_addr = [&]() __attribute__((always_inline)) {
         constexpr uint32_t FLIP = (uint32_t) (NCH / 2) * 4u;
         o_cs ^= FLIP;
-        rB.lo ^= FLIP, rB.hi ^= FLIP, rB.mid ^= FLIP, rF0.lo ^= FLIP, rF0.hi ^= FLIP, rF0.mid ^= FLIP, rF1.lo ^= FLIP, rF1.hi ^= FLIP, rF1.mid ^= FLIP;
+        rF0.lo ^= FLIP, rF0.hi ^= FLIP, rF0.mid ^= FLIP, rF1.lo ^= FLIP, rF1.hi ^= FLIP, rF1.mid ^= FLIP;
         m_own = m_own_sum - m_own, m_fa = m_fa_sum - m_fa, m_fb = m_fb_sum - m_fb;
     };
     auto ld32 = [](const uint32_t *base, uint32_t byte_off) -> uint32_t { return *(const uint32_t *) ((const char *) base + byte_off); };
@@ -267,7 +281,10 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
     // therefore switched on by the ties themselves: a wave that meets a tie says so in LDS; one barrier later every thread knows and the hashing
     // of the tile after keeps the minima -- until two tiles have passed without a tie.  What a tying wave needs from tiles hashed without them
     // (the first two tiles of a repeat, and one window's reach behind) it computes itself from the packed bases, wave-wide (fill_c_min below).
-    bool rep_mode = false, rep_next = false;
+    // (all of it on scalars: the flag is read through v_readfirstlane, and rep_mode / rep_next are 0 / 1 words.  As bools tested through
+    //  `readfirstlane((int) rep_mode)` they were lane masks that the compiler turned into vector 0 / 1 and read back: three v_cndmask and three
+    //  v_readfirstlane at the head of every tile -- r21.)
+    uint32_t rep_mode = 0, rep_next = 0;
     int32_t rep_start = 0x7FFFFFFF;             // first chunk hashed in repeat mode (valid while rep_mode)
     uint32_t quiet = 0, tpar = 0;
     const int32_t wave_first = __builtin_amdgcn_readfirstlane((int) (wid * OATK_WAVE * C));
@@ -290,8 +307,9 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
             {   // the next tile's words, while this one is hashed (same lanes, 2048 positions on: 128 words).  Unconditional -- a load whose
                 // result is selected under a condition is waited for on the spot --, with the word index held inside the read: lanes (and a
                 // whole last tile) behind the read's end fetch its last words, which nobody looks at
-                const uint32_t wn = ((I0 + T + tid * C) - 32u) >> 4;
-                const Words3 nx = *(const Words3 *) (ghs + (wn < last_w? wn : last_w));
+                // (as a byte offset: a tile start is a multiple of sixteen positions, so the lane's part of the word index never changes -- an add and a minimum)
+                const uint32_t wn4 = (I0 + T) / 4u + lane_w4;
+                const Words3 nx = *(const Words3 *) ((const char *) ghs + (wn4 < last_w * 4u? wn4 : last_w * 4u));
                 rw0 = nx.a, rw1 = nx.b, rw2 = nx.c;
             }
             uint64_t cm = UINT64_MAX;                   // the chunk minimum in full (repeat mode only)
@@ -309,8 +327,10 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
                     // v_alignbit_b32 per strand and position, against the six + four instructions of rolling both 62-bit values along (r04: both forms
                     // cost the same per instruction class, profiles/r04a_valu_rates.txt, so the count decides).
                     auto rc16 = [](uint32_t x) -> uint32_t {
+                        // (the select between the two shifts and the complement are ONE three-input function: truth table 0x1b with a = 0xf0, b = 0xcc, c = 0xaa.
+                        //  Written as ~(((r >> 1) & m) | ((r & m) << 1)) the compiler masks one side with a v_and of its own first -- r21)
                         const uint32_t r = __builtin_bitreverse32(x);
-                        return ~(((r >> 1) & 0x55555555u) | ((r & 0x55555555u) << 1));
+                        return (uint32_t) __builtin_amdgcn_bitop3_b32((int) (r >> 1), (int) (r << 1), 0x55555555, 0x1b);      // ~(c? a : b)
                     };
                     const uint32_t r0 = rc16(a_hi), r1 = rc16(a_lo), r2 = rc16(vbh);
                     auto hash_chunk = [&](auto keep, auto ends) __attribute__((always_inline)) {
@@ -336,9 +356,9 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
                     };
                     // (two copies of the loop, chosen by a scalar branch: as one loop with a per-position select the compiler keeps the 64-bit chain for every position)
                     if (inside) {
-                        if (__builtin_amdgcn_readfirstlane((int) rep_mode)) hash_chunk(std::true_type(), std::false_type()); else hash_chunk(std::false_type(), std::false_type());
+                        if (rep_mode) hash_chunk(std::true_type(), std::false_type()); else hash_chunk(std::false_type(), std::false_type());
                     } else {
-                        if (__builtin_amdgcn_readfirstlane((int) rep_mode)) hash_chunk(std::true_type(), std::true_type()); else hash_chunk(std::false_type(), std::true_type());
+                        if (rep_mode) hash_chunk(std::true_type(), std::true_type()); else hash_chunk(std::false_type(), std::true_type());
                     }
                 } else {
                     const uint64_t X = ((uint64_t) a_hi << 32 | a_lo) << (2 * (32 - S));       // the S bases that end at i0 - 1, at the top
@@ -387,13 +407,13 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
             // still read that tile's windows from the ring.  Ring slots are only overwritten behind this barrier.
             __syncthreads();
             static_assert(C == 8, "two 16-byte stores per lane");
-            *(uint4 *) (m_top + m_own) = make_uint4(y[0], y[1], y[2], y[3]);
-            *(uint4 *) (m_top + m_own + 4) = make_uint4(y[4], y[5], y[6], y[7]);
-            if (rep_mode) *(uint64_t *) ((char *) c_min + 2u * o_cs) = cm;
+            *(uint4 *) ((char *) m_top + m_own) = make_uint4(y[0], y[1], y[2], y[3]);
+            *(uint4 *) ((char *) m_top + m_own + 16) = make_uint4(y[4], y[5], y[6], y[7]);
             {   // what the tile before saw (its flags are behind a barrier now) decides how the tile AFTER this one is hashed
-                const uint32_t seen = s_tie[tpar ^ 1u];
-                quiet = seen? 0u : quiet + 1u;
-                rep_next = seen != 0u || (rep_mode && quiet < 2u);
+                const uint32_t seen = (uint32_t) __builtin_amdgcn_readfirstlane((int) s_tie[tpar ^ 1u]);
+                // (the flag is 0 or 1 and quiet counts tiles, far below 2^31; arithmetic on words, no compare whose result would have to cross a block as a lane mask)
+                quiet = (quiet + 1u) & (seen - 1u);                          // seen? 0 : quiet + 1
+                rep_next = seen | (rep_mode & ((quiet - 2u) >> 31));          // seen || (rep_mode && quiet < 2)
             }
             *(uint32_t *) ((char *) pre32 + o_cs) = pre;
 #ifdef OATK_SCAN_SHFL
@@ -401,6 +421,9 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
 #else
             *(uint32_t *) ((char *) suf32 + (o_cs ^ 252u)) = suf;        // lane l holds the suffix minimum of the chunk of lane 63 - l
 #endif
+            // (behind the prefix / suffix stores: in front of them this branch ended the basic block of the two scans, their last minimum sank below it, and its
+            //  row_bcast:31 shift was left a v_mov -1 and a v_mov_dpp of its own -- three instructions for one, in either direction.  r21)
+            if (rep_mode) *(uint64_t *) ((char *) c_min + 2u * o_cs) = cm;
         }
         __syncthreads();
         if (tid == 0) s_tie[tpar ^ 1u] = 0;             // (read above by everybody, written next by the tile after this one, two barriers on)
@@ -421,32 +444,28 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
         //  fetching the ragged ends of one window: 11.5 % of the kernel's time for two positions in a thousand, profiles/r03i_b_phase_experiments.txt.)
         static_assert(SH >= 0 && SH < C, "the window's alignment against the chunks is a template argument");
         constexpr int RR = (C - SH) & (C - 1);          // r = w mod 8
-        uint32_t backF_keep = 0, fwd0_keep = 0, fwd1_keep = 0;
         uint32_t kinds = 0;                             // 2 bits per position of the chunk: 0 none, 1 Close, 2 Open
         uint32_t tiemask = 0;
         // (not in a wave where no k-mer ends -- E + 1 <= wb + 512 < K for every position E of it: the first wave of a read, the first two on the 4096-slot
         //  ring.  The edge form below found `fits` false at all eight positions there, after the loads and the filter: nothing decided, nothing tied.  r16)
+        // minimum of the chunk minima over chunks [lo, hi], hi - lo = D - 1: suffix of lo's block, prefix of hi's block and,
+        // when the two are not adjacent, the one whole block between them (otherwise hi's prefix again).  Chunks before the read map to
+        // ring slots that still hold the initial MAX, which is exactly "no constraint".
+        auto range_min = [&](const RangeAddr &ra) -> uint32_t {
+            const uint32_t a0 = ld32(suf32, ra.lo), a1 = ld32(pre32, ra.hi), a2 = ld32(pre32, ra.mid);
+            const uint32_t v = a0 < a1? a0 : a1;
+            return a2 < v? a2 : v;
+        };
         if (!(wb + OATK_WAVE * C < K)) {
-            // minimum of the chunk minima over chunks [lo, hi], hi - lo = D - 1: suffix of lo's block, prefix of hi's block and,
-            // when the two are not adjacent, the one whole block between them.  Chunks before the read map to ring slots that
-            // still hold the initial MAX, which is exactly "no constraint".
-            auto range_min = [&](const RangeAddr &ra) -> uint32_t {
-                const uint32_t a0 = ld32(suf32, ra.lo), a1 = ld32(pre32, ra.hi);
-                const uint32_t mid = ld32(pre32, ra.mid);
-                const uint32_t a2 = ra.whole? mid : 0xFFFFFFFFu;
-                const uint32_t v = a0 < a1? a0 : a1;
-                return a2 < v? a2 : v;
-            };
-            const uint32_t backF = range_min(rB);            // Close bound: chunks [ch - D, ch - 1]
             const uint32_t fwd0 = range_min(rF0);            // Open bound, first s-mers ending in chunk ca0: chunks [ca0 + 1, ca0 + D]
             const uint32_t fwd1 = range_min(rF1);            // ... and in chunk ca0 + 1: chunks [ca0 + 2, ca0 + 1 + D]
-            backF_keep = backF, fwd0_keep = fwd0, fwd1_keep = fwd1;
+            const uint32_t backF = RR? fwd1 : fwd0;          // Close bound: chunks [ch - D, ch - 1], the same range as one of the two (see the ring addresses)
             // W[j] = top word of position lo(o = 0) + j: chunk ca0 from offset SH on (j < BD), then chunk ca0 + 1
             constexpr int BD = RR? RR : C;              // index of the first position of the second chunk
             uint32_t W[2 * C];
             {
-                const uint4 a0 = *(const uint4 *) (m_top + m_fa), a1 = *(const uint4 *) (m_top + m_fa + 4);
-                const uint4 b0 = *(const uint4 *) (m_top + m_fb), b1 = *(const uint4 *) (m_top + m_fb + 4);
+                const uint4 a0 = *(const uint4 *) ((const char *) m_top + m_fa), a1 = *(const uint4 *) ((const char *) m_top + m_fa + 16);
+                const uint4 b0 = *(const uint4 *) ((const char *) m_top + m_fb), b1 = *(const uint4 *) ((const char *) m_top + m_fb + 16);
                 const uint32_t all[2 * C] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
                 for (int j = 0; j < 2 * C - SH; ++j) W[j] = all[SH + j];
@@ -454,9 +473,8 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
             // the minimum of the chunk before the lane's own (Open with o < r): the neighbour lane's, or for lane 0 the last chunk of the wave before
             uint32_t cprev = 0xFFFFFFFFu;
             if (RR > 0) {
-                const uint32_t nb = dpp_u32<0x138>(0xFFFFFFFFu, cmin_keep);                   // wave_shr:1
                 const uint32_t lb = ld32(suf32, (o_cs - 4u) & (uint32_t) (NCH * 4 - 1));         // (the suffix minimum of a block's last chunk is that chunk's own)
-                cprev = lane == 0? lb : nb;
+                cprev = dpp_u32<0x138>(lb, cmin_keep);       // wave_shr:1 with old = lb: lane 0 has no source lane and keeps lb -- one v_mov_dpp, no select
             }
             // per position: a cheap necessary condition -- a minimum and two compares whose results are LANE MASKS in scalar registers, or'ed and tested there --
             // and the rule itself only where some lane of the wave passes it: about one position per wave and tile on random sequence.
@@ -469,8 +487,9 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
                     const uint32_t yhi = y[o], fhi = W[o];
                     const uint32_t fb = o + SH < C? fwd0 : fwd1;
                     const uint32_t fy = fb < yhi? fb : yhi;
-                    const bool c1 = yhi <= backF, c2 = fhi <= fy;
-                    uint64_t cand = __ballot(c1) | __ballot(c2);
+                    // (the compares as the intrinsic that returns the lane mask: as `__ballot(bool)` the two of position 0, which both copies of this loop
+                    //  share, were hoisted above the branch that chooses the copy and came back as v_cndmask 0 / 1 + v_cmp_ne each -- r04's pathology, r21)
+                    uint64_t cand = __builtin_amdgcn_uicmp(yhi, backF, OATK_ICMP_ULE) | __builtin_amdgcn_uicmp(fhi, fy, OATK_ICMP_ULE);
                     bool fits = true;
                     if (decltype(at_edge)::value) {
                         fits = (uint32_t) (i0 + o) < hl && i0 + o + 1 >= K;
@@ -480,7 +499,7 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
                     if (!a.want_n) cand = 0;                // (timing experiment: nothing survives the filter)
 #endif
                     if (cand) {
-                        const bool c = (c1 | c2) && fits;
+                        const bool c = (yhi <= backF || fhi <= fy) && fits;
                         uint32_t pmin = 0xFFFFFFFFu;        // the lane's own positions before E
 #pragma unroll
                         for (int j = 0; j < o; ++j) pmin = y[j] < pmin? y[j] : pmin;
@@ -517,6 +536,11 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
         // position in p); and the whole chunks of a window come from the 64-bit chunk minima the hashing phase leaves in `c_min`.
         if (__ballot(tiemask != 0)) {
             constexpr int sh = SH;
+            // (what only this path needs is worked out here, not carried through every tile: the three bounds are read again -- the prefix / suffix rings do not
+            //  change before the next tile's barrier --, and the lane's first position is taken from a tile start the loop optimiser cannot see through, or it keeps
+            //  i0 - w, i0 - w + 2 and 2 i0 - 60 as induction registers of their own, a v_add each per tile.  r21)
+            const int32_t i0 = (int32_t) ((uint32_t) __builtin_amdgcn_readfirstlane((int) I0) + tid * C);
+            const uint32_t fwd0_keep = range_min(rF0), fwd1_keep = range_min(rF1), backF_keep = RR? fwd1_keep : fwd0_keep;
             {   // the 64-bit minima of the chunks this wave's windows cover, where the hashing phase did not keep them (see "repeat mode" above): the wave
                 // computes them from the packed bases, a chunk per lane and turn, and leaves them in the ring (another wave with ties may write the same
                 // values to the same slots).  The windows of the wave's 64 chunks reach from chunk ca0(lane 0) + 1 to ca0(lane 63) + 1 + D: fewer than the ring holds.
@@ -590,7 +614,7 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
         const uint32_t incl = wave_incl_sum_dpp(ns, lane);
         const uint32_t wtot = (uint32_t) __builtin_amdgcn_readlane((int) incl, 63);
         if (lane == 0) w_cnt[par][wid] = wtot;
-        pend_kinds = kinds, pend_rank = incl - ns, pend_i0 = i0, pend_wtot = wtot, pend_par = par, pend_any = 1u;
+        pend_kinds = kinds, pend_rank = incl - ns, pend_I0 = I0, pend_wtot = wtot, pend_par = par, pend_any = 1u;
         par ^= 1u;
     }
     if (I0 < hl) {
