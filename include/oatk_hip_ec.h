@@ -57,9 +57,9 @@ int oatk_hip_debug_wf_ed(oatk_hip_ctx *ctx, uint64_t n_jobs, const uint8_t *t_co
 int oatk_hip_debug_wf_ed_turns(oatk_hip_ctx *ctx, int regroup, uint64_t n_jobs, const uint8_t *t_codes, const uint64_t *t_off, const uint8_t *q_codes, const uint64_t *q_off,
                                const int32_t *bw, const int32_t *step_ql, const uint64_t *step_off, int32_t *out3, uint32_t *turns);
 /* The refreshed table's coverage on its own (update_syncmer_db, syncerr.c:769-814): from n (key, occurrence) pairs sorted by key -- key_sorted[i] < nv ascending, bit 0 of
- * occ[i] the strand, 0 = forward -- cov[k] = entries of key k, fwd[k] = forward ones among them, del[k] = !fwd[k], for k < nv.  runs != 0: in one pass over the runs
- * (ec.hpp: ec_cov_runs_kernel, what ships); runs = 0: by flags, their prefix sums and a search per run end (OATK_DEBUG_EC_REFRESH_RUNS=0).  Host pointers. */
-int oatk_hip_debug_cov_runs(oatk_hip_ctx *ctx, int runs, uint64_t n, const uint32_t *key_sorted, const uint64_t *occ, uint64_t nv, uint32_t *cov, uint32_t *fwd, uint8_t *del);
+ * occ[i] the strand, 0 = forward -- cov[k] = entries of key k, fwd[k] = forward ones among them, del[k] = !fwd[k], for k < nv, in one pass over the runs
+ * (ec.hpp: ec_cov_runs_kernel).  Host pointers. */
+int oatk_hip_debug_cov_runs(oatk_hip_ctx *ctx, uint64_t n, const uint32_t *key_sorted, const uint64_t *occ, uint64_t nv, uint32_t *cov, uint32_t *fwd, uint8_t *del);
 /* The same jobs through the step of the workgroup solver (round 5: the blocks that are not small, one workgroup per block with the wavefront in
  * registers, R = 1, 2 or 6 diagonals per lane; R = 16: the second stage's step, sixteen waves and four steps per barrier, 2 bw + 3 <= 896).  A job needs 2 bw + 3
  * (no band: tl + ql + 3) <= 256 R diagonals; otherwise OATK_E_ARG. */

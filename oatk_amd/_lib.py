@@ -229,7 +229,7 @@ def load():
     if hasattr(L, "oatk_hip_debug_wf_ed_turns"):   # (a library built before r20 lacks it)
         L.oatk_hip_debug_wf_ed_turns.argtypes = [vp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "oatk_hip_debug_cov_runs"):
-        L.oatk_hip_debug_cov_runs.argtypes = [vp, C.c_int, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp]
+        L.oatk_hip_debug_cov_runs.argtypes = [vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp]
     if hasattr(L, "oatk_hip_debug_wf_ed_wg"):      # (an experiments library built before round 5 lacks it)
         L.oatk_hip_debug_wf_ed_wg.argtypes = [vp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "oatk_hip_debug_ed_ab"):      # tools/experiments/liboatk_hip_experiments.so only

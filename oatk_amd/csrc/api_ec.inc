@@ -245,7 +245,7 @@ extern "C" int oatk_hip_debug_wf_ed_turns(oatk_hip_ctx *ctx, int regroup, uint64
 }
 
 // the refreshed table's coverage, forward counts and marks from sorted (key, occurrence) pairs on their own (include/oatk_hip_ec.h)
-extern "C" int oatk_hip_debug_cov_runs(oatk_hip_ctx *ctx, int runs, uint64_t n, const uint32_t *key_sorted, const uint64_t *occ, uint64_t nv, uint32_t *cov, uint32_t *fwd, uint8_t *del)
+extern "C" int oatk_hip_debug_cov_runs(oatk_hip_ctx *ctx, uint64_t n, const uint32_t *key_sorted, const uint64_t *occ, uint64_t nv, uint32_t *cov, uint32_t *fwd, uint8_t *del)
 {
     using namespace oatk;
     if (!ctx) return OATK_E_NODEV;
@@ -253,18 +253,13 @@ extern "C" int oatk_hip_debug_cov_runs(oatk_hip_ctx *ctx, int runs, uint64_t n, 
     for (uint64_t i = 0; i < n; ++i)
         if (key_sorted[i] >= nv || (i && key_sorted[i] < key_sorted[i - 1])) { ctx->err = "oatk_hip_debug_cov_runs: keys must ascend and lie below nv"; return OATK_E_ARG; }
     CK(hipSetDevice(ctx->device));
-    DevBuf d_key, d_occ, d_flag, d_cov, d_fwd, d_del;
-    if (!d_key.ensure(n * 4 + 16, ctx->stream) || !d_occ.ensure(n * 8 + 16, ctx->stream) || !d_flag.ensure(n * 4 + 16, ctx->stream) || !d_cov.ensure(nv * 4 + 16, ctx->stream) ||
+    DevBuf d_key, d_occ, d_cov, d_fwd, d_del;
+    if (!d_key.ensure(n * 4 + 16, ctx->stream) || !d_occ.ensure(n * 8 + 16, ctx->stream) || !d_cov.ensure(nv * 4 + 16, ctx->stream) ||
         !d_fwd.ensure(nv * 4 + 16, ctx->stream) || !d_del.ensure(nv + 16, ctx->stream)) { ctx->err = "oatk_hip_debug_cov_runs: hipMalloc failed"; return OATK_E_NOMEM; }
     if (n) { CK(hipMemcpyAsync(d_key.p, key_sorted, n * 4, hipMemcpyHostToDevice, ctx->stream)); CK(hipMemcpyAsync(d_occ.p, occ, n * 8, hipMemcpyHostToDevice, ctx->stream)); }
     CK(hipMemsetAsync(d_cov.p, 0, nv * 4, ctx->stream));
     CK(hipMemsetAsync(d_fwd.p, 0, nv * 4, ctx->stream));
-    if (n && runs) hipLaunchKernelGGL(ec_cov_runs_kernel, grid256(n), dim3(256), 0, ctx->stream, n, d_key.as<uint32_t>(), d_occ.as<uint64_t>(), d_cov.as<uint32_t>(), d_fwd.as<uint32_t>());
-    else if (n) {
-        hipLaunchKernelGGL(ec_fwd_flag_kernel, grid256(n), dim3(256), 0, ctx->stream, n, d_occ.as<uint64_t>(), d_flag.as<uint32_t>());
-        PRIM(rocprim::inclusive_scan, d_flag.as<uint32_t>(), d_flag.as<uint32_t>(), n, rocprim::plus<uint32_t>(), ctx->stream);
-        hipLaunchKernelGGL(ec_cov_sorted_kernel, grid256(n), dim3(256), 0, ctx->stream, n, d_key.as<uint32_t>(), d_flag.as<uint32_t>(), d_cov.as<uint32_t>(), d_fwd.as<uint32_t>());
-    }
+    if (n) hipLaunchKernelGGL(ec_cov_runs_kernel, grid256(n), dim3(256), 0, ctx->stream, n, d_key.as<uint32_t>(), d_occ.as<uint64_t>(), d_cov.as<uint32_t>(), d_fwd.as<uint32_t>());
     hipLaunchKernelGGL(ec_del_kernel, grid256(nv), dim3(256), 0, ctx->stream, nv, d_fwd.as<uint32_t>(), d_del.as<uint8_t>());
     CK(hipMemcpyAsync(cov, d_cov.p, nv * 4, hipMemcpyDeviceToHost, ctx->stream));
     CK(hipMemcpyAsync(fwd, d_fwd.p, nv * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -714,20 +709,14 @@ struct EcKnobs {
     int32_t heavy_cap2 = 0;       // OATK_DEBUG_EC_HEAVY_CAP2: longest block of the second class (tests: blocks the cases would not send there)
     int32_t heavy_fl = 0;         // OATK_DEBUG_EC_HEAVY_FL: bytes of the classes' LDS frame arena (tests: 64 sends every frame to HBM)
     int32_t waves = 32;           // OATK_DEBUG_EC_WAVES: first-tier waves per CU (tools/solverbench.py)
-    bool assemble_walk = false;   // OATK_DEBUG_EC_ASSEMBLE_WALK=1: the corrected chains by a third walk (ec_new_n_kernel, ec_assemble_wave_kernel<1>) instead of from the blocks' descriptors (A/B, tests)
     int memo = 2;                 // OATK_DEBUG_EC_MEMO=0: every level of every block gathers its k-mer again (ec_wave.hpp: EcwMemo); =1: levels are reused, no block starts at its
                                   // sink; unset: both (A/B, tests)
     bool queue_sort = true;       // OATK_DEBUG_EC_QUEUE_SORT=0: the wave solver's queues in read order (A/B, tests)
-    bool list_walk = false;       // OATK_DEBUG_EC_LIST_WALK=1: the blocks listed by a second walk behind the scan (ec_count_blocks_wave_kernel, ec_list_blocks_wave_kernel) instead of from the
-                                  // descriptors the one walk stages (ec_stage_blocks_wave_kernel, ec_fill_work_kernel) (A/B, tests)
     bool light_packed = true;     // OATK_DEBUG_EC_LIGHT_PACKED=0: the light graph's pairs sorted as 64-bit keys on vertex ids (ec_light_pairs), not on candidate ranks (A/B, tests)
-    bool light_pairs = true;      // OATK_DEBUG_EC_LIGHT_PAIRS=0: in front of the sort on ranks, the pairs by a wave per read, a scan and a compaction instead of a lane per entry (A/B, tests)
     bool regroup = true;          // OATK_DEBUG_EC_REGROUP=0: the wave solver's alignment keeps its lanes on the diagonals they started a step on (ec_wave.hpp: ecw_step) (A/B, tests)
     int32_t batch = ECW_BATCH;    // OATK_DEBUG_EC_BATCH: blocks a first-tier wave takes from its queue at a time, 1 .. 64 (A/B, tests)
     bool assemble_pairs = true;   // OATK_DEBUG_EC_ASSEMBLE_PAIRS=0: the corrected chains by a wave per read (ec_assemble_seg_kernel) instead of two reads to a wave where both have at most 32
                                   // chain entries and blocks (ec_assemble_pair_kernel) (A/B, tests)
-    bool refresh_runs = true;     // OATK_DEBUG_EC_REFRESH_RUNS=0: coverage and forward counts of the refreshed table from flags, their prefix sums and a search per run end
-                                  // (ec_fwd_flag_kernel, a scan, ec_cov_sorted_kernel) instead of one pass over the sorted runs (ec_cov_runs_kernel) (A/B, tests)
     bool light_wide = false;      // OATK_DEBUG_EC_LIGHT_KEYBITS=64: packed keys of 64 bits whatever the number of candidates (tests: the form large candidate sets take)
 };
 static EcKnobs ec_knobs_read()
@@ -741,25 +730,20 @@ static EcKnobs ec_knobs_read()
     k.min_nw = num("OATK_DEBUG_EC_FUSED_MIN_NW", 2, 0);
     k.heavy_cap2 = num("OATK_DEBUG_EC_HEAVY_CAP2", 1, 0), k.heavy_fl = num("OATK_DEBUG_EC_HEAVY_FL", 64, 0) & ~7;
     k.waves = num("OATK_DEBUG_EC_WAVES", 1, 32);
-    { const char *e = getenv("OATK_DEBUG_EC_ASSEMBLE_WALK"); k.assemble_walk = e && e[0] == '1'; }
-    { const char *e = getenv("OATK_DEBUG_EC_LIST_WALK"); k.list_walk = e && e[0] == '1'; }
     { const char *e = getenv("OATK_DEBUG_EC_MEMO"); k.memo = e && (e[0] == '0' || e[0] == '1') && !e[1]? e[0] - '0' : 2; }
     { const char *e = getenv("OATK_DEBUG_EC_QUEUE_SORT"); k.queue_sort = !(e && e[0] == '0' && !e[1]); }
     { const char *e = getenv("OATK_DEBUG_EC_LIGHT_PACKED"); k.light_packed = !(e && e[0] == '0' && !e[1]); }
-    { const char *e = getenv("OATK_DEBUG_EC_LIGHT_PAIRS"); k.light_pairs = !(e && e[0] == '0' && !e[1]); }
     { const char *e = getenv("OATK_DEBUG_EC_REGROUP"); k.regroup = !(e && e[0] == '0' && !e[1]); }
     k.batch = num("OATK_DEBUG_EC_BATCH", 1, ECW_BATCH);
     if (k.batch > 64) k.batch = 64;                    // (lane i holds block i of a batch)
     { const char *e = getenv("OATK_DEBUG_EC_ASSEMBLE_PAIRS"); k.assemble_pairs = !(e && e[0] == '0' && !e[1]); }
-    { const char *e = getenv("OATK_DEBUG_EC_REFRESH_RUNS"); k.refresh_runs = !(e && e[0] == '0' && !e[1]); }
     { const char *e = getenv("OATK_DEBUG_EC_LIGHT_KEYBITS"); k.light_wide = e && !strcmp(e, "64"); }
     return k;
 }
 
 // The light graph of a handle in local ids, on candidate ranks (ecgraph.hpp): the rank table, the kept pairs with packed keys -- by a lane per chain entry in
-// two passes, or (pairs_old) by the three kernels of ec_light_pairs with the packing in the compaction -- and ec_graph_build's entry for packed keys.
-// One wait on the host brings the number of candidates and of kept pairs; pairs_old has a second one, because its compaction needs the key width first.
-static int ec_light_packed(oatk_hip_ctx *ctx, uint32_t c, bool pairs_old, bool force_wide)
+// two passes -- and ec_graph_build's entry for packed keys.  One wait on the host brings the number of candidates and of kept pairs.
+static int ec_light_packed(oatk_hip_ctx *ctx, uint32_t c, bool force_wide)
 {
     using namespace oatk;
     EcState *e = ctx->ec;
@@ -771,9 +755,7 @@ static int ec_light_packed(oatk_hip_ctx *ctx, uint32_t c, bool pairs_old, bool f
     t_begin(ctx, OATK_T_EC_GRAPH);
     CK(hipMemsetAsync(e->g_other.p, 0, 2 * nv + 8, ctx->stream));
     uint32_t n_cand = 0, nk32 = 0;
-    uint64_t nk = 0;
     EgrPacked pk = {nullptr, 1, force_wide, nullptr};
-    int rc;
     if (n && nv) {
         const uint64_t *bits = e->g_cbits.as<uint64_t>();
         const uint32_t *wpre = e->g_wpre.as<uint32_t>();
@@ -782,45 +764,25 @@ static int ec_light_packed(oatk_hip_ctx *ctx, uint32_t c, bool pairs_old, bool f
         hipLaunchKernelGGL(egr_cand_flag_kernel, grid256(nv), dim3(256), 0, ctx->stream, nv, nw, ctx->scm_cov.as<uint32_t>(), c, e->g_cbits.as<uint64_t>(), e->g_wcnt.as<uint32_t>());
         PRIM(rocprim::exclusive_scan, e->g_wcnt.as<const uint32_t>(), e->g_wpre.as<uint32_t>(), 0u, nw + 1, rocprim::plus<uint32_t>(), ctx->stream);
         CK(hipMemcpyAsync(&n_cand, e->g_wpre.as<uint32_t>() + nw, 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (pairs_old) {
-            EENSURE(g_keys, (n + 1) * 8); EENSURE(g_dist, (n + 1) * 4); EENSURE(g_keep, n + 8); EENSURE(g_keys2, (n + 1) * 8);
-            hipLaunchKernelGGL(egr_pair_light_wave_kernel, dim3((unsigned) ((nr + 3) / 4)), dim3(256), 0, ctx->stream, nr, scm_off, chains, mpos, ctx->scm_cov.as<uint32_t>(), c,
-                               e->g_keys.as<uint64_t>(), e->g_dist.as<uint32_t>(), e->g_keep.as<uint8_t>(), e->g_other.as<uint8_t>());
-            auto flags = rocprim::make_transform_iterator(e->g_keep.as<uint8_t>(), [] __device__(uint8_t f) -> uint32_t { return f; });
-            PRIM(rocprim::exclusive_scan, flags, e->g_keys2.as<uint32_t>(), 0u, n, rocprim::plus<uint32_t>(), ctx->stream);
-        } else {
-            hipLaunchKernelGGL((egr_pair_entry_kernel<uint32_t, false>), dim3((unsigned) nwg), dim3(256), 0, ctx->stream, nr, scm_off, chains, mpos, bits, wpre, 0u,
-                               e->g_gcnt.as<uint32_t>(), (const uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint8_t *) nullptr);
-            PRIM(rocprim::exclusive_scan, e->g_gcnt.as<const uint32_t>(), e->g_gpre.as<uint32_t>(), 0u, nwg + 1, rocprim::plus<uint32_t>(), ctx->stream);
-            CK(hipMemcpyAsync(&nk32, e->g_gpre.as<uint32_t>() + nwg, 4, hipMemcpyDeviceToHost, ctx->stream));
-        }
+        hipLaunchKernelGGL((egr_pair_entry_kernel<uint32_t, false>), dim3((unsigned) nwg), dim3(256), 0, ctx->stream, nr, scm_off, chains, mpos, bits, wpre, 0u,
+                           e->g_gcnt.as<uint32_t>(), (const uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint8_t *) nullptr);
+        PRIM(rocprim::exclusive_scan, e->g_gcnt.as<const uint32_t>(), e->g_gpre.as<uint32_t>(), 0u, nwg + 1, rocprim::plus<uint32_t>(), ctx->stream);
+        CK(hipMemcpyAsync(&nk32, e->g_gpre.as<uint32_t>() + nwg, 4, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
         // B = the bits of the largest oriented rank, 2 n_cand - 1; n_cand <= nv < 2^31 keeps a key within 64 bits, and the test stays all the same
         while ((1ULL << pk.B) < 2 * (uint64_t) n_cand) ++pk.B;
         if (2 * pk.B > 64) { ctx->err = "light EC graph: a pair of candidate ranks does not fit a 64-bit key"; return OATK_E_ARG; }
         pk.wide = force_wide || 2 * pk.B > 32;
-        const uint64_t cap = pairs_old? n : (uint64_t) nk32;
-        EENSURE(g_lkeys, (cap + 1) * (pk.wide? 8 : 4)); EENSURE(g_ldist, (cap + 1) * 4); EENSURE(g_candid, ((uint64_t) n_cand + 1) * 4);
+        EENSURE(g_lkeys, ((uint64_t) nk32 + 1) * (pk.wide? 8 : 4)); EENSURE(g_ldist, ((uint64_t) nk32 + 1) * 4); EENSURE(g_candid, ((uint64_t) n_cand + 1) * 4);
         pk.keys = e->g_lkeys.p, pk.cand_id = e->g_candid.as<uint32_t>();
         if (n_cand) hipLaunchKernelGGL(egr_cand_id_kernel, grid256(nv), dim3(256), 0, ctx->stream, nv, bits, wpre, e->g_candid.as<uint32_t>());
-        if (pairs_old) {
-            uint64_t *d_cnt = e->g_nruns.as<uint64_t>() + 2;
-            if (pk.wide) hipLaunchKernelGGL(egr_compact_pack_kernel<uint64_t>, grid256(n), dim3(256), 0, ctx->stream, n, e->g_keep.as<uint8_t>(), e->g_keys2.as<uint32_t>(), e->g_keys.as<uint64_t>(),
-                                            e->g_dist.as<uint32_t>(), bits, wpre, pk.B, e->g_lkeys.as<uint64_t>(), e->g_ldist.as<uint32_t>(), d_cnt);
-            else hipLaunchKernelGGL(egr_compact_pack_kernel<uint32_t>, grid256(n), dim3(256), 0, ctx->stream, n, e->g_keep.as<uint8_t>(), e->g_keys2.as<uint32_t>(), e->g_keys.as<uint64_t>(),
-                                    e->g_dist.as<uint32_t>(), bits, wpre, pk.B, e->g_lkeys.as<uint32_t>(), e->g_ldist.as<uint32_t>(), d_cnt);
-            CK(hipMemcpyAsync(&nk, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-        } else {
-            nk = nk32;
-            if (pk.wide) hipLaunchKernelGGL((egr_pair_entry_kernel<uint64_t, true>), dim3((unsigned) nwg), dim3(256), 0, ctx->stream, nr, scm_off, chains, mpos, bits, wpre, pk.B,
-                                            (uint32_t *) nullptr, (const uint32_t *) e->g_gpre.as<uint32_t>(), e->g_lkeys.as<uint64_t>(), e->g_ldist.as<uint32_t>(), e->g_other.as<uint8_t>());
-            else hipLaunchKernelGGL((egr_pair_entry_kernel<uint32_t, true>), dim3((unsigned) nwg), dim3(256), 0, ctx->stream, nr, scm_off, chains, mpos, bits, wpre, pk.B,
-                                    (uint32_t *) nullptr, (const uint32_t *) e->g_gpre.as<uint32_t>(), e->g_lkeys.as<uint32_t>(), e->g_ldist.as<uint32_t>(), e->g_other.as<uint8_t>());
-        }
+        if (pk.wide) hipLaunchKernelGGL((egr_pair_entry_kernel<uint64_t, true>), dim3((unsigned) nwg), dim3(256), 0, ctx->stream, nr, scm_off, chains, mpos, bits, wpre, pk.B,
+                                        (uint32_t *) nullptr, (const uint32_t *) e->g_gpre.as<uint32_t>(), e->g_lkeys.as<uint64_t>(), e->g_ldist.as<uint32_t>(), e->g_other.as<uint8_t>());
+        else hipLaunchKernelGGL((egr_pair_entry_kernel<uint32_t, true>), dim3((unsigned) nwg), dim3(256), 0, ctx->stream, nr, scm_off, chains, mpos, bits, wpre, pk.B,
+                                (uint32_t *) nullptr, (const uint32_t *) e->g_gpre.as<uint32_t>(), e->g_lkeys.as<uint32_t>(), e->g_ldist.as<uint32_t>(), e->g_other.as<uint8_t>());
         CK(hipGetLastError());
     }
-    return ec_graph_build(ctx, nullptr, e->g_ldist.as<uint32_t>(), nullptr, nk, true, &pk);
+    return ec_graph_build(ctx, nullptr, e->g_ldist.as<uint32_t>(), nullptr, nk32, true, &pk);
 }
 
 // The graph read_error_correction needs and no more (include/oatk_hip_ec.h): arcs between syncmers seen at least err_mer_c times, plus one
@@ -838,7 +800,7 @@ extern "C" int oatk_hip_ec_graph_light(oatk_hip_ctx *ctx, uint32_t err_mer_c)
     const EcKnobs kn = ec_knobs_read();
     int rc;
     if (kn.light_packed && !ctx->ec->global) {           // (a handle in global ids: the sharded round's pairs, 64-bit keys on global ids)
-        if ((rc = ec_light_packed(ctx, err_mer_c, !kn.light_pairs, kn.light_wide)) != OATK_OK) return rc;
+        if ((rc = ec_light_packed(ctx, err_mer_c, kn.light_wide)) != OATK_OK) return rc;
     } else {
         if ((rc = ec_light_pairs(ctx, err_mer_c, &k, &d, &n)) != OATK_OK) return rc;
         if ((rc = ec_graph_build(ctx, k, d, nullptr, n, true)) != OATK_OK) return rc;
@@ -1419,6 +1381,122 @@ static int ec_solve_tiers(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, cons
     return OATK_OK;
 }
 
+// ---- the phases around the solve, in the order oatk_hip_ec_correct runs them; each works on ctx->stream and leaves what the next one reads in EcState ----
+// a wave per read (ec.hpp: ECR_READS_PER_BLOCK reads to a workgroup)
+static inline dim3 ec_read_blocks(uint64_t nr) { return dim3((unsigned) ((nr + ECR_READS_PER_BLOCK - 1) / ECR_READS_PER_BLOCK > 0? (nr + ECR_READS_PER_BLOCK - 1) / ECR_READS_PER_BLOCK : 1)); }
+
+// the arcs that survive, squeezed, each with what the search needs about its target (ec.hpp: EcLiveArc); whether the live graph branches anywhere
+static int ec_live_arcs(oatk_hip_ctx *ctx, EcState *e, EcLive &lv, bool &graph_branches)
+{
+    const uint64_t nv = e->g_n_vtx, na = e->g_n_arc;
+    uint64_t n_live = 0;
+    EENSURE(g_flags, 64);
+    CK(hipMemsetAsync(e->g_flags.as<uint32_t>() + 8, 0, 12, ctx->stream));         // [8] a live vertex without its k-mer here, [9] the live graph branches, [10] a block beyond a read's staging entries
+    EENSURE(live32, (na + 1) * 4); EENSURE(lidx_p, (2 * nv + 1) * 4); EENSURE(lidx_n, (2 * nv + 1) * 4);
+    if (na) hipLaunchKernelGGL(ec_live_flag_kernel, grid256(na), dim3(256), 0, ctx->stream, na, (const uint8_t *) e->arc_del.p, e->live32.as<uint32_t>());
+    { int rc = prim_scan_total_u32(ctx, e->live32, e->live64, e->live_off, na, &n_live); if (rc) return rc; }
+    if (n_live >= 0xFFFFFFFFULL) { ctx->err = "error correction: more than 2^32 live arcs"; return OATK_E_ARG; }
+    EENSURE(larc, (n_live + 1) * sizeof(EcLiveArc));
+    e->n_live = n_live;
+    hipLaunchKernelGGL(ec_live_idx_kernel, grid256(2 * nv), dim3(256), 0, ctx->stream, 2 * nv, e->idx_p.as<uint64_t>(), e->idx_n.as<uint32_t>(),
+                       e->live_off.as<uint64_t>(), e->lidx_p.as<uint32_t>(), e->lidx_n.as<uint32_t>(), e->g_flags.as<uint32_t>() + 9);
+    if (na) hipLaunchKernelGGL(ec_live_arc_kernel, grid256(na), dim3(256), 0, ctx->stream, na, (const uint8_t *) e->arc_del.p, e->live_off.as<uint64_t>(),
+                               e->arc_w.as<uint64_t>(), e->arc_ls.as<uint32_t>(), e->vtx_hs_off.as<uint64_t>(), e->vtx_mpos.as<uint32_t>(),
+                               e->lidx_p.as<uint32_t>(), e->lidx_n.as<uint32_t>(), e->larc.as<EcLiveArc>(), e->g_flags.as<uint32_t>() + 8);
+    uint32_t fl[2] = {0, 0};
+    CK(hipMemcpyAsync(fl, e->g_flags.as<uint32_t>() + 8, 8, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    const uint32_t no_src = fl[0];
+    graph_branches = fl[1] != 0;
+    if (no_src && ctx->n_occ) { ctx->err = "error correction: a live vertex has no k-mer on this shard (import it: oatk_hip_ec_import_kmers)"; return OATK_E_STATE; }
+    lv.idx_p = e->lidx_p.as<uint32_t>(), lv.idx_n = e->lidx_n.as<uint32_t>(), lv.arc = e->larc.as<EcLiveArc>();
+    return OATK_OK;
+}
+
+// the blocks of every read as the solver's work list (e->work, e->seg, e->blk_off), what the reads keep between their blocks (e->copy_n, e->keep_all), and with
+// keep_seq a slot per block for its consensus
+static int ec_list_blocks(oatk_hip_ctx *ctx, EcState *e, const EcReads &rd, const EcLive &lv, bool keep_seq, double max_edist, uint64_t &n_work)
+{
+    const uint64_t nr = ctx->n_reads, nocc = ctx->n_occ;
+    EENSURE(n_blocks, (nr + 1) * 4);
+    EENSURE(new_n, (nr + 1) * 4); EENSURE(copy_n, (nr + 1) * 4); EENSURE(keep_all, nr + 1);
+    // One walk over the chains: it counts a read's blocks and stages their descriptors, n + 1 entries per read of n syncmers (ec.hpp: ec_stage_blocks_wave_kernel).
+    // The staging array is val_occ, which nothing holds before the chains are assembled and which is of this size once they are (a buffer of its own would be
+    // another 8 bytes per chain entry, 0.4 GB at 2 M reads).  Its last reader is ec_fill_work_kernel below; the assembly (ec_assemble_chains) is its next writer.
+    const uint64_t stage_cap = nocc + nr + 1;
+    e->staged_over = 0;
+    static_assert(sizeof(EcSeg) == 8, "a staging entry is one val_occ entry");
+    EENSURE(val_occ, stage_cap * sizeof(EcSeg));
+    hipLaunchKernelGGL(ec_stage_blocks_wave_kernel, ec_read_blocks(nr), dim3(256), 0, ctx->stream, rd, (const uint8_t *) e->scm_del.p, e->n_blocks.as<uint32_t>(), e->copy_n.as<uint32_t>(),
+                       e->keep_all.as<uint8_t>(), e->val_occ.as<EcSeg>(), stage_cap, e->g_flags.as<uint32_t>() + 10);
+    CK(hipMemcpyAsync(&e->staged_over, e->g_flags.as<uint32_t>() + 10, 4, hipMemcpyDeviceToHost, ctx->stream));       // (waited for with the scan's total)
+    n_work = 0;
+    { int rc = prim_scan_total_u32(ctx, e->n_blocks, e->n_blocks64, e->blk_off, nr, &n_work); if (rc) return rc; }
+    if (e->staged_over) { ctx->err = "error correction: a read has more error blocks than syncmers + 1 (the block walk's staging array)"; return OATK_E_STATE; }
+    EENSURE(work, (n_work + 1) * sizeof(EcWork)); EENSURE(out, (n_work + 1) * sizeof(EcBlockOut));
+    e->n_work = n_work;
+    EENSURE(seg, (n_work + 1) * sizeof(EcSeg));
+    hipLaunchKernelGGL(ec_fill_work_kernel, grid256(nr), dim3(256), 0, ctx->stream, rd, lv, e->blk_off.as<uint64_t>(), (const EcSeg *) e->val_occ.as<EcSeg>(), e->work.as<EcWork>(), e->seg.as<EcSeg>());
+    // a fixed slot per block for its optimum consensus (oatk_hip_ec_keep_seq): no atomics, no overflow, and the same addresses whichever launch finishes a block
+    if (keep_seq) {
+        uint64_t slot_words = 0;
+        EENSURE(slot_w, (n_work + 1) * 4); EENSURE(qend, (n_work + 1) * 4);
+        if (n_work) hipLaunchKernelGGL(ec_slot_words_kernel, grid256(n_work), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), n_work, max_edist, e->slot_w.as<uint32_t>());
+        { int rc = prim_scan_total_u32(ctx, e->slot_w, e->slot_w64, e->slot_off, n_work, &slot_words); if (rc) return rc; }
+        EENSURE(slots, (slot_words + 4) * 4);
+    }
+    return OATK_OK;
+}
+
+// the corrected chains (e->new_k, new_m, new_s behind e->new_off) and the (syncmer, occurrence) pairs of the refreshed table (e->key_id, e->val_occ): the block
+// statistics, the chains' lengths and then the chains from the blocks' descriptors and outcomes, nobody walking a chain again (ec.hpp: EcSeg)
+static int ec_assemble_chains(oatk_hip_ctx *ctx, EcState *e, const EcKnobs &kn, const EcReads &rd, const uint64_t *scm_s, uint64_t n_work, uint64_t &tot)
+{
+    const uint64_t nr = ctx->n_reads;
+    EENSURE(new_n, (nr + 1) * 4);
+    CK(hipMemsetAsync(e->stats.p, 0, 16 * 8, ctx->stream));
+    EcAssembleArgs aa;
+    aa.rd = rd, aa.scm_del = (const uint8_t *) e->scm_del.p, aa.scm_s = scm_s, aa.blk_off = e->blk_off.as<uint64_t>();
+    aa.out = e->out.as<EcBlockOut>(), aa.path_pool = e->path_pool.as<uint64_t>(), aa.new_n = e->new_n.as<uint32_t>(), aa.new_off = nullptr;
+    aa.new_k_mer = nullptr, aa.new_s_mer = nullptr, aa.new_m_pos = nullptr, aa.old_s_mer = ctx->pos_smer.as<uint64_t>();
+    aa.stats = (unsigned long long *) e->stats.p, aa.pass = 1, aa.seg = e->seg.as<EcSeg>(), aa.keep_all = e->keep_all.as<uint8_t>();
+    if (n_work) hipLaunchKernelGGL(ec_block_stats_kernel, dim3((unsigned) (n_work / 256 + 1 < 512? n_work / 256 + 1 : 512)), dim3(256), 0, ctx->stream, e->work.as<EcWork>(),
+                                   e->out.as<EcBlockOut>(), n_work, (unsigned long long *) e->stats.p);
+    hipLaunchKernelGGL(ec_new_n_seg_kernel, grid256(nr), dim3(256), 0, ctx->stream, nr, e->copy_n.as<uint32_t>(), e->blk_off.as<uint64_t>(), e->seg.as<EcSeg>(), e->out.as<EcBlockOut>(), e->new_n.as<uint32_t>());
+    tot = 0;
+    { int rc = prim_scan_total_u32(ctx, e->new_n, e->new_n64, e->new_off, nr, &tot); if (rc) return rc; }
+    e->new_tot = tot;
+    EENSURE(new_k, (tot + 1) * 8); EENSURE(new_m, (tot + 1) * 4); EENSURE(new_s, (tot + 1) * 8);
+    // (val_occ held the block walk's staging entries until ec_fill_work_kernel had read them, ec_list_blocks: nothing may write it between the two)
+    EENSURE(key_id, (tot + 1) * 4); EENSURE(key_sorted, (tot + 1) * 4); EENSURE(val_occ, (tot + 1) * 8); EENSURE(occ, (tot + 1) * 8);
+    aa.new_off = e->new_off.as<uint64_t>(), aa.new_k_mer = e->new_k.as<uint64_t>(), aa.new_m_pos = e->new_m.as<uint32_t>(), aa.new_s_mer = e->new_s.as<uint64_t>();
+    aa.key_id = e->key_id.as<uint32_t>(), aa.val_occ = e->val_occ.as<uint64_t>(), aa.sid0 = ctx->sid0;
+    if (kn.assemble_pairs) hipLaunchKernelGGL(ec_assemble_pair_kernel, dim3((unsigned) ((nr + 7) / 8 > 0? (nr + 7) / 8 : 1)), dim3(256), 0, ctx->stream, aa);      // four waves, two reads each
+    else hipLaunchKernelGGL(ec_assemble_seg_kernel, ec_read_blocks(nr), dim3(256), 0, ctx->stream, aa);
+    return OATK_OK;
+}
+
+// update_syncmer_db (syncerr.c:769-814) from the `tot` pairs the assembly left: occurrence lists (e->occ behind e->occ_off), coverage, marks; `chk` is the
+// coverage summed up, which the caller holds against tot
+static int ec_refresh_table(oatk_hip_ctx *ctx, EcState *e, uint64_t tot, uint64_t &chk)
+{
+    const uint64_t nv = e->g_n_vtx;
+    EENSURE(cov, (nv + 1) * 4); EENSURE(fwd, (nv + 1) * 4);
+    CK(hipMemsetAsync(e->cov.p, 0, (nv + 1) * 4, ctx->stream));
+    CK(hipMemsetAsync(e->fwd.p, 0, (nv + 1) * 4, ctx->stream));
+    if (tot) {
+        unsigned id_bits = 1;   // the keys are syncmer ids: the passes stop at the id's highest bit
+        while (id_bits < 32 && (nv - 1) >> id_bits) ++id_bits;
+        // stable: occurrences of one syncmer stay in (sid, idx) order (syncerr.c:796-805)
+        PRIM(rocprim::radix_sort_pairs, e->key_id.as<uint32_t>(), e->key_sorted.as<uint32_t>(), e->val_occ.as<uint64_t>(), e->occ.as<uint64_t>(), tot, 0, id_bits, ctx->stream);
+        // coverage and forward-strand counts per syncmer from the sorted lists: one pass over the runs (cov and fwd are zero: runs that cross a wave's tile add up)
+        hipLaunchKernelGGL(ec_cov_runs_kernel, grid256(tot), dim3(256), 0, ctx->stream, tot, e->key_sorted.as<uint32_t>(), e->occ.as<uint64_t>(), e->cov.as<uint32_t>(), e->fwd.as<uint32_t>());
+    }
+    hipLaunchKernelGGL(ec_del_kernel, grid256(nv), dim3(256), 0, ctx->stream, nv, e->fwd.as<uint32_t>(), e->scm_del.as<uint8_t>());
+    chk = 0;
+    return prim_scan_total_u32(ctx, e->cov, e->cov64, e->occ_off, nv, &chk);
+}
+
 }  // namespace oatk
 
 // the rest of read_error_correction (syncerr.c:819): blocks, search, corrected chains, refreshed table
@@ -1434,67 +1512,13 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
     e->seq_kept = false;
     const EcKnobs kn = ec_knobs_read();
     EC_VIEWS();
-    // the arcs that survive, squeezed, each with what the search needs about its target (ec.hpp: EcLiveArc)
+    (void) nv; (void) na; (void) nr;
+    // ---- live arcs, blocks ----
     EcLive lv;
     bool graph_branches = true;
-    {
-        uint64_t n_live = 0;
-        EENSURE(g_flags, 64);
-        CK(hipMemsetAsync(e->g_flags.as<uint32_t>() + 8, 0, 12, ctx->stream));         // [8] a live vertex without its k-mer here, [9] the live graph branches, [10] a block beyond a read's staging entries
-        EENSURE(live32, (na + 1) * 4); EENSURE(lidx_p, (2 * nv + 1) * 4); EENSURE(lidx_n, (2 * nv + 1) * 4);
-        if (na) hipLaunchKernelGGL(ec_live_flag_kernel, grid256(na), dim3(256), 0, ctx->stream, na, (const uint8_t *) e->arc_del.p, e->live32.as<uint32_t>());
-        { int rc = prim_scan_total_u32(ctx, e->live32, e->live64, e->live_off, na, &n_live); if (rc) return rc; }
-        if (n_live >= 0xFFFFFFFFULL) { ctx->err = "error correction: more than 2^32 live arcs"; return OATK_E_ARG; }
-        EENSURE(larc, (n_live + 1) * sizeof(EcLiveArc));
-        e->n_live = n_live;
-        hipLaunchKernelGGL(ec_live_idx_kernel, grid256(2 * nv), dim3(256), 0, ctx->stream, 2 * nv, e->idx_p.as<uint64_t>(), e->idx_n.as<uint32_t>(),
-                           e->live_off.as<uint64_t>(), e->lidx_p.as<uint32_t>(), e->lidx_n.as<uint32_t>(), e->g_flags.as<uint32_t>() + 9);
-        if (na) hipLaunchKernelGGL(ec_live_arc_kernel, grid256(na), dim3(256), 0, ctx->stream, na, (const uint8_t *) e->arc_del.p, e->live_off.as<uint64_t>(),
-                                   e->arc_w.as<uint64_t>(), e->arc_ls.as<uint32_t>(), e->vtx_hs_off.as<uint64_t>(), e->vtx_mpos.as<uint32_t>(),
-                                   e->lidx_p.as<uint32_t>(), e->lidx_n.as<uint32_t>(), e->larc.as<EcLiveArc>(), e->g_flags.as<uint32_t>() + 8);
-        uint32_t fl[2] = {0, 0};
-        CK(hipMemcpyAsync(fl, e->g_flags.as<uint32_t>() + 8, 8, hipMemcpyDeviceToHost, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
-        const uint32_t no_src = fl[0];
-        graph_branches = fl[1] != 0;
-        if (no_src && ctx->n_occ) { ctx->err = "error correction: a live vertex has no k-mer on this shard (import it: oatk_hip_ec_import_kmers)"; return OATK_E_STATE; }
-        lv.idx_p = e->lidx_p.as<uint32_t>(), lv.idx_n = e->lidx_n.as<uint32_t>(), lv.arc = e->larc.as<EcLiveArc>();
-    }
-
-    // ---- blocks ----
-    EENSURE(n_blocks, (nr + 1) * 4);
-    const dim3 rblocks((unsigned) ((nr + ECR_READS_PER_BLOCK - 1) / ECR_READS_PER_BLOCK > 0? (nr + ECR_READS_PER_BLOCK - 1) / ECR_READS_PER_BLOCK : 1));      // a wave per read
-    EENSURE(new_n, (nr + 1) * 4); EENSURE(copy_n, (nr + 1) * 4); EENSURE(keep_all, nr + 1);
-    // One walk over the chains: it counts a read's blocks and stages their descriptors, n + 1 entries per read of n syncmers (ec.hpp: ec_stage_blocks_wave_kernel).
-    // The staging array is val_occ, which nothing holds before the chains are assembled and which is of this size once they are (a buffer of its own would be
-    // another 8 bytes per chain entry, 0.4 GB at 2 M reads).  Its last reader is ec_fill_work_kernel below; the assembly ("corrected chains") is its next writer.
-    const uint64_t stage_cap = nocc + nr + 1;
-    e->staged_over = 0;
-    if (kn.list_walk) hipLaunchKernelGGL(ec_count_blocks_wave_kernel, rblocks, dim3(256), 0, ctx->stream, rd, (const uint8_t *) e->scm_del.p, e->n_blocks.as<uint32_t>());
-    else {
-        static_assert(sizeof(EcSeg) == 8, "a staging entry is one val_occ entry");
-        EENSURE(val_occ, stage_cap * sizeof(EcSeg));
-        hipLaunchKernelGGL(ec_stage_blocks_wave_kernel, rblocks, dim3(256), 0, ctx->stream, rd, (const uint8_t *) e->scm_del.p, e->n_blocks.as<uint32_t>(), e->copy_n.as<uint32_t>(),
-                           e->keep_all.as<uint8_t>(), e->val_occ.as<EcSeg>(), stage_cap, e->g_flags.as<uint32_t>() + 10);
-        CK(hipMemcpyAsync(&e->staged_over, e->g_flags.as<uint32_t>() + 10, 4, hipMemcpyDeviceToHost, ctx->stream));       // (waited for with the scan's total)
-    }
+    { int rc = ec_live_arcs(ctx, e, lv, graph_branches); if (rc) return rc; }
     uint64_t n_work = 0;
-    { int rc = prim_scan_total_u32(ctx, e->n_blocks, e->n_blocks64, e->blk_off, nr, &n_work); if (rc) return rc; }
-    if (e->staged_over) { ctx->err = "error correction: a read has more error blocks than syncmers + 1 (the block walk's staging array)"; return OATK_E_STATE; }
-    EENSURE(work, (n_work + 1) * sizeof(EcWork)); EENSURE(out, (n_work + 1) * sizeof(EcBlockOut));
-    e->n_work = n_work;
-    EENSURE(seg, (n_work + 1) * sizeof(EcSeg));
-    if (kn.list_walk) hipLaunchKernelGGL(ec_list_blocks_wave_kernel, rblocks, dim3(256), 0, ctx->stream, rd, lv, (const uint8_t *) e->scm_del.p, e->blk_off.as<uint64_t>(), e->work.as<EcWork>(),
-                                         e->copy_n.as<uint32_t>(), e->seg.as<EcSeg>(), e->keep_all.as<uint8_t>());
-    else hipLaunchKernelGGL(ec_fill_work_kernel, grid256(nr), dim3(256), 0, ctx->stream, rd, lv, e->blk_off.as<uint64_t>(), (const EcSeg *) e->val_occ.as<EcSeg>(), e->work.as<EcWork>(), e->seg.as<EcSeg>());
-    // a fixed slot per block for its optimum consensus (oatk_hip_ec_keep_seq): no atomics, no overflow, and the same addresses whichever launch finishes a block
-    if (keep_seq) {
-        uint64_t slot_words = 0;
-        EENSURE(slot_w, (n_work + 1) * 4); EENSURE(qend, (n_work + 1) * 4);
-        if (n_work) hipLaunchKernelGGL(ec_slot_words_kernel, grid256(n_work), dim3(256), 0, ctx->stream, e->work.as<EcWork>(), n_work, max_edist, e->slot_w.as<uint32_t>());
-        { int rc = prim_scan_total_u32(ctx, e->slot_w, e->slot_w64, e->slot_off, n_work, &slot_words); if (rc) return rc; }
-        EENSURE(slots, (slot_words + 4) * 4);
-    }
+    { int rc = ec_list_blocks(ctx, e, rd, lv, keep_seq, max_edist, n_work); if (rc) return rc; }
     t_end(ctx, OATK_T_EC_MARK);
     t_begin(ctx, OATK_T_EC_SOLVE);
 
@@ -1532,55 +1556,12 @@ extern "C" int oatk_hip_ec_correct(oatk_hip_ctx *ctx, double max_edist)
         pool_cap = used + used / 4 + 4096;          // the pool overflowed: grow it and solve again
     }
 
-    // ---- corrected chains ----
+    // ---- corrected chains, refreshed table ----
     t_end(ctx, OATK_T_EC_SOLVE);
     t_begin(ctx, OATK_T_EC_REFRESH);
-    EENSURE(new_n, (nr + 1) * 4);
-    CK(hipMemsetAsync(e->stats.p, 0, 16 * 8, ctx->stream));
-    EcAssembleArgs aa;
-    aa.rd = rd, aa.scm_del = (const uint8_t *) e->scm_del.p, aa.scm_s = g.scm_s, aa.blk_off = e->blk_off.as<uint64_t>();
-    aa.out = e->out.as<EcBlockOut>(), aa.path_pool = e->path_pool.as<uint64_t>(), aa.new_n = e->new_n.as<uint32_t>(), aa.new_off = nullptr;
-    aa.new_k_mer = nullptr, aa.new_s_mer = nullptr, aa.new_m_pos = nullptr, aa.old_s_mer = ctx->pos_smer.as<uint64_t>();
-    aa.stats = (unsigned long long *) e->stats.p, aa.pass = 1, aa.seg = e->seg.as<EcSeg>(), aa.keep_all = e->keep_all.as<uint8_t>();
-    if (n_work) hipLaunchKernelGGL(ec_block_stats_kernel, dim3((unsigned) (n_work / 256 + 1 < 512? n_work / 256 + 1 : 512)), dim3(256), 0, ctx->stream, e->work.as<EcWork>(),
-                                   e->out.as<EcBlockOut>(), n_work, (unsigned long long *) e->stats.p);
-    // the chains' lengths and then the chains from the descriptors the list walk left, nobody walking a chain again (ec.hpp: EcSeg)
-    if (kn.assemble_walk) hipLaunchKernelGGL(ec_new_n_kernel, grid256(nr), dim3(256), 0, ctx->stream, nr, e->copy_n.as<uint32_t>(), e->blk_off.as<uint64_t>(), e->work.as<EcWork>(), e->out.as<EcBlockOut>(), e->new_n.as<uint32_t>());
-    else hipLaunchKernelGGL(ec_new_n_seg_kernel, grid256(nr), dim3(256), 0, ctx->stream, nr, e->copy_n.as<uint32_t>(), e->blk_off.as<uint64_t>(), e->seg.as<EcSeg>(), e->out.as<EcBlockOut>(), e->new_n.as<uint32_t>());
-    uint64_t tot = 0;
-    { int rc = prim_scan_total_u32(ctx, e->new_n, e->new_n64, e->new_off, nr, &tot); if (rc) return rc; }
-    e->new_tot = tot;
-    EENSURE(new_k, (tot + 1) * 8); EENSURE(new_m, (tot + 1) * 4); EENSURE(new_s, (tot + 1) * 8);
-    // (val_occ held the block walk's staging entries until ec_fill_work_kernel had read them, "blocks" above: nothing may write it between the two)
-    EENSURE(key_id, (tot + 1) * 4); EENSURE(key_sorted, (tot + 1) * 4); EENSURE(val_occ, (tot + 1) * 8); EENSURE(occ, (tot + 1) * 8);
-    aa.new_off = e->new_off.as<uint64_t>(), aa.new_k_mer = e->new_k.as<uint64_t>(), aa.new_m_pos = e->new_m.as<uint32_t>(), aa.new_s_mer = e->new_s.as<uint64_t>();
-    aa.key_id = e->key_id.as<uint32_t>(), aa.val_occ = e->val_occ.as<uint64_t>(), aa.sid0 = ctx->sid0;
-    if (kn.assemble_walk) hipLaunchKernelGGL(ec_assemble_wave_kernel<1>, rblocks, dim3(256), 0, ctx->stream, aa);
-    else if (kn.assemble_pairs) hipLaunchKernelGGL(ec_assemble_pair_kernel, dim3((unsigned) ((nr + 7) / 8 > 0? (nr + 7) / 8 : 1)), dim3(256), 0, ctx->stream, aa);      // four waves, two reads each
-    else hipLaunchKernelGGL(ec_assemble_seg_kernel, rblocks, dim3(256), 0, ctx->stream, aa);
-
-    // ---- update_syncmer_db ----
-    EENSURE(cov, (nv + 1) * 4); EENSURE(fwd, (nv + 1) * 4);
-    CK(hipMemsetAsync(e->cov.p, 0, (nv + 1) * 4, ctx->stream));
-    CK(hipMemsetAsync(e->fwd.p, 0, (nv + 1) * 4, ctx->stream));
-    if (tot) {
-        unsigned id_bits = 1;   // the keys are syncmer ids: the passes stop at the id's highest bit
-        while (id_bits < 32 && (nv - 1) >> id_bits) ++id_bits;
-        // stable: occurrences of one syncmer stay in (sid, idx) order (syncerr.c:796-805)
-        PRIM(rocprim::radix_sort_pairs, e->key_id.as<uint32_t>(), e->key_sorted.as<uint32_t>(), e->val_occ.as<uint64_t>(), e->occ.as<uint64_t>(), tot, 0, id_bits, ctx->stream);
-        // coverage and forward-strand counts per syncmer from the sorted lists: one pass over the runs (cov and fwd are zero: runs that cross a wave's tile add up), or
-        // (key_id is free again: it carries the flags and their prefix sums) the three passes it replaced
-        if (kn.refresh_runs) hipLaunchKernelGGL(ec_cov_runs_kernel, grid256(tot), dim3(256), 0, ctx->stream, tot, e->key_sorted.as<uint32_t>(), e->occ.as<uint64_t>(), e->cov.as<uint32_t>(), e->fwd.as<uint32_t>());
-        else {
-        hipLaunchKernelGGL(ec_fwd_flag_kernel, grid256(tot), dim3(256), 0, ctx->stream, tot, e->occ.as<uint64_t>(), e->key_id.as<uint32_t>());
-        PRIM(rocprim::inclusive_scan, e->key_id.as<uint32_t>(), e->key_id.as<uint32_t>(), tot, rocprim::plus<uint32_t>(), ctx->stream);
-        hipLaunchKernelGGL(ec_cov_sorted_kernel, grid256(tot), dim3(256), 0, ctx->stream, tot, e->key_sorted.as<uint32_t>(), e->key_id.as<uint32_t>(),
-                           e->cov.as<uint32_t>(), e->fwd.as<uint32_t>());
-        }
-    }
-    hipLaunchKernelGGL(ec_del_kernel, grid256(nv), dim3(256), 0, ctx->stream, nv, e->fwd.as<uint32_t>(), e->scm_del.as<uint8_t>());
-    uint64_t chk = 0;
-    { int rc = prim_scan_total_u32(ctx, e->cov, e->cov64, e->occ_off, nv, &chk); if (rc) return rc; }
+    uint64_t tot = 0, chk = 0;
+    { int rc = ec_assemble_chains(ctx, e, kn, rd, g.scm_s, n_work, tot); if (rc) return rc; }
+    { int rc = ec_refresh_table(ctx, e, tot, chk); if (rc) return rc; }
     unsigned long long st[16];
     CK(hipMemcpyAsync(st, e->stats.p, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
     t_end(ctx, OATK_T_EC_REFRESH);

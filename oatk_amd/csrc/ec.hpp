@@ -2,9 +2,9 @@
 //
 // Replaces, on flat arrays that stay resident in HBM:
 //   find_error_syncmers            syncerr.c:679-757   -> ec_mark_kernel, ec_arc_del_kernel
-//   error blocks of a read         syncerr.c:339-612   -> ec_blocks (device function, shared by three kernels)
+//   error blocks of a read         syncerr.c:339-612   -> ec_blocks, ec_blocks_wave (device functions)
 //   dfs_search + wf_ed_core        syncerr.c:144-286, levdist.c:75-310 -> ec_wave_kernel (ec_wave.hpp)
-//   update_syncmer_db              syncerr.c:769-814   -> a stable radix sort of (syncmer, occurrence) pairs + ec_fwd_flag / ec_cov_sorted kernels (api_ec.inc)
+//   update_syncmer_db              syncerr.c:769-814   -> a stable radix sort of (syncmer, occurrence) pairs + ec_cov_runs_kernel, ec_del_kernel (api_ec.inc)
 //
 // The graph is the reference's asmg_t in arc-array order (sorted (v,w), graph.c:70-83) as CSR over oriented vertices.
 // Every vertex is one syncmer (utg id == syncmer id, syncerr.c:421-423) and its hoco consensus is the oriented k-mer of
@@ -195,11 +195,11 @@ struct __attribute__((aligned(16))) EcWork {   // one block, self-contained for 
     int32_t l, r;
     uint32_t hs16;                // hoco byte offset / 16 of the read
     uint32_t lp, ln;              // live arcs of beg_utg
-    uint32_t pad;                 // (list kernel -> ec_new_n_kernel) chain entries the read keeps if this block is NOT corrected (syncerr.c:533-542)
+    uint32_t pad;                 // chain entries the read keeps if this block is NOT corrected (syncerr.c:533-542); nothing on the device reads it any more
 };
 
-// What the assembly needs of a block besides its outcome, left by the walk that lists the blocks (one per EcWork, same index): the chain indices that
-// delimit it.  With them the corrected chain is a table of segments -- per block the originals kept in front of it, then its body (the optimum path's
+// What the assembly needs of a block besides its outcome, left by the walk that stages the blocks (one per EcWork, same index): the chain indices that
+// delimit it (EcBlock::beg, EcBlock::end cut at the chain's length) and two flags (EcBlock::r, an open end).  With them the corrected chain is a table of segments -- per block the originals kept in front of it, then its body (the optimum path's
 // interior, or the originals it keeps) -- and nobody walks the chain again (ec_new_n_seg_kernel, ec_assemble_seg_kernel).
 #define EC_SEG_R 1u               // leading block (EcBlock::r)
 #define EC_SEG_OPEN 2u            // end_utg == EC_NONE
@@ -260,7 +260,7 @@ __global__ void ec_live_arc_kernel(uint64_t n_arc, const uint8_t *arc_del, const
     larc[live_off[a]] = x;
 }
 
-// ---- assemble the corrected chains (syncerr.c:513-542, :585-612): pass 0 counts, pass 1 writes ----
+// ---- assemble the corrected chains (syncerr.c:513-542, :585-612) ----
 struct EcAssembleArgs {
     EcReads rd;
     const uint8_t *scm_del;
@@ -269,10 +269,10 @@ struct EcAssembleArgs {
     const EcBlockOut *out;
     const uint64_t *path_pool;
     uint32_t *new_n;              // [n_reads]
-    const uint64_t *new_off;      // [n_reads + 1] (pass 1)
+    const uint64_t *new_off;      // [n_reads + 1]
     uint64_t *new_k_mer, *new_s_mer;
     uint32_t *new_m_pos;
-    uint32_t *key_id;             // pass 1: the (syncmer, occurrence) pairs update_syncmer_db sorts, written along with the chains
+    uint32_t *key_id;             // the (syncmer, occurrence) pairs update_syncmer_db sorts, written along with the chains
     uint64_t *val_occ;
     uint64_t sid0;
     const uint64_t *old_s_mer;
@@ -286,8 +286,8 @@ struct EcAssembleArgs {
 // The same walk with ONE WAVE PER READ.  A HiFi read carries a few dozen syncmers, so its whole chain sits in the lanes of a wave: lane j
 // holds entry j, the two searches of the loop at syncerr.c:394-598 ("first good syncmer at or beyond a position", "first deleted syncmer
 // after it") are one ballot and a count-trailing-zeros each, and everything the callbacks write goes out with the lanes side by side
-// instead of one lane striding through its own read.  Four kernels use it -- block count, block list, and the two passes of the chain
-// assembly -- and the lane-per-read versions above remain for reads with more than 64 syncmers (lane 0 runs them).
+// instead of one lane striding through its own read.  ec_stage_blocks_wave_kernel uses it, and the lane-per-read version above remains for
+// reads with more than 64 syncmers (lane 0 runs it).
 // ---------------------------------------------------------------------------------------------------------------------------------
 // entry `lane` of v, in a scalar register: `lane` is the same in every active lane of the wave wherever these are called, so it goes to an SGPR and v_readlane
 // takes the value (a __shfl is a ds_bpermute, a wait on LDS and a v_readfirstlane -- inside the walk's serial loop)
@@ -355,9 +355,9 @@ __device__ int ec_blocks_wave(int lane, int32_t n_, uint64_t km, uint32_t mp, bo
 }
 
 // A wave takes ECR_RPW consecutive reads: everything the walks need of them is requested first (the loads of all of them are in flight
-// together), then the reads are walked one after the other.  Measured at config 3 (2 M reads): with two reads per wave the count + list
-// kernels take what they take with one (2.9 ms) and the assembly passes are slower (7.0 against 6.3 ms) -- the walks are not bound by the
-// rate at which waves launch but by what each does once its data is there -- so a wave takes ONE read.
+// together), then the reads are walked one after the other.  Measured at config 3 (2 M reads, on the walks of that time: DESIGN.md 7): two
+// reads per wave were no faster than one -- the walks are not bound by the rate at which waves launch but by what each does once its
+// data is there -- so a wave takes ONE read.
 #ifndef ECR_RPW
 #define ECR_RPW 1
 #endif
@@ -390,90 +390,12 @@ __device__ __forceinline__ void ecr_load(const EcReads &rd, const uint8_t *scm_d
     for (int k = 0; k < ECR_RPW; ++k) q[k].del = q[k].n >= 0 && q[k].n <= 64 && lane < q[k].n && scm_del[q[k].km >> 1];
 }
 
-__global__ __launch_bounds__(256) void ec_count_blocks_wave_kernel(EcReads rd, const uint8_t *scm_del, uint32_t *n_blocks)
-{
-    const uint64_t r0 = ((uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6)) * ECR_RPW;
-    const int lane = threadIdx.x & 63;
-    if (r0 >= rd.n_reads) return;
-    EcrRead q[ECR_RPW];
-    ecr_load(rd, scm_del, r0, lane, q);
-#pragma unroll
-    for (int k = 0; k < ECR_RPW; ++k) {
-        const EcrRead &x = q[k];
-        if (x.n < 0) continue;
-        int nb = 0;
-        if (x.n > 64) {
-            if (lane == 0) {
-                ec_blocks(scm_del, rd.k_mer + x.o, rd.m_pos + x.o, x.n, x.hoco_l, rd.K, [&](int, const EcBlock &) { ++nb; }, [](int32_t, int32_t) {});
-                n_blocks[x.r] = (uint32_t) nb;
-            }
-            continue;
-        }
-        ec_blocks_wave(lane, x.n, x.km, x.mp, x.del, x.hoco_l, rd.K, [&](int, const EcBlock &) { ++nb; }, [](int32_t, int32_t) {});
-        if (lane == 0) n_blocks[x.r] = (uint32_t) nb;
-    }
-}
-
-__global__ __launch_bounds__(256) void ec_list_blocks_wave_kernel(EcReads rd, EcLive lv, const uint8_t *scm_del, const uint64_t *blk_off, EcWork *work, uint32_t *copy_n, EcSeg *seg,
-                                                                  uint8_t *keep_all)
-{
-    const uint64_t r0 = ((uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6)) * ECR_RPW;
-    const int lane = threadIdx.x & 63;
-    if (r0 >= rd.n_reads) return;
-    EcrRead q[ECR_RPW];
-    ecr_load(rd, scm_del, r0, lane, q);
-    EcWork *wq[ECR_RPW];
-    EcSeg *sq[ECR_RPW];
-    uint32_t hq[ECR_RPW];
-#pragma unroll
-    for (int k = 0; k < ECR_RPW; ++k) {
-        const uint64_t b0 = q[k].n >= 0? blk_off[q[k].r] : 0;
-        wq[k] = q[k].n >= 0? work + b0 : nullptr, sq[k] = q[k].n >= 0? seg + b0 : nullptr, hq[k] = q[k].n >= 0? (uint32_t) (rd.off[q[k].r] >> 6) : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < ECR_RPW; ++k) {
-        const EcrRead &x = q[k];
-        if (x.n < 0) continue;
-        EcWork *w = wq[k];
-        EcSeg *sg = sq[k];
-        const uint32_t hs16 = hq[k];
-        const int32_t n = x.n;
-        auto put = [&](int i, const EcBlock &b) {
-            EcWork y;
-            y.beg_utg = b.beg_utg, y.end_utg = b.end_utg, y.read = (uint32_t) x.r, y.beg_pos = b.beg_pos, y.l = b.l, y.r = b.r;
-            y.hs16 = hs16, y.lp = lv.idx_p[b.beg_utg], y.ln = lv.idx_n[b.beg_utg];
-            // what the assembly copies when the block is not corrected (ec_assemble_wave_kernel: copy(0, beg) / copy(beg + 1, min(end, n)))
-            const int32_t last = b.end < n? b.end : n;
-            y.pad = b.r? (uint32_t) b.beg : (b.beg + 1 < n && last > b.beg + 1? (uint32_t) (last - b.beg - 1) : 0u);
-            w[i] = y;
-            sg[i] = ec_seg_of(b, n);
-        };
-        // ... and what it copies between the blocks whatever becomes of them; a read without a good syncmer keeps its chain (syncerr.c:562-572)
-        uint32_t cp = 0;
-        auto on_copy = [&](int32_t first, int32_t last) { if (last > first) cp += (uint32_t) (last - first); };
-        if (x.n > 64) {
-            if (lane == 0) {
-                const int nbs = ec_blocks(scm_del, rd.k_mer + x.o, rd.m_pos + x.o, x.n, x.hoco_l, rd.K, put, on_copy);
-                copy_n[x.r] = nbs < 0? (uint32_t) n : cp;
-                keep_all[x.r] = nbs < 0;
-            }
-            continue;
-        }
-        // lane i keeps block i and writes it after the walk, so the gathers of a read's blocks are in flight together
-        EcBlock mine;
-        mine.beg_utg = 0, mine.end_utg = 0, mine.beg_pos = 0, mine.l = 0, mine.beg = 0, mine.end = 0, mine.r = 0;
-        const int nb = ec_blocks_wave(lane, x.n, x.km, x.mp, x.del, x.hoco_l, rd.K,
-                                      [&](int i, const EcBlock &b) { if (i < 64) { if (lane == i) mine = b; } else if (lane == 0) put(i, b); }, on_copy);
-        if (lane < nb) put(lane, mine);
-        if (lane == 0) copy_n[x.r] = nb < 0? (uint32_t) n : cp, keep_all[x.r] = nb < 0;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The blocks listed in ONE walk (r16).  The count walk cannot write a block where it belongs -- blk_off[r] is a scan away -- but it knows everything the list
-// walk found out: copy_n and keep_all need nothing from the scan, and a block is the 8 bytes of its EcSeg (the chain indices of its anchors and two flags;
-// every other field of its EcWork is a function of the chain entries at those two indices).  So the walk leaves the descriptors in a staging array at a
-// place known beforehand, and a kernel without a walk in it builds the work items behind the scan (ec_fill_work_kernel).
+// The blocks listed in ONE walk (r16).  The walk that counts a read's blocks cannot write a block where it belongs -- blk_off[r] is a scan away -- but it finds
+// out everything there is to know: copy_n and keep_all need nothing from the scan, and a block is the 8 bytes of its EcSeg (EcBlock::beg and EcBlock::end, the
+// chain indices of its anchors, and the flags for EcBlock::r and an open end; every other field of its EcWork is a function of the chain entries at those two
+// indices).  So the walk leaves the descriptors in a staging array at a place known beforehand, and a kernel without a walk in it builds the work items
+// behind the scan (ec_fill_work_kernel).
 //
 // Staging: read r owns the n + 1 entries from scm_off[r] + r on, n = its chain's length.  That is enough: a round of the walk yields at most one block and
 // moves `beg` on (-1, then end + 1 >= 1, then at least two further each round) until it exceeds n -- at most n + 1 rounds.  A block beyond that, or beyond
@@ -519,7 +441,8 @@ __global__ __launch_bounds__(256) void ec_stage_blocks_wave_kernel(EcReads rd, c
     }
 }
 
-// What ec_list_blocks_wave_kernel's `put` took from the walk's EcBlock, read back from the chain entries at the block's two indices (ec_blocks: the three cases).
+// The work item of a block from its staged descriptor: beg_utg, end_utg, beg_pos, l and r as the walk's EcBlock has them, read back from the chain entries at
+// the descriptor's two indices (ec_blocks: the three cases -- leading, open, closed); `pad` from EcBlock::beg and EcBlock::end alone.
 // o, n: the read's chain; d: the block's staged descriptor.
 __device__ __forceinline__ EcWork ec_work_of(const EcReads &rd, const EcLive &lv, uint64_t r, uint64_t o, int32_t n, const EcSeg &d)
 {
@@ -567,22 +490,6 @@ __global__ __launch_bounds__(256) void ec_fill_work_kernel(EcReads rd, EcLive lv
     }
 }
 
-// the corrected chains' lengths from the blocks' outcomes (r04; until then a third walk over the chains, ec_assemble_wave_kernel<0>): what the read keeps between
-// its blocks, plus per block the optimum path's interior (syncerr.c:513-532) or the originals it keeps
-__global__ __launch_bounds__(256) void ec_new_n_kernel(uint64_t n_reads, const uint32_t *copy_n, const uint64_t *blk_off, const EcWork *work, const EcBlockOut *out, uint32_t *new_n)
-{
-    const uint64_t r = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_reads) return;
-    uint32_t s = copy_n[r];
-    for (uint64_t i = blk_off[r]; i < blk_off[r + 1]; ++i) {
-        if (out[i].status == EC_SUCCESS) {
-            const int32_t np = (int32_t) out[i].np;
-            s += work[i].r? (uint32_t) (np >= 1? np - 1 : 0) : (uint32_t) ((np >= 2? np - 2 : 0) + (work[i].end_utg == EC_NONE && np > 1? 1 : 0));
-        } else s += work[i].pad;
-    }
-    new_n[r] = s;
-}
-
 // stats[11] of read_error_correction (syncerr.c:502-504, :513-542) from the solved blocks; a small fixed grid strides over them and every
 // workgroup adds its eleven sums once (eleven addresses take atomics one at a time: 90 k of them cost 0.4 ms, 3 k nothing)
 __global__ __launch_bounds__(256) void ec_block_stats_kernel(const EcWork *work, const EcBlockOut *out, uint64_t n_work, unsigned long long *stats)
@@ -607,7 +514,7 @@ __global__ __launch_bounds__(256) void ec_block_stats_kernel(const EcWork *work,
     }
 }
 
-// one read, lane-serial (the body of ec_assemble_kernel without the statistics): reads with more than 64 syncmers
+// one read, lane-serial, by a walk of its own over the chain: reads with more than 64 syncmers or blocks (ec_assemble_seg_read hands them over)
 __device__ inline void ec_assemble_read_serial(const EcAssembleArgs &a, uint64_t r)
 {
     const uint64_t o = a.rd.scm_off[r];
@@ -659,94 +566,14 @@ __device__ inline void ec_assemble_read_serial(const EcAssembleArgs &a, uint64_t
     if (!a.pass) a.new_n[r] = cnt;
 }
 
-// the corrected chains (syncerr.c:513-542, :585-612), pass 0 counts and pass 1 writes, one wave per read
-template <int PASS>
-__global__ __launch_bounds__(256) void ec_assemble_wave_kernel(EcAssembleArgs a)
-{
-    const uint64_t r0 = ((uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6)) * ECR_RPW;
-    const int lane = threadIdx.x & 63;
-    if (r0 >= a.rd.n_reads) return;
-    EcrRead q[ECR_RPW];
-    ecr_load(a.rd, a.scm_del, r0, lane, q);
-    // lane i holds the outcome of block i of each read: one load for all of a read's blocks instead of one after the other inside the walk
-    const EcBlockOut *boq[ECR_RPW];
-    uint32_t st_q[ECR_RPW], np_q[ECR_RPW];
-    uint64_t path_q[ECR_RPW], w0_q[ECR_RPW], s_q[ECR_RPW];
-#pragma unroll
-    for (int k = 0; k < ECR_RPW; ++k) {
-        const bool live = q[k].n >= 0;
-        const uint64_t b0 = live? a.blk_off[q[k].r] : 0;
-        const int32_t nbk = live? (int32_t) (a.blk_off[q[k].r + 1] - b0) : 0;
-        boq[k] = a.out + b0;
-        st_q[k] = EC_FAILURE, np_q[k] = 0, path_q[k] = 0;
-        if (lane < nbk) st_q[k] = boq[k][lane].status, np_q[k] = boq[k][lane].np, path_q[k] = boq[k][lane].path_off;
-        w0_q[k] = PASS && live? a.new_off[q[k].r] : 0;
-        s_q[k] = PASS && live && q[k].n <= 64 && lane < q[k].n? a.old_s_mer[q[k].o + lane] : 0;    // a syncmer's s-mer is the same at every occurrence (count.hpp: check_smer_kernel)
-    }
-#pragma unroll
-    for (int k = 0; k < ECR_RPW; ++k) {
-        const EcrRead &x = q[k];
-        if (x.n < 0) continue;
-        if (x.n > 64) {
-            if (lane == 0) ec_assemble_read_serial(a, x.r);
-            continue;
-        }
-        const int32_t n = x.n;
-        const uint64_t km = x.km, my_s = s_q[k], w0 = w0_q[k], my_path = path_q[k];
-        const uint32_t mp = x.mp, my_status = st_q[k], my_np = np_q[k];
-        const EcBlockOut *bo = boq[k];
-        uint64_t wpos = w0;
-        const uint64_t sid = (a.sid0 + x.r) << 32;
-        auto write = [&](uint64_t at, uint64_t kk, uint32_t m, uint64_t sv) {
-            a.new_k_mer[at] = kk, a.new_m_pos[at] = m, a.new_s_mer[at] = sv;
-            a.key_id[at] = (uint32_t) (kk >> 1), a.val_occ[at] = sid | (at - w0) << 1 | (m & 1u);                 // syncerr.c:796-805
-        };
-        auto copy = [&](int32_t first, int32_t last) {                     // original entries [first, last) stay
-            if (last <= first) return;
-            if (PASS && lane >= first && lane < last) write(wpos + (uint32_t) (lane - first), km, mp, my_s);
-            wpos += (uint32_t) (last - first);
-        };
-        const int nb = ec_blocks_wave(lane, n, km, mp, x.del, x.hoco_l, a.rd.K,
-            [&](int i, const EcBlock &b) {
-                const uint32_t status = i < 64? ecr_u32(my_status, i) : bo[i].status;
-                if (status == EC_SUCCESS) {
-                    const int32_t np = (int32_t) (i < 64? ecr_u32(my_np, i) : bo[i].np);
-                    const uint64_t *path = a.path_pool + (i < 64? ecr_u64(my_path, i) : bo[i].path_off);
-                    int32_t c;
-                    if (b.r) c = np >= 1? np - 1 : 0;
-                    else c = (np >= 2? np - 2 : 0) + (b.end_utg == EC_NONE && np > 1? 1 : 0);
-                    if (PASS) {
-                        for (int32_t t = lane; t < c; t += 64) {
-                            const uint64_t p = b.r? path[np - 1 - t] : path[1 + t];
-                            const uint64_t kk = (p & ~1ULL) | 1ULL;
-                            write(wpos + (uint32_t) t, kk, b.r? 0xFFFFFFFFu ^ (uint32_t) (p & 1ULL) : 0xFFFFFFFEu | (uint32_t) (p & 1ULL), a.scm_s[kk >> 1]);
-                        }
-                    }
-                    wpos += (uint32_t) c;
-                } else if (b.r) {
-                    copy(0, b.beg);
-                } else if (b.beg + 1 < n) {
-                    copy(b.beg + 1, b.end < n? b.end : n);
-                }
-            },
-            copy);
-        if (nb < 0) {                                    // no good syncmer: the read keeps its arrays (syncerr.c:562-572)
-            wpos = w0;
-            if (PASS && lane < n) write(w0 + (uint32_t) lane, km, mp, my_s);
-            wpos += (uint32_t) n;
-        }
-        if (!PASS && lane == 0) a.new_n[x.r] = (uint32_t) (wpos - w0);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The corrected chains WITHOUT a walk: from the descriptors the list walk left (EcSeg) and the blocks' outcomes.  A read with blocks 0 .. nb - 1 becomes
+// The corrected chains WITHOUT a walk: from the descriptors the block walk left (EcSeg) and the blocks' outcomes.  A read with blocks 0 .. nb - 1 becomes
 //   front(0) body(0) front(1) body(1) ... front(nb - 1) body(nb - 1)
 // front(i) = the originals [end(i - 1), beg(i)] (ec_seg_front), body(i) = ec_seg_body entries; the last block of a read always ends at or beyond n (the walk
 // leaves its loop nowhere else), so nothing follows it.  A read without a block is one without a good syncmer (the first round of the walk either finds the
-// leading block or gives the read up) and keeps its chain; the list walk says so in keep_all[] all the same.
+// leading block or gives the read up) and keeps its chain; the block walk says so in keep_all[] all the same.
 // ---------------------------------------------------------------------------------------------------------------------------------
-// the chains' lengths: a lane per read over its blocks' descriptors and outcomes (ec_new_n_kernel reads the 48-byte EcWork of every block for three of its fields)
+// the chains' lengths: a lane per read over its blocks' 8-byte descriptors and outcomes
 __global__ __launch_bounds__(256) void ec_new_n_seg_kernel(uint64_t n_reads, const uint32_t *copy_n, const uint64_t *blk_off, const EcSeg *seg, const EcBlockOut *out, uint32_t *new_n)
 {
     const uint64_t r = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -777,7 +604,7 @@ __device__ __forceinline__ uint32_t ecr_incl_sum(uint32_t v)
 // One wave per read, lane i holds chain entry i AND block i.  Two prefix sums over the blocks give every segment's place (all entries) and every path
 // interior's place among the path entries; a lane then finds the block its chain entry belongs to by comparing its index with the blocks' boundaries and
 // writes the entry if it stays, and the path interiors of all solved blocks of the read are copied together, 64 entries at a time.  Reads with more than 64
-// syncmers take ec_assemble_read_serial, as in ec_assemble_wave_kernel<1>, which this replaces (OATK_DEBUG_EC_ASSEMBLE_WALK=1 runs that one).
+// syncmers or blocks, and reads with neither a block nor keep_all, take ec_assemble_read_serial.
 // one read by the whole wave (r and everything read through it are wave-uniform)
 __device__ __forceinline__ void ec_assemble_seg_read(const EcAssembleArgs &a, uint64_t r, int lane)
 {
@@ -959,27 +786,7 @@ __global__ __launch_bounds__(256) void ec_assemble_pair_kernel(EcAssembleArgs a)
 }
 
 // ---- update_syncmer_db (syncerr.c:769-814): coverage, forward-strand presence; occurrence lists come from a stable sort ----
-__global__ void ec_fwd_flag_kernel(uint64_t tot, const uint64_t *occ, uint32_t *flag)
-{
-    uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < tot) flag[i] = !(occ[i] & 1ULL);
-}
-__global__ void ec_cov_sorted_kernel(uint64_t tot, const uint32_t *key_sorted, const uint32_t *fwd_incl, uint32_t *cov, uint32_t *fwd)
-{
-    uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= tot) return;
-    const uint32_t k = key_sorted[i];
-    if (i + 1 < tot && key_sorted[i + 1] == k) return;
-    uint64_t lo = 0, hi = i;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (key_sorted[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    cov[k] = (uint32_t) (i - lo + 1);
-    fwd[k] = fwd_incl[i] - (lo? fwd_incl[lo - 1] : 0u);
-}
-
-// The same in one pass (r20): a lane per entry, and a wave finds the runs of equal keys in its 64 entries with two ballots.  The lane at a run's head counts the run's entries
+// Coverage and forward counts in one pass over the sorted pairs (r20): a lane per entry, and a wave finds the runs of equal keys in its 64 entries with two ballots.  The lane at a run's head counts the run's entries
 // and its forward strands in the ballots; a run that begins behind the wave's first lane and ends in front of its last valid one belongs to nobody else and is stored, the
 // (at most two) runs that may go on in a neighbouring wave are added atomically -- cov and fwd are zero before the pass, and sums of integers do not depend on their order
 __global__ __launch_bounds__(256) void ec_cov_runs_kernel(uint64_t tot, const uint32_t *key_sorted, const uint64_t *occ, uint32_t *cov, uint32_t *fwd)

@@ -55,7 +55,7 @@ __global__ void egr_pair_keys_kernel(uint64_t n_reads, const uint64_t *scm_off, 
 // candidate vertex (`other`), and only pairs between two candidates become arcs.  keep[i] = 1 for those.
 // A handle in local ids takes the route on CANDIDATE RANKS at the end of this file (egr_cand_flag_kernel, egr_pair_entry_kernel: packed keys from a lane per
 // chain entry, a sort over 2 B bits).  The kernel below serves handles in global ids (the sharded round, api_multi.inc, exchanges 64-bit keys on global ids)
-// and the switches OATK_DEBUG_EC_LIGHT_PACKED=0 / OATK_DEBUG_EC_LIGHT_PAIRS=0:
+// and the switch OATK_DEBUG_EC_LIGHT_PACKED=0:
 // pair keys and the split are made in one pass, a wave per read (lane j holds entry j of the chain and its left neighbour's comes by a lane
 // shift; reads with more than 64 syncmers are walked by lane 0): a lane-per-read key kernel that strides through the chains plus a pass over its
 // output took 2.4 ms at 2 M reads, this takes 0.85.
@@ -545,12 +545,6 @@ __device__ __forceinline__ uint32_t egr_rank(const uint64_t *bits, const uint32_
 {
     return wpre[v >> 6] + (uint32_t) __builtin_popcountll(bits[v >> 6] & ((1ULL << (v & 63)) - 1ULL));
 }
-// oriented vertex ids v0, v1 of two candidates adjacent on a read -> the canonical key on oriented ranks
-__device__ __forceinline__ uint64_t egr_packed_key(const uint64_t *bits, const uint32_t *wpre, uint32_t B, uint64_t v0, uint64_t v1)
-{
-    const uint64_t o0 = (uint64_t) egr_rank(bits, wpre, v0 >> 1) << 1 | (v0 & 1ULL), o1 = (uint64_t) egr_rank(bits, wpre, v1 >> 1) << 1 | (v1 & 1ULL);
-    return v0 <= v1? o0 << B | o1 : (o1 ^ 1ULL) << B | (o0 ^ 1ULL);
-}
 // the inverse table: cand_id[rank] = vertex
 __global__ __launch_bounds__(256) void egr_cand_id_kernel(uint64_t nv, const uint64_t *bits, const uint32_t *wpre, uint32_t *cand_id)
 {
@@ -640,21 +634,6 @@ __global__ __launch_bounds__(256) void egr_pair_entry_kernel(uint64_t n_reads, c
         gcnt[blockIdx.x] = base;
         if (blockIdx.x == 0) gcnt[gridDim.x] = 0;                          // the scan's last entry is the total
     }
-}
-
-// egr_compact_pairs_kernel with the keys packed on the way (the old three kernels in front of the sort on ranks, OATK_DEBUG_EC_LIGHT_PAIRS=0)
-template <class KeyT>
-__global__ void egr_compact_pack_kernel(uint64_t n, const uint8_t *keep, const uint32_t *pos, const uint64_t *keys, const uint32_t *dist, const uint64_t *bits,
-                                        const uint32_t *wpre, uint32_t B, KeyT *lkeys, uint32_t *ldist, uint64_t *n_out)
-{
-    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t k = keep[i], p = pos[i];
-    if (k) {
-        const uint64_t a = keys[i] >> 32, b = keys[i] & 0xFFFFFFFFULL;    // canonical already: a <= b
-        lkeys[p] = (KeyT) egr_packed_key(bits, wpre, B, a, b), ldist[p] = dist[i];
-    }
-    if (i == n - 1) *n_out = (uint64_t) p + k;
 }
 
 // the distinct packed keys back in the form the rest of the builder reads: a << 32 | b on oriented vertex ids

@@ -247,11 +247,11 @@ class HipSyncasm:
         self._check(self.L.oatk_hip_ec_stats(self.h, st.ctypes.data), "oatk_hip_ec_stats")
         return st
 
-    def cov_runs(self, key_sorted, occ, nv, runs=True):
-        """the refreshed table's (cov, fwd, del) from sorted (key, occurrence) pairs (oatk_hip_debug_cov_runs): in one pass over the runs (what ships) or, runs=False, the three passes it replaced"""
+    def cov_runs(self, key_sorted, occ, nv):
+        """the refreshed table's (cov, fwd, del) from sorted (key, occurrence) pairs, in one pass over the runs (oatk_hip_debug_cov_runs)"""
         key, oc = np.ascontiguousarray(key_sorted, np.uint32), np.ascontiguousarray(occ, np.uint64)
         cov, fwd, dl = np.zeros(nv, np.uint32), np.zeros(nv, np.uint32), np.zeros(nv, np.uint8)
-        self._check(self.L.oatk_hip_debug_cov_runs(self.h, int(bool(runs)), len(key), key.ctypes.data, oc.ctypes.data, nv, cov.ctypes.data, fwd.ctypes.data, dl.ctypes.data), "oatk_hip_debug_cov_runs")
+        self._check(self.L.oatk_hip_debug_cov_runs(self.h, len(key), key.ctypes.data, oc.ctypes.data, nv, cov.ctypes.data, fwd.ctypes.data, dl.ctypes.data), "oatk_hip_debug_cov_runs")
         return cov, fwd, dl
 
     def wf_ed_turns(self, jobs, regroup=True):

@@ -166,12 +166,12 @@ static void hoco_dna(const uint8_t *hoco_s, uint32_t pos, int32_t l, int rev, ch
 }
 
 /* ---- per-read driver, syncerr.c:339-612 ---- */
-void orc_ec_reads(const orc_graph_t *g, const uint8_t *scm_del, const uint64_t *scm_s, int K, double max_edist, uint64_t n_reads,
-                  const uint32_t *hoco_l, const uint8_t *hoco_s, const uint64_t *hoco_byte_off, const uint32_t *n_scm,
-                  const uint64_t *k_mer, const uint32_t *m_pos, const uint64_t *s_mer, orc_ec_out_t *out)
+void orc_ec_reads_blocks(const orc_graph_t *g, const uint8_t *scm_del, const uint64_t *scm_s, int K, double max_edist, uint64_t n_reads,
+                         const uint32_t *hoco_l, const uint8_t *hoco_s, const uint64_t *hoco_byte_off, const uint32_t *n_scm,
+                         const uint64_t *k_mer, const uint32_t *m_pos, const uint64_t *s_mer, orc_ec_out_t *out, orc_ec_blocks_t *blocks)
 {
     uint64_t rd, in_off = 0;
-    v64_t okm = {0, 0, 0}, osm = {0, 0, 0};
+    v64_t okm = {0, 0, 0}, osm = {0, 0, 0}, blk = {0, 0, 0};
     v32_t omp = {0, 0, 0};
     memset(out, 0, sizeof(*out));
     out->n_scm = (uint32_t *) calloc(n_reads + 1, sizeof(uint32_t));
@@ -206,6 +206,11 @@ void orc_ec_reads(const orc_graph_t *g, const uint8_t *scm_del, const uint64_t *
                     if (end >= n) end_utg = UINT64_MAX, l = (int32_t) hoco_l[rd] - (int32_t) beg_pos;
                     else end_utg = (km[end] & ~1ULL) | (mp[end] & 1), l = (int32_t) (mp[end] >> 1) - (int32_t) beg_pos;
                     r = 0;
+                }
+                if (blocks) {
+                    const uint64_t rec[8] = {rd, (uint64_t) beg, (uint64_t) end, beg_utg, end_utg, beg_pos, (uint64_t) (int64_t) l, (uint64_t) r};
+                    int t;
+                    for (t = 0; t < 8; ++t) VPUSH(blk, uint64_t, rec[t]);
                 }
                 int err = EC_FAILURE;
                 if (l >= MIN_ERR_SEQ_LEN) {
@@ -270,13 +275,27 @@ void orc_ec_reads(const orc_graph_t *g, const uint8_t *scm_del, const uint64_t *
     }
     out->tot = okm.n;
     out->k_mer = okm.a, out->m_pos = omp.a, out->s_mer = osm.a;
+    if (blocks) blocks->n = blk.n / 8, blocks->rec = blk.a;
     free(seq.s); free(d.c_seq.s); free(d.opt_seq.s); free(d.c_path.a); free(d.opt_path.a);
+}
+
+void orc_ec_reads(const orc_graph_t *g, const uint8_t *scm_del, const uint64_t *scm_s, int K, double max_edist, uint64_t n_reads,
+                  const uint32_t *hoco_l, const uint8_t *hoco_s, const uint64_t *hoco_byte_off, const uint32_t *n_scm,
+                  const uint64_t *k_mer, const uint32_t *m_pos, const uint64_t *s_mer, orc_ec_out_t *out)
+{
+    orc_ec_reads_blocks(g, scm_del, scm_s, K, max_edist, n_reads, hoco_l, hoco_s, hoco_byte_off, n_scm, k_mer, m_pos, s_mer, out, NULL);
 }
 
 void orc_ec_out_free(orc_ec_out_t *o)
 {
     free(o->n_scm); free(o->k_mer); free(o->m_pos); free(o->s_mer);
     memset(o, 0, sizeof(*o));
+}
+
+void orc_ec_blocks_free(orc_ec_blocks_t *b)
+{
+    free(b->rec);
+    memset(b, 0, sizeof(*b));
 }
 
 /* ---- update_syncmer_db, syncerr.c:769-814: recount coverage, rebuild occurrence lists in (sid, idx) order;

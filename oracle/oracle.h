@@ -182,10 +182,22 @@ typedef struct {
     long stats[11];               /* syncerr.c:76: tail {n, fail, ok, ambiseq?...}, middle {...}, overlapped */
 } orc_ec_out_t;
 
+/* the error blocks the driver visits, in read and chain order: eight words a block -- read, beg, end (chain indices of the left anchor, after its
+ * adjustment, and of the right anchor; end >= n_scm[read] for an open block), beg_utg, end_utg, beg_pos, l, r */
+typedef struct {
+    uint64_t n;
+    uint64_t *rec;                /* [8 n]                                           */
+} orc_ec_blocks_t;
+
 void orc_ec_reads(const orc_graph_t *g, const uint8_t *scm_del, const uint64_t *scm_s, int K, double max_edist, uint64_t n_reads,
                   const uint32_t *hoco_l, const uint8_t *hoco_s, const uint64_t *hoco_byte_off, const uint32_t *n_scm,
                   const uint64_t *k_mer, const uint32_t *m_pos, const uint64_t *s_mer, orc_ec_out_t *out);
+/* the same, and the blocks it visited (`blocks` may be NULL).  An entry point of its own: callers of orc_ec_reads pass fourteen arguments */
+void orc_ec_reads_blocks(const orc_graph_t *g, const uint8_t *scm_del, const uint64_t *scm_s, int K, double max_edist, uint64_t n_reads,
+                         const uint32_t *hoco_l, const uint8_t *hoco_s, const uint64_t *hoco_byte_off, const uint32_t *n_scm,
+                         const uint64_t *k_mer, const uint32_t *m_pos, const uint64_t *s_mer, orc_ec_out_t *out, orc_ec_blocks_t *blocks);
 void orc_ec_out_free(orc_ec_out_t *o);
+void orc_ec_blocks_free(orc_ec_blocks_t *b);
 void orc_update_db(uint64_t n_reads, const uint32_t *n_scm, const uint64_t *k_mer, const uint32_t *m_pos, uint64_t n_syncmers,
                    uint32_t *cov, uint8_t *del, uint64_t *occ_off, uint64_t *occ);
 

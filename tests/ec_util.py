@@ -1,4 +1,5 @@
-"""Helpers for the error-correction parity tests: flatten the reference's EC graph, run the oracle's EC (oracle/ec.c)."""
+"""Helpers for the error-correction parity tests: flatten the reference's EC graph, run the oracle's EC (oracle/ec.c), and a whole round of the
+oracle's on what a device handle holds (oracle_round)."""
 import ctypes as C
 import os
 import re
@@ -21,6 +22,10 @@ class EcOutT(C.Structure):
     _fields_ = [("tot", C.c_uint64), ("updated_reads", C.c_uint64), ("n_scm", C.POINTER(C.c_uint32)),
                 ("k_mer", C.POINTER(C.c_uint64)), ("m_pos", C.POINTER(C.c_uint32)), ("s_mer", C.POINTER(C.c_uint64)),
                 ("stats", C.c_long * 11)]
+
+
+class EcBlocksT(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("rec", C.POINTER(C.c_uint64))]
 
 
 def ref_graph(db, scm, min_k_cov=0, min_a_cov_f=0.0):
@@ -65,22 +70,27 @@ def oracle_find_error_syncmers(G, scm_cov, scm_del, err_mer_c, max_err_c, err_ar
     return L.orc_find_error_syncmers(C.byref(gs), scm_cov.ctypes.data, scm_del.ctypes.data, err_mer_c, max_err_c, err_arc_c, max_arc_f)
 
 
-def oracle_ec_reads(G, scm_del, scm_s, K, max_edist, sr):
-    """sr: flat image of sr_db (hoco_l, hoco_s, n_scm, k_mer (ids), m_pos, s_mer); returns dict with the corrected chains"""
+def oracle_ec_reads(G, scm_del, scm_s, K, max_edist, sr, blocks=False):
+    """sr: flat image of sr_db (hoco_l, hoco_s, n_scm, k_mer (ids), m_pos, s_mer); returns dict with the corrected chains and, with `blocks`, the error
+    blocks the driver visited in read and chain order, one row each: read, beg, end, beg_utg, end_utg, beg_pos, l, r (oracle.h: orc_ec_blocks_t)"""
     L = O.lib()
-    L.orc_ec_reads.argtypes = [C.POINTER(GraphT), C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_uint64] + [C.c_void_p] * 7 + [C.POINTER(EcOutT)]
+    L.orc_ec_reads_blocks.argtypes = [C.POINTER(GraphT), C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_uint64] + [C.c_void_p] * 7 + [C.POINTER(EcOutT), C.POINTER(EcBlocksT)]
     L.orc_ec_out_free.argtypes = [C.POINTER(EcOutT)]
+    L.orc_ec_blocks_free.argtypes = [C.POINTER(EcBlocksT)]
     gs = _graph_struct(G)
     n = len(sr["hoco_l"])
     boff = np.zeros(n + 1, np.uint64)
     boff[1:] = np.cumsum((sr["hoco_l"].astype(np.uint64) + 3) // 4)
-    out = EcOutT()
+    out, blk = EcOutT(), EcBlocksT()
     arrs = [np.ascontiguousarray(sr[k]) for k in ("hoco_l", "hoco_s")] + [boff] + [np.ascontiguousarray(sr[k]) for k in ("n_scm", "k_mer", "m_pos", "s_mer")]
-    L.orc_ec_reads(C.byref(gs), scm_del.ctypes.data, scm_s.ctypes.data, K, max_edist, n, *[a.ctypes.data for a in arrs], C.byref(out))
+    L.orc_ec_reads_blocks(C.byref(gs), scm_del.ctypes.data, scm_s.ctypes.data, K, max_edist, n, *[a.ctypes.data for a in arrs], C.byref(out), C.byref(blk) if blocks else None)
     res = {"n_scm": O._arr(out.n_scm, n, np.uint32), "k_mer": O._arr(out.k_mer, out.tot, np.uint64),
            "m_pos": O._arr(out.m_pos, out.tot, np.uint32), "s_mer": O._arr(out.s_mer, out.tot, np.uint64),
            "stats": np.array(list(out.stats), np.int64)}
     L.orc_ec_out_free(C.byref(out))
+    if blocks:
+        res["blocks"] = O._arr(blk.rec, 8 * blk.n, np.uint64).reshape(-1, 8)
+        L.orc_ec_blocks_free(C.byref(blk))
     return res
 
 
@@ -160,3 +170,30 @@ def oracle_ecgraph(n_scm, k_mer, m_pos, occ_off, occ, K):
            "idx_p": O._arr(g.idx_p, 2 * nv, np.uint64), "idx_n": O._arr(g.idx_n, 2 * nv, np.uint64)}
     L.orc_ecgraph_free(gp)
     return out
+
+
+def oracle_round(hip, off, K, c, max_edist, arc_f, blocks=False):
+    """One error-correction round of the oracle's on the scan + count resident in `hip` (`off`: the reads' offsets in the packed stream the scan was given):
+    its graph (oracle/ecgraph.c), its marks, its corrected chains (oracle/ec.c) and the table made of them, with syncasm's arguments (max_err_c = 10 c,
+    err_arc_c = c).  Returns n_scm, k_mer, m_pos, s_mer, cov, del, occ_off, occ and stats; with `blocks`, oracle_ec_reads' block list too."""
+    got, cnt = hip.fetch_scan(off, with_hash=False), hip.fetch_count()
+    og = oracle_ecgraph(got["n_scm"], cnt["k_id"], got["m_pos"], cnt["occ_off"], cnt["occ"], K)
+    nv, na = og["n_vtx"], og["n_arc"]
+    # vertex strings: the oriented k-mer of each syncmer's first occurrence, one base character per byte
+    first = cnt["occ"][cnt["occ_off"][:-1].astype(np.int64)]
+    scm_off = np.concatenate([[0], np.cumsum(got["n_scm"].astype(np.int64))])
+    hs_off = np.concatenate([[0], np.cumsum((got["hoco_l"].astype(np.int64) + 3) // 4)])
+    rd, idx = (first >> np.uint64(32)).astype(np.int64), ((first >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64)
+    mp = got["m_pos"][scm_off[rd] + idx].astype(np.int64)
+    p = (mp >> 1)[:, None] + np.arange(K)[None, :]
+    codes = (got["hoco_s"][hs_off[rd][:, None] + (p >> 2)] >> (((p & 3) ^ 3) << 1)) & 3
+    codes = np.where((mp & 1)[:, None] != 0, 3 - codes[:, ::-1], codes)
+    G = {"n_vtx": nv, "n_arc": na, "vtx_len": np.full(nv, K, np.uint64), "vtx_del": np.zeros(nv, np.uint8), "vtx_seq_off": np.arange(nv, dtype=np.uint64) * np.uint64(K),
+         "seq": np.ascontiguousarray(np.frombuffer(b"ACGT", np.uint8)[codes].reshape(-1)) if nv else np.zeros(1, np.uint8),
+         "arc_w": og["arc_w"], "arc_ls": og["arc_ls"], "arc_cov": og["arc_cov"], "arc_del": np.zeros(max(na, 1), np.uint8), "idx_p": og["idx_p"], "idx_n": og["idx_n"]}
+    scm_del = np.zeros(nv, np.uint8)
+    oracle_find_error_syncmers(G, cnt["cov"], scm_del, c, 10 * c, c, arc_f)
+    sr = {"hoco_l": got["hoco_l"], "hoco_s": got["hoco_s"], "n_scm": got["n_scm"], "k_mer": cnt["k_id"], "m_pos": got["m_pos"], "s_mer": got["s_mer"]}
+    res = oracle_ec_reads(G, scm_del, cnt["s"], K, max_edist, sr, blocks=blocks)
+    res.update(oracle_update_db(res["n_scm"], res["k_mer"], res["m_pos"], nv))
+    return res

@@ -1,10 +1,10 @@
-"""GPU: the corrected chains built from the blocks' descriptors (ec.hpp: EcSeg, ec_new_n_seg_kernel, ec_assemble_seg_kernel) against the walk they
-replace (ec_new_n_kernel, ec_assemble_wave_kernel<1>, kept behind OATK_DEBUG_EC_ASSEMBLE_WALK=1) and, where oracle/_ref is built, against the compiled
-reference's read_error_correction.
+"""GPU: the corrected chains built from the blocks' descriptors (ec.hpp: EcSeg, ec_new_n_seg_kernel, ec_assemble_pair_kernel / ec_assemble_seg_kernel)
+against a round of the CPU oracle's on the same scan and count (tests/ec_util.py: oracle_round -- oracle/ecgraph.c, oracle/ec.c) and, where oracle/_ref is
+built, against the compiled reference's read_error_correction.
 
 What is compared.  The assembly writes five arrays per chain entry: the three that stay (EC_KMER, EC_MPOS, EC_SMER) and the (syncmer id, occurrence)
-pairs, which the stable sort behind it turns into EC_SCM_OCC / EC_SCM_COV / EC_SCM_OCC_OFF / EC_SCM_DEL before anything can fetch them: two runs whose
-sorted lists and coverages agree wrote the same pairs.  EC_N_SCM is new_n.
+pairs, which the stable sort behind it turns into EC_SCM_OCC / EC_SCM_COV / EC_SCM_OCC_OFF / EC_SCM_DEL before anything can fetch them: a run whose
+sorted lists and coverages are the oracle's wrote the pairs the oracle's chains give.  EC_N_SCM is new_n.
 
 The cases are the places a table of segments can go wrong, and test_cases_are_present holds the data to them, read from the solver's own work list
 and outcomes (EC_BLOCK_WORK, EC_BLOCK_OUT), not from the assembly:
@@ -20,12 +20,11 @@ and outcomes (EC_BLOCK_WORK, EC_BLOCK_OUT), not from the assembly:
   * a read with more than 64 blocks (a substitution every 410 bases over 36 kb; with more than 64 syncmers it takes the serial walk like any long read);
   * a number of reads that is no multiple of the four reads of a workgroup, down to a single wave in the last one;
   * sid0 > 0; a batch assembled by oatk_hip_scan_append."""
-import os
-
 import numpy as np
 import pytest
 
 import adversarial as A
+import ec_util as EU
 import ref_lib as R
 import test_gpu_ec as G
 from oatk_amd import HipSyncasm, pack_reads
@@ -33,7 +32,6 @@ from oatk_amd import HipSyncasm, pack_reads
 pytestmark = pytest.mark.gpu
 
 K, S, C_MIN, EDIST, ARC_F = 101, 11, 4, 0.02, 0.35
-SWITCH = "OATK_DEBUG_EC_ASSEMBLE_WALK"
 OUT = ["EC_N_SCM", "EC_SCM_OFF", "EC_KMER", "EC_MPOS", "EC_SMER", "EC_SCM_COV", "EC_SCM_DEL", "EC_SCM_OCC_OFF", "EC_SCM_OCC"]
 
 
@@ -90,23 +88,25 @@ def case_reads(hip):
     return reads
 
 
-def correct(h, walk):
-    """one correction on the resident scan + count + graph, by the walk or from the descriptors; what it left"""
-    old = os.environ.get(SWITCH)
-    os.environ[SWITCH] = "1" if walk else "0"
-    try:
-        st = h.ec(EDIST, C_MIN, ARC_F)
-    finally:
-        if old is None:
-            del os.environ[SWITCH]
-        else:
-            os.environ[SWITCH] = old
+def correct(h):
+    """one correction on the resident scan + count + graph; what it left"""
+    st = h.ec(EDIST, C_MIN, ARC_F)
     got = {k: h.fetch(k) for k in OUT}
     got["stats"] = np.array(st[:11], np.uint64)
     return got
 
 
+def oracle(h, off, blocks=False):
+    """the oracle's round on the scan + count resident in `h`, under the names of `correct`'s arrays; with `blocks`, also the list of the blocks it visited"""
+    o = EU.oracle_round(h, off, K, C_MIN, EDIST, ARC_F, blocks=blocks)
+    scm_off = np.concatenate([[0], np.cumsum(o["n_scm"].astype(np.uint64))]).astype(np.uint64)
+    res = {"EC_N_SCM": o["n_scm"], "EC_SCM_OFF": scm_off, "EC_KMER": o["k_mer"], "EC_MPOS": o["m_pos"], "EC_SMER": o["s_mer"], "EC_SCM_COV": o["cov"],
+           "EC_SCM_DEL": o["del"], "EC_SCM_OCC_OFF": o["occ_off"], "EC_SCM_OCC": o["occ"], "stats": o["stats"].astype(np.uint64)}
+    return (res, o["blocks"]) if blocks else res
+
+
 def assert_same(a, b, what):
+    assert sorted(a) == sorted(b), what
     for k in a:
         assert np.array_equal(a[k], b[k]), (what, k)
 
@@ -115,34 +115,35 @@ def assert_same(a, b, what):
 def runs(hip):
     reads = case_reads(hip)
     ref = None
+    seq, off, lens = pack_reads(reads)
     if R.available():
         from test_gpu_dropin import device_dbs
         db, scm = device_dbs(hip, reads, K, S)            # the device's scan + count, resident, and as the reference's structs
     else:
-        seq, off, lens = pack_reads(reads)
         hip.scan_host(seq, off, lens, K, S)
         hip.count()
     n_scm = hip.fetch("N_SCM")
     hip.ec_graph()
-    walk = correct(hip, True)
-    seg = correct(hip, False)
+    seg = correct(hip)
     work = hip.fetch("EC_BLOCK_WORK").reshape(-1, 12)
     out = hip.fetch("EC_BLOCK_OUT").reshape(-1, 12)
+    orc, blocks = oracle(hip, off, blocks=True)
     if R.available():
         from test_gpu_ec_routes import reference_run
         ref = reference_run(db, scm, K, S, EDIST, C_MIN, 10 * C_MIN, C_MIN, ARC_F)
-    return {"reads": reads, "n_scm": n_scm, "walk": walk, "seg": seg, "work": work, "out": out, "ref": ref}
+    return {"reads": reads, "n_scm": n_scm, "seg": seg, "oracle": orc, "blocks": blocks, "work": work, "out": out, "ref": ref}
 
 
 def test_descriptors_give_what_the_walk_gives(runs):
-    assert_same(runs["walk"], runs["seg"], "descriptors against the walk")
+    """(the walk is the oracle's: oracle/ec.c walks every chain as syncerr.c does)"""
+    assert_same(runs["oracle"], runs["seg"], "descriptors against the oracle's walk")
     assert int(runs["seg"]["EC_N_SCM"].sum()) == len(runs["seg"]["EC_KMER"]) > 0
 
 
 @pytest.mark.skipif(not R.available(), reason="oracle/_ref not built")
 def test_descriptors_give_what_the_reference_gives(runs):
     sr1, sc1, summary, marks = runs["ref"]
-    for name, got in (("walk", runs["walk"]), ("seg", runs["seg"])):
+    for name, got in (("seg", runs["seg"]),):
         assert np.array_equal(got["EC_N_SCM"], sr1["n_scm"]), name
         assert np.array_equal(got["EC_KMER"], sr1["k_mer"]), name
         assert np.array_equal(got["EC_MPOS"], sr1["m_pos"]), name
@@ -202,7 +203,7 @@ def test_last_workgroup_partly_filled(hip, drop):
     hip.scan_host(seq, off, lens, K, S)
     hip.count()
     hip.ec_graph()
-    assert_same(correct(hip, True), correct(hip, False), "drop %d" % drop)
+    assert_same(oracle(hip, off), correct(hip), "drop %d" % drop)
 
 
 def test_sid0_above_zero(hip, runs):
@@ -212,10 +213,9 @@ def test_sid0_above_zero(hip, runs):
     hip.scan_host(seq, off, lens, K, S, sid0=sid0)
     hip.count()
     hip.ec_graph()
-    walk, seg = correct(hip, True), correct(hip, False)
-    assert_same(walk, seg, "sid0")
-    # the same chains as at sid0 = 0, the occurrences' read ids moved by sid0
-    for k in ("EC_N_SCM", "EC_KMER", "EC_MPOS", "EC_SMER", "EC_SCM_COV"):
+    seg = correct(hip)
+    # the same chains as at sid0 = 0 (which test_descriptors_give_what_the_walk_gives holds to the oracle), the occurrences' read ids moved by sid0
+    for k in ("EC_N_SCM", "EC_SCM_OFF", "EC_KMER", "EC_MPOS", "EC_SMER", "EC_SCM_COV", "EC_SCM_DEL", "EC_SCM_OCC_OFF", "stats"):
         assert np.array_equal(seg[k], runs["seg"][k]), k
     assert np.array_equal(seg["EC_SCM_OCC"], runs["seg"]["EC_SCM_OCC"] + (np.uint64(sid0) << np.uint64(32)))
 
@@ -232,8 +232,8 @@ def test_appended_batch(hip, runs):
             main.scan_append(piece)
         main.count()
         main.ec_graph()
-        walk, seg = correct(main, True), correct(main, False)
-        assert_same(walk, seg, "appended")
+        seg = correct(main)
+        assert_same(runs["oracle"], seg, "appended against the oracle's round on these reads")
         assert_same(seg, runs["seg"], "appended against one scan")
     finally:
         piece.close()

@@ -1,7 +1,7 @@
 """GPU: the corrected chains with two reads to a wave (oatk_amd/csrc/ec.hpp: ec_assemble_pair_kernel; r20) against a wave per read
-(OATK_DEBUG_EC_ASSEMBLE_PAIRS=0: ec_assemble_seg_kernel) and against the walk (OATK_DEBUG_EC_ASSEMBLE_WALK=1), compared as tests/test_gpu_ec_assemble.py
-compares them: EC_N_SCM, EC_KMER, EC_MPOS, EC_SMER and, for the (syncmer id, occurrence) pairs, the sorted lists and coverages made of them; where oracle/_ref
-is built, against the compiled reference too.
+(OATK_DEBUG_EC_ASSEMBLE_PAIRS=0: ec_assemble_seg_kernel) and against a round of the CPU oracle's on the same scan and count (tests/ec_util.py: oracle_round),
+compared as tests/test_gpu_ec_assemble.py compares them: EC_N_SCM, EC_KMER, EC_MPOS, EC_SMER and, for the (syncmer id, occurrence) pairs, the sorted lists
+and coverages made of them; where oracle/_ref is built, against the compiled reference too.
 
 Wave w takes reads 2 w and 2 w + 1, in halves of 32 lanes when both have at most 32 chain entries and 32 blocks, one after the other otherwise.  The reads
 are built the way that module builds its own (same haplotypes, K, S): 440 sampled reads of about 26 syncmers with errors and bubbles (solved and unsolved
@@ -22,7 +22,7 @@ from oatk_amd import pack_reads
 pytestmark = pytest.mark.gpu
 
 K, S, C_MIN = AS.K, AS.S, AS.C_MIN
-PAIRS, WALK = "OATK_DEBUG_EC_ASSEMBLE_PAIRS", AS.SWITCH
+PAIRS = "OATK_DEBUG_EC_ASSEMBLE_PAIRS"
 LENGTHS = (0, 1, 2, 31, 32, 33, 63, 64, 65)
 _reads = {}
 
@@ -58,17 +58,15 @@ def case_reads(hip):
 
 
 def correct(hip, env):
-    old = {k: os.environ.get(k) for k in (PAIRS, WALK)}
-    for k in (PAIRS, WALK):
-        os.environ.pop(k, None)
+    old = os.environ.get(PAIRS)
+    os.environ.pop(PAIRS, None)
     os.environ.update(env)
     try:
         st = hip.ec(AS.EDIST, C_MIN, AS.ARC_F)
     finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
+        os.environ.pop(PAIRS, None)
+        if old is not None:
+            os.environ[PAIRS] = old
     got = {k: hip.fetch(k) for k in AS.OUT}
     got["stats"] = np.array(st[:11], np.uint64)
     return got
@@ -78,29 +76,29 @@ def correct(hip, env):
 def runs(hip):
     reads = case_reads(hip)
     ref = None
+    seq, off, lens = pack_reads(reads)
     if R.available():
         from test_gpu_dropin import device_dbs
         db, scm = device_dbs(hip, reads, K, S)
     else:
-        seq, off, lens = pack_reads(reads)
         hip.scan_host(seq, off, lens, K, S)
         hip.count()
     n_scm = hip.fetch("N_SCM")
     hip.ec_graph()
     pairs = correct(hip, {})
     single = correct(hip, {PAIRS: "0"})
-    walk = correct(hip, {WALK: "1"})
+    orc = AS.oracle(hip, off)
     work = hip.fetch("EC_BLOCK_WORK").reshape(-1, 12)
     out = hip.fetch("EC_BLOCK_OUT").reshape(-1, 12)
     if R.available():
         from test_gpu_ec_routes import reference_run
         ref = reference_run(db, scm, K, S, AS.EDIST, C_MIN, 10 * C_MIN, C_MIN, AS.ARC_F)
-    return {"reads": reads, "n_scm": n_scm, "pairs": pairs, "single": single, "walk": walk, "work": work, "out": out, "ref": ref}
+    return {"reads": reads, "n_scm": n_scm, "pairs": pairs, "single": single, "oracle": orc, "work": work, "out": out, "ref": ref}
 
 
 def test_two_reads_to_a_wave_give_what_one_gives(runs):
     AS.assert_same(runs["single"], runs["pairs"], "two reads to a wave against one")
-    AS.assert_same(runs["walk"], runs["pairs"], "two reads to a wave against the walk")
+    AS.assert_same(runs["oracle"], runs["pairs"], "two reads to a wave against the oracle's round")
     assert int(runs["pairs"]["EC_N_SCM"].sum()) == len(runs["pairs"]["EC_KMER"]) > 0
 
 

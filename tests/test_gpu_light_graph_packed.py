@@ -1,8 +1,8 @@
 """GPU: the light EC graph on candidate ranks (ecgraph.hpp: packed pair keys, the pairs by a lane per chain entry) against the route it replaces.
 
 Every comparison takes the graph arrays (OATK_BUF_EG_*, the flags of OATK_BUF_EG_OTHER among them), the results of hip.ec(...) on that graph and its
-statistics, and holds them between OATK_DEBUG_EC_LIGHT_PACKED=0 (64-bit keys on vertex ids), the packed sort behind the old pair kernels
-(OATK_DEBUG_EC_LIGHT_PAIRS=0) and both steps, with the key width the candidates give and with OATK_DEBUG_EC_LIGHT_KEYBITS=64.  Where the full graph is
+statistics, and holds them between OATK_DEBUG_EC_LIGHT_PACKED=0 (64-bit keys on vertex ids) and the route on candidate ranks, with the key width the
+candidates give and with OATK_DEBUG_EC_LIGHT_KEYBITS=64.  Where the full graph is
 built, the arcs are also held against the full graph's arcs between candidates, as test_gpu_light_graph does: test_gpu_ec.py holds the full graph to the
 compiled reference."""
 import ctypes as C
@@ -19,15 +19,14 @@ from oatk_amd import OatkHipError, pack_reads
 pytestmark = pytest.mark.gpu
 
 EG_OTHER = 127
-# name, OATK_DEBUG_EC_LIGHT_PACKED, _PAIRS, _KEYBITS
-ROUTES = [("old", "0", "1", "0"), ("sort", "1", "0", "0"), ("sort-64", "1", "0", "64"), ("both", "1", "1", "0"), ("both-64", "1", "1", "64")]
+# name, OATK_DEBUG_EC_LIGHT_PACKED, _KEYBITS
+ROUTES = [("old", "0", "0"), ("both", "1", "0"), ("both-64", "1", "64")]
 ARCS = ("arc_v", "arc_w", "arc_ls", "arc_cov", "arc_comp")
 
 
 def set_route(monkeypatch, route):
-    _, packed, pairs, bits = route
+    _, packed, bits = route
     monkeypatch.setenv("OATK_DEBUG_EC_LIGHT_PACKED", packed)
-    monkeypatch.setenv("OATK_DEBUG_EC_LIGHT_PAIRS", pairs)
     monkeypatch.setenv("OATK_DEBUG_EC_LIGHT_KEYBITS", bits)
 
 
