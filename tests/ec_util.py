@@ -1,5 +1,5 @@
 """Helpers for the error-correction parity tests: flatten the reference's EC graph, run the oracle's EC (oracle/ec.c), and a whole round of the
-oracle's on what a device handle holds (oracle_round)."""
+oracle's on what a device handle holds (oracle_round) or on a scan and count given as dicts (oracle_round_on)."""
 import ctypes as C
 import os
 import re
@@ -176,7 +176,12 @@ def oracle_round(hip, off, K, c, max_edist, arc_f, blocks=False):
     """One error-correction round of the oracle's on the scan + count resident in `hip` (`off`: the reads' offsets in the packed stream the scan was given):
     its graph (oracle/ecgraph.c), its marks, its corrected chains (oracle/ec.c) and the table made of them, with syncasm's arguments (max_err_c = 10 c,
     err_arc_c = c).  Returns n_scm, k_mer, m_pos, s_mer, cov, del, occ_off, occ and stats; with `blocks`, oracle_ec_reads' block list too."""
-    got, cnt = hip.fetch_scan(off, with_hash=False), hip.fetch_count()
+    return oracle_round_on(hip.fetch_scan(off, with_hash=False), hip.fetch_count(), K, c, max_edist, arc_f, blocks)
+
+
+def oracle_round_on(got, cnt, K, c, max_edist, arc_f, blocks=False):
+    """oracle_round on a scan (hoco_l, hoco_s, n_scm, m_pos, s_mer) and a count (k_id, cov, s, occ_off, occ) given as dicts: a device handle's, or the
+    oracle's own (oracle_lib.scan_and_count), which needs no device"""
     og = oracle_ecgraph(got["n_scm"], cnt["k_id"], got["m_pos"], cnt["occ_off"], cnt["occ"], K)
     nv, na = og["n_vtx"], og["n_arc"]
     # vertex strings: the oriented k-mer of each syncmer's first occurrence, one base character per byte

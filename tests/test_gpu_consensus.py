@@ -17,7 +17,9 @@ def device_consensus(hip, min_cov):
     return {k: hip.fetch("CONS_" + k) for k in ("SEL", "SLOT", "RL", "MSEQ", "FIRST", "TOT")}
 
 
-def compare_with_oracle(hip, reads, K, S, after_ec, min_cov, c_ec=4):
+def load_reads(hip, reads, K, S, after_ec, c_ec=4):
+    """scan, count and, with after_ec, one correction round on the handle; returns what the consensus is then made of, as host arrays: the flat
+    reads (with the chains' k_mer and m_pos), and cov, occ, occ_off, del of the table"""
     seq, off, lens = pack_reads(reads)
     hip.scan_host(seq, off, lens, K, S)
     hip.count()
@@ -35,6 +37,11 @@ def compare_with_oracle(hip, reads, K, S, after_ec, min_cov, c_ec=4):
         sr = dict(sr)
         sr["k_mer"] = c["k_id"]
         cov, occ, occ_off, dele = c["cov"], c["occ"], c["occ_off"], np.zeros(len(c["cov"]), np.uint8)
+    return sr, cov, occ, occ_off, dele
+
+
+def check_consensus(hip, K, min_cov, sr, cov, occ, occ_off, dele):
+    """oatk_hip_consensus(min_cov) on what load_reads left resident: every CONS_* array of every selected syncmer against the oracle"""
     D = device_consensus(hip, min_cov)
     want_sel = np.nonzero((dele == 0) & (cov >= max(min_cov, 1)))[0].astype(np.uint32)
     assert np.array_equal(D["SEL"], want_sel) and len(want_sel) > 0
@@ -54,6 +61,10 @@ def compare_with_oracle(hip, reads, K, S, after_ec, min_cov, c_ec=4):
             assert np.array_equal(rl[s_i], want), i
             n_long += int(tot.max() // m >= 255)
     return D, view, keep, n_long
+
+
+def compare_with_oracle(hip, reads, K, S, after_ec, min_cov, c_ec=4):
+    return check_consensus(hip, K, min_cov, *load_reads(hip, reads, K, S, after_ec, c_ec))
 
 
 @pytest.mark.parametrize("K,S,after_ec", [(101, 11, False), (101, 11, True), (301, 21, True), (1001, 31, False)])
