@@ -18,6 +18,7 @@
 #include <unistd.h>
 #include <rccl/rccl.h>
 #include <rocprim/device/device_select.hpp>
+#include <initializer_list>
 
 namespace {
 
@@ -126,7 +127,7 @@ struct MultiState {
     DevBuf keys_all, dist_all, need, need_all, need_srt, uni, owner, mine, kout, krev, ids_all, rev_all, km_all, lack, ids_i, rev_i, km_i;
     DevBuf ec_cov, ec_fwd, ec_del, st64, loc_c, loc_f, rcv_c, rcv_f, pc;
     DevBuf x[64];                        // the graph hand-off (api_multi_tail.inc: MX_*)
-    uint64_t n_global = 0, n_owned = 0, n_cand = 0, table_occ = 0, gkid_n = 0;
+    uint64_t n_global = 0, n_owned = 0, table_occ = 0, gkid_n = 0;
     int rank = 0, table_root = -1;
     bool merged = false, ec_done = false;
 };
@@ -159,6 +160,11 @@ static int multi_buffer(oatk_hip_ctx *ctx, int which, const void **d_ptr, uint64
 // ---------------------------------------------------------------- the primitives ----------------------------------------------------------------
 
 #define MENSURE(buf, bytes) ENSURE_IN(m, "multi.", buf, bytes)
+// MultiState::num, in 64-bit numbers: the all-gather of comm_allgather_vec (up to 64 ranks' 64 numbers, then this rank's own), behind it the counters rocPRIM writes
+// (mg_select_u32, the distinct ids of ec_step2_kmers, the byte-wide select of ec_import_kmers)
+enum { NUM_GATHER_END = 64 * 65, NUM_SELECT = NUM_GATHER_END + 8, NUM_UNIQUE, NUM_SELECT8, NUM_COUNT_ = NUM_GATHER_END + 64 };
+static_assert(NUM_SELECT8 < NUM_COUNT_, "the counters of MultiState::num lie inside the buffer");
+#define NUM_ENSURE() MENSURE(num, NUM_COUNT_ * 8)
 #define NCK(call)                                                                                  \
     do {                                                                                           \
         ncclResult_t r_ = (call);                                                                  \
@@ -243,8 +249,8 @@ static int comm_allgather_vec(oatk_hip_ctx *ctx, oatk_comm *c, const uint64_t *m
         GWAIT(c);
         return OATK_OK;
     }
-    MENSURE(num, (64 * 65 + 64) * 8);
-    uint64_t *d_all = m->num.as<uint64_t>(), *d_mine = d_all + (size_t) c->n * k;
+    NUM_ENSURE();
+    uint64_t *d_all = m->num.as<uint64_t>(), *d_mine = d_all + (size_t) c->n * k;        // (at most 64 * 64 + 64 = NUM_GATHER_END numbers)
     CK(hipMemcpyAsync(d_mine, mine, (size_t) k * 8, hipMemcpyHostToDevice, ctx->stream));
     NCK(g_rccl.AllGather(d_mine, d_all, (size_t) k, ncclUint64, c->nccl, ctx->stream));
     CK(hipMemcpyAsync(all, d_all, (size_t) c->n * k * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -303,94 +309,83 @@ static int comm_allreduce(oatk_hip_ctx *ctx, oatk_comm *c, void *d_buf, uint64_t
     return comm_wait(ctx, c);
 }
 
-// every rank's variable-length array of `width`-byte items, concatenated in rank order (the buffer is grown as needed); *n_all = items
-static int comm_gather_items(oatk_hip_ctx *ctx, oatk_comm *c, const void *d_src, uint64_t n_mine, uint32_t width, DevBuf &dst, uint64_t *n_all)
-{
-    uint64_t cnt[64], bytes[64], tot = 0;
-    { int rc = comm_allgather_u64(ctx, c, n_mine, cnt); if (rc) return rc; }
-    for (int r = 0; r < c->n; ++r) bytes[r] = cnt[r] * width, tot += cnt[r];
-    if (!dst.ensure(tot * width + 64, ctx->stream)) { ctx->err = "hipMalloc failed (gather)"; return OATK_E_NOMEM; }
-    *n_all = tot;
-    return comm_allgatherv(ctx, c, d_src, bytes, dst.p);
-}
-
-// Several arrays with the same number of items per rank (a struct of arrays): ONE exchange of counts and ONE collective for all of them -- what the per-step latency budget
-// of eight GPUs is spent on is the number of collectives, not their bytes (DESIGN.md 9.2).  cnt_extra: one more number per rank travels with the counts (a verdict, see
-// ec_sharded_impl), extra_all[r] receives it.
-static int comm_gather_items_multi(oatk_hip_ctx *ctx, oatk_comm *c, int k, const void *const *d_src, const uint32_t *width, DevBuf *const *dst, uint64_t n_mine, uint64_t *n_all,
-                                   uint64_t cnt_extra = 0, uint64_t *extra_all = nullptr)
+// Every rank's variable-length arrays of items, concatenated in rank order (the buffers are grown as needed); *n_all = items.  Several arrays with the same number of
+// items per rank (a struct of arrays) take ONE exchange of counts and ONE collective for all of them -- what the per-step latency budget
+// of eight GPUs is spent on is the number of collectives, not their bytes (DESIGN.md 9.2).  A column is one of the arrays: {this rank's items, where everybody's land,
+// bytes per item}.  cnt_extra: one more number per rank travels with the counts (a verdict, see ec_step2_kmers), extra_all[r] receives it.
+struct GatherCol { const void *src; DevBuf *dst; uint32_t width; };
+static int comm_gather_cols(oatk_hip_ctx *ctx, oatk_comm *c, std::initializer_list<GatherCol> cols, uint64_t n_mine, uint64_t *n_all, uint64_t cnt_extra = 0,
+                            uint64_t *extra_all = nullptr)
 {
     uint64_t mine2[2] = {n_mine, cnt_extra}, all2[128], cnt[64], tot = 0;
     { int rc = comm_allgather_vec(ctx, c, mine2, extra_all? 2 : 1, all2); if (rc) return rc; }
     for (int r = 0; r < c->n; ++r) { cnt[r] = all2[extra_all? 2 * r : r]; if (extra_all) extra_all[r] = all2[2 * r + 1]; tot += cnt[r]; }
-    for (int i = 0; i < k; ++i)
-        if (!dst[i]->ensure(tot * width[i] + 64, ctx->stream)) { ctx->err = "hipMalloc failed (gather)"; return OATK_E_NOMEM; }
+    for (const GatherCol &col : cols)
+        if (!col.dst->ensure(tot * col.width + 64, ctx->stream)) { ctx->err = "hipMalloc failed (gather)"; return OATK_E_NOMEM; }
     *n_all = tot;
     if (extra_all) for (int r = 0; r < c->n; ++r) if (extra_all[r]) return OATK_OK;      // (somebody refuses: nobody enters the data's collective)
     if (c->grp) {
         uint64_t bytes[64];
-        for (int i = 0; i < k; ++i) {
-            for (int r = 0; r < c->n; ++r) bytes[r] = cnt[r] * width[i];
-            int rc = comm_allgatherv(ctx, c, d_src[i], bytes, dst[i]->p);
+        for (const GatherCol &col : cols) {
+            for (int r = 0; r < c->n; ++r) bytes[r] = cnt[r] * col.width;
+            int rc = comm_allgatherv(ctx, c, col.src, bytes, col.dst->p);
             if (rc) return rc;
-            if (i) c->traffic[2] -= 1, c->entered -= 1;       // (counted as the one collective it is on the wire)
+            if (&col != cols.begin()) c->traffic[2] -= 1, c->entered -= 1;       // (counted as the one collective it is on the wire)
         }
         return OATK_OK;
     }
     { int rc = comm_enter(ctx, c); if (rc) return rc; }
     c->traffic[2] += 1;
     NCK(g_rccl.GroupStart());
-    for (int i = 0; i < k; ++i) {
+    for (const GatherCol &col : cols) {
         uint64_t off = 0;
-        c->traffic[3] += cnt[c->rank] * width[i];
-        for (int r = 0; r < c->n; off += cnt[r] * width[i], ++r)
-            if (cnt[r]) NCK(g_rccl.Broadcast(r == c->rank? d_src[i] : (const void *) ((uint8_t *) dst[i]->p + off), (uint8_t *) dst[i]->p + off, cnt[r] * width[i], ncclUint8, r, c->nccl, ctx->stream));
+        uint8_t *to = (uint8_t *) col.dst->p;
+        c->traffic[3] += cnt[c->rank] * col.width;
+        for (int r = 0; r < c->n; off += cnt[r] * col.width, ++r)
+            if (cnt[r]) NCK(g_rccl.Broadcast(r == c->rank? col.src : (const void *) (to + off), to + off, cnt[r] * col.width, ncclUint8, r, c->nccl, ctx->stream));
     }
     NCK(g_rccl.GroupEnd());
     return comm_wait(ctx, c);
 }
 
-// The personalised exchange: items [out_off[r], out_off[r + 1]) of d_out go to rank r, and what rank r sends here lands at
-// [in_off[r], in_off[r + 1]) of d_in (the two offset arrays agree across the ranks: comm_plan).  The same plan serves both directions.
-static int comm_exchange_multi(oatk_hip_ctx *ctx, oatk_comm *c, int k, const void *const *d_out, const uint64_t *out_off, void *const *d_in, const uint64_t *in_off, const uint32_t *width)
+// The personalised exchange: items [out_off[r], out_off[r + 1]) of a column's `out` go to rank r, and what rank r sends here lands at
+// [in_off[r], in_off[r + 1]) of its `in` (the two offset arrays agree across the ranks: comm_plan).  The same plan serves both directions and every column.
+struct XchgCol { const void *out; void *in; uint32_t width; };
+static int comm_exchange_cols(oatk_hip_ctx *ctx, oatk_comm *c, std::initializer_list<XchgCol> cols, const uint64_t *out_off, const uint64_t *in_off)
 {
     const int me = c->rank;
     { int rc = comm_enter(ctx, c); if (rc) return rc; }
     c->traffic[6] += 1;
-    for (int i = 0; i < k; ++i) c->traffic[7] += (out_off[c->n] - out_off[0]) * width[i];
+    for (const XchgCol &col : cols) c->traffic[7] += (out_off[c->n] - out_off[0]) * col.width;
     if (c->grp) {
-        for (int i = 0; i < k; ++i) {
-            c->grp->ptr[me] = d_out[i];
+        for (const XchgCol &col : cols) {
+            c->grp->ptr[me] = col.out;
             for (int r = 0; r <= c->n; ++r) c->grp->off[me][r] = out_off[r];
             CK(hipStreamSynchronize(ctx->stream));
             GWAIT(c);
             for (int r = 0; r < c->n; ++r) {
                 const uint64_t cnt = in_off[r + 1] - in_off[r];
-                if (cnt) CK(hipMemcpyAsync((uint8_t *) d_in[i] + in_off[r] * width[i], (const uint8_t *) c->grp->ptr[r] + c->grp->off[r][me] * width[i], cnt * width[i], hipMemcpyDeviceToDevice, ctx->stream));
+                if (cnt) CK(hipMemcpyAsync((uint8_t *) col.in + in_off[r] * col.width, (const uint8_t *) c->grp->ptr[r] + c->grp->off[r][me] * col.width, cnt * col.width, hipMemcpyDeviceToDevice, ctx->stream));
             }
             CK(hipStreamSynchronize(ctx->stream));
             GWAIT(c);
         }
         return OATK_OK;
     }
-    for (int i = 0; i < k; ++i) {   // a rank's own range does not go through the network
+    for (const XchgCol &col : cols) {   // a rank's own range does not go through the network
         const uint64_t cnt = in_off[me + 1] - in_off[me];
-        if (cnt) CK(hipMemcpyAsync((uint8_t *) d_in[i] + in_off[me] * width[i], (const uint8_t *) d_out[i] + out_off[me] * width[i], cnt * width[i], hipMemcpyDeviceToDevice, ctx->stream));
+        if (cnt) CK(hipMemcpyAsync((uint8_t *) col.in + in_off[me] * col.width, (const uint8_t *) col.out + out_off[me] * col.width, cnt * col.width, hipMemcpyDeviceToDevice, ctx->stream));
     }
     NCK(g_rccl.GroupStart());
-    for (int i = 0; i < k; ++i)
+    for (const XchgCol &col : cols)
         for (int r = 0; r < c->n; ++r) {
             if (r == me) continue;
             const uint64_t so = out_off[r + 1] - out_off[r], si = in_off[r + 1] - in_off[r];
-            if (so) NCK(g_rccl.Send((const uint8_t *) d_out[i] + out_off[r] * width[i], so * width[i], ncclUint8, r, c->nccl, ctx->stream));
-            if (si) NCK(g_rccl.Recv((uint8_t *) d_in[i] + in_off[r] * width[i], si * width[i], ncclUint8, r, c->nccl, ctx->stream));
+            if (so) NCK(g_rccl.Send((const uint8_t *) col.out + out_off[r] * col.width, so * col.width, ncclUint8, r, c->nccl, ctx->stream));
+            if (si) NCK(g_rccl.Recv((uint8_t *) col.in + in_off[r] * col.width, si * col.width, ncclUint8, r, c->nccl, ctx->stream));
         }
     NCK(g_rccl.GroupEnd());
     return comm_wait(ctx, c);
-}
-static int comm_exchange(oatk_hip_ctx *ctx, oatk_comm *c, const void *d_out, const uint64_t *out_off, void *d_in, const uint64_t *in_off, uint32_t width)
-{
-    return comm_exchange_multi(ctx, c, 1, &d_out, out_off, &d_in, in_off, &width);
 }
 // from what this rank sends each peer (send_off, n + 1 entries) to where each peer's part lands (recv_off)
 static int comm_plan(oatk_hip_ctx *ctx, oatk_comm *c, const uint64_t *send_off, uint64_t *recv_off, uint64_t *largest_recv = nullptr)
@@ -645,24 +640,19 @@ __global__ void mg_l2g_kernel(const uint64_t *back, uint64_t nl, const uint64_t 
 
 static int mg_select_u32(oatk_hip_ctx *ctx, MultiState *m, const uint32_t *in, const uint8_t *flag, uint64_t n, DevBuf &out, uint64_t *n_out);
 
-static int merge_counts_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint64_t *n_global)
+// The host ends of the table merge's asynchronous copies: they live in merge_counts_impl's frame, for the whole call.
+struct MergeHost { uint64_t key[65] = {0}, req_off[65] = {0}, asked_off[65] = {0}; };
+
+// 1. what this shard owes each owner: ranges of its own (hash-sorted) table
+static int mg_send_ranges(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, uint64_t *key)
 {
-    { int rc0 = comm_check(ctx, c, "oatk_hip_merge_counts"); if (rc0) return rc0; }
-    if (!ctx->counted) { ctx->err = "oatk_hip_merge_counts needs a resident scan + count"; return OATK_E_STATE; }
-    CK(hipSetDevice(ctx->device));
-    if (!ctx->multi) ctx->multi = new MultiState();
-    MultiState *m = ctx->multi;
-    m->merged = m->ec_done = false, m->rank = c->rank, m->table_root = -1;
     const uint64_t nl = ctx->n_scm_total;
-    const int n = c->n, me = c->rank;
+    const int n = c->n;
     int rc;
     MENSURE(bad, 64); MENSURE(plan_d, 130 * 8);
     CK(hipMemsetAsync(m->bad.p, 0, 64, ctx->stream));
-
-    // 1. what this shard owes each owner: ranges of its own (hash-sorted) table
-    uint64_t key[65] = {0};              // (function scope: the copy below is asynchronous)
     for (int r = 0; r < n; ++r) key[r] = (uint64_t) ((((unsigned __int128) (uint64_t) r << 64) + (uint64_t) (n - 1)) / (uint64_t) n);      // ceil(r 2^64 / n) < 2^64
-    CK(hipMemcpyAsync(m->plan_d.as<uint64_t>() + 65, key, sizeof(key), hipMemcpyHostToDevice, ctx->stream));
+    CK(hipMemcpyAsync(m->plan_d.as<uint64_t>() + 65, key, 65 * 8, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(mg_bounds_kernel, dim3(1), dim3(128), 0, ctx->stream, ctx->scm_h.as<uint64_t>(), nl, n, m->plan_d.as<uint64_t>());
     CK(hipMemcpyAsync(m->send_off, m->plan_d.p, (size_t) (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
@@ -675,22 +665,23 @@ static int merge_counts_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint64_t *n_global
         return OATK_E_ARG;
     }
     MENSURE(recv_h, (nr + 1) * 8); MENSURE(recv_s, (nr + 1) * 8); MENSURE(recv_cov, (nr + 1) * 4);
-    {   // hashes, s-mers and coverage along the same routes: one exchange
-        const void *out3[3] = {ctx->scm_h.p, ctx->scm_s.p, ctx->scm_cov.p};
-        void *in3[3] = {m->recv_h.p, m->recv_s.p, m->recv_cov.p};
-        const uint32_t w3[3] = {8, 8, 4};
-        if ((rc = comm_exchange_multi(ctx, c, 3, out3, m->send_off, in3, m->recv_off, w3)) != OATK_OK) return rc;
-    }
+    // hashes, s-mers and coverage along the same routes: one exchange
+    return comm_exchange_cols(ctx, c, {{ctx->scm_h.p, m->recv_h.p, 8}, {ctx->scm_s.p, m->recv_s.p, 8}, {ctx->scm_cov.p, m->recv_cov.p, 4}}, m->send_off, m->recv_off);
+}
 
-    // 2. the owner's range: sorted by hash; entries that share a hash are compared k-mer by k-mer (their shards send the k-mers: a true syncmer is
-    //    on every shard, a sequencing error on one, so this is thousands of k-mers) and clustered in first-seen order -- the reference's ids for
-    //    the union of the shards, hash collisions included; coverage summed per k-mer
-    uint64_t n_own = 0;
+// 2. the owner's range: sorted by hash; entries that share a hash are compared k-mer by k-mer (their shards send the k-mers: a true syncmer is
+//    on every shard, a sequencing error on one, so this is thousands of k-mers) and clustered in first-seen order -- the reference's ids for
+//    the union of the shards, hash collisions included; coverage summed per k-mer
+static int mg_owner_range(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, uint64_t *req_off, uint64_t *asked_off)
+{
+    const int n = c->n;
+    const uint64_t nr = m->recv_off[n];
+    uint64_t n_own = 0, n_req = 0;
+    int rc;
     MENSURE(srt_h, (nr + 1) * 8); MENSURE(srt_i, (nr + 1) * 4); MENSURE(iota, (nr + 1) * 4); MENSURE(flag, (nr + 1) * 4); MENSURE(grp, (nr + 1) * 4); MENSURE(grp_of, (nr + 1) * 4);
     MENSURE(own_h, (nr + 1) * 8); MENSURE(own_s, (nr + 1) * 8); MENSURE(own_cov, (nr + 1) * 4); MENSURE(reply, (nr + 1) * 8);
     MENSURE(need_j, (nr + 1) * 4); MENSURE(pos_of_j, (nr + 2) * 4); MENSURE(rep, (nr + 1) * 4); MENSURE(clhead, (nr + 1) * 4); MENSURE(req_j, (nr + 1) * 4); MENSURE(req_k, (nr + 1) * 4);
     MENSURE(need8, nr + 8);
-    uint64_t n_req = 0, req_off[65] = {0}, asked_off[65] = {0};
     const int nw = (ctx->K + 31) / 32;
     CK(hipMemsetAsync(m->need_j.p, 0, (nr + 1) * 4, ctx->stream));
     if (nr) {
@@ -720,7 +711,7 @@ static int merge_counts_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint64_t *n_global
     if ((rc = comm_plan(ctx, c, req_off, asked_off)) != OATK_OK) return rc;
     const uint64_t n_asked = asked_off[n];
     MENSURE(asked, (n_asked + 1) * 4); MENSURE(lid, (n_asked + 1) * 4); MENSURE(seq_out, (n_asked + 1) * (size_t) nw * 8); MENSURE(seq_in, (n_req + 1) * (size_t) nw * 8);
-    if ((rc = comm_exchange(ctx, c, m->req_k.p, req_off, m->asked.p, asked_off, 4)) != OATK_OK) return rc;
+    if ((rc = comm_exchange_cols(ctx, c, {{m->req_k.p, m->asked.p, 4}}, req_off, asked_off)) != OATK_OK) return rc;
     if (n_asked) {
         CK(hipMemcpyAsync(m->plan_d.as<uint64_t>(), m->send_off, 65 * 8, hipMemcpyHostToDevice, ctx->stream));
         CK(hipMemcpyAsync(m->plan_d.as<uint64_t>() + 65, asked_off, 65 * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -730,7 +721,7 @@ static int merge_counts_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint64_t *n_global
                            ctx->scm_occ.as<uint64_t>(), ctx->sid0, ctx->d_off, ctx->scm_off.as<uint64_t>(), ctx->pos_mpos.as<uint32_t>(), ctx->hoco_s.as<uint8_t>(), ctx->K, nw,
                            m->seq_out.as<uint64_t>());
     }
-    if ((rc = comm_exchange(ctx, c, m->seq_out.p, asked_off, m->seq_in.p, req_off, (uint32_t) nw * 8u)) != OATK_OK) return rc;
+    if ((rc = comm_exchange_cols(ctx, c, {{m->seq_out.p, m->seq_in.p, (uint32_t) nw * 8u}}, asked_off, req_off)) != OATK_OK) return rc;
     if (nr) {
         hipLaunchKernelGGL(mg_cluster_kernel, grid256(nr), dim3(256), 0, ctx->stream, m->flag.as<uint32_t>(), m->srt_i.as<uint32_t>(), nr, m->need_j.as<uint32_t>(), m->pos_of_j.as<uint32_t>(),
                            m->seq_in.as<uint64_t>(), nw, m->recv_s.as<uint64_t>(), m->rep.as<uint32_t>(), m->clhead.as<uint32_t>(), m->bad.as<uint32_t>() + 1);
@@ -744,28 +735,58 @@ static int merge_counts_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint64_t *n_global
         CK(hipStreamSynchronize(ctx->stream));
         n_own = last;
     }
+    m->n_owned = n_own;
+    return OATK_OK;
+}
+
+// every rank must come to the same verdict, or the ones that go on wait for the ones that left; the same call tells everybody every range's size
+static int mg_verdict_ranges(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m)
+{
+    const int n = c->n;
+    int rc;
     uint32_t bad[2] = {0, 0};
     CK(hipMemcpyAsync(bad, m->bad.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
-    // every rank must come to the same verdict, or the ones that go on wait for the ones that left; the same call tells everybody every range's size
-    uint64_t mine2[2] = {(uint64_t) (bad[1]? 1 : 0), n_own}, all2[128], worst = 0, ng = 0;
+    uint64_t mine2[2] = {(uint64_t) (bad[1]? 1 : 0), m->n_owned}, all2[128], worst = 0, ng = 0;
     if ((rc = comm_allgather_vec(ctx, c, mine2, 2, all2)) != OATK_OK) return rc;
     for (int r = 0; r < n; ++r) { worst = all2[2 * r] > worst? all2[2 * r] : worst; m->first_id[r] = ng; ng += all2[2 * r + 1]; }
-    m->first_id[n] = ng;
+    m->first_id[n] = m->n_global = ng;
     if (worst == 1) { c->agreed = true; ctx->err = "identical k-mers with different s-mers across shards (syncmer.c:1370: fatal in the reference)"; return OATK_E_SMER; }
     if (ng >= 0x7FFFFFFFULL) { c->agreed = true; ctx->err = "merged syncmer table too large for 32-bit ids"; return OATK_E_ARG; }      // (the same sum on every rank)
+    return OATK_OK;
+}
 
-    // 3. every entry goes back to where it came from with its rank inside the owner's range and the coverage over all shards
+// 3. every entry goes back to where it came from with its rank inside the owner's range and the coverage over all shards
+static int mg_reply_l2g(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m)
+{
+    const uint64_t nl = ctx->n_scm_total;
+    int rc;
     MENSURE(back, (nl + 1) * 8); MENSURE(l2g, (nl + 1) * 4); MENSURE(lcov, (nl + 1) * 4);
-    if ((rc = comm_exchange(ctx, c, m->reply.p, m->recv_off, m->back.p, m->send_off, 8)) != OATK_OK) return rc;
+    if ((rc = comm_exchange_cols(ctx, c, {{m->reply.p, m->back.p, 8}}, m->recv_off, m->send_off)) != OATK_OK) return rc;
     CK(hipMemcpyAsync(m->plan_d.p, m->send_off, 65 * 8, hipMemcpyHostToDevice, ctx->stream));
     CK(hipMemcpyAsync(m->plan_d.as<uint64_t>() + 65, m->first_id, 65 * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (nl) hipLaunchKernelGGL(mg_l2g_kernel, grid256(nl), dim3(256), 0, ctx->stream, m->back.as<uint64_t>(), nl, m->plan_d.as<uint64_t>(), n, m->l2g.as<uint32_t>(), m->lcov.as<uint32_t>());
+    if (nl) hipLaunchKernelGGL(mg_l2g_kernel, grid256(nl), dim3(256), 0, ctx->stream, m->back.as<uint64_t>(), nl, m->plan_d.as<uint64_t>(), c->n, m->l2g.as<uint32_t>(), m->lcov.as<uint32_t>());
     CK(hipStreamSynchronize(ctx->stream));
     CK(hipGetLastError());
-    (void) me;
-    m->n_global = ng, m->n_owned = n_own, m->merged = true;
-    if (n_global) *n_global = ng;
+    return OATK_OK;
+}
+
+static int merge_counts_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint64_t *n_global)
+{
+    int rc;
+    if ((rc = comm_check(ctx, c, "oatk_hip_merge_counts")) != OATK_OK) return rc;
+    if (!ctx->counted) { ctx->err = "oatk_hip_merge_counts needs a resident scan + count"; return OATK_E_STATE; }
+    CK(hipSetDevice(ctx->device));
+    if (!ctx->multi) ctx->multi = new MultiState();
+    MultiState *m = ctx->multi;
+    m->merged = m->ec_done = false, m->rank = c->rank, m->table_root = -1;
+    MergeHost H;
+    if ((rc = mg_send_ranges(ctx, c, m, H.key)) != OATK_OK) return rc;
+    if ((rc = mg_owner_range(ctx, c, m, H.req_off, H.asked_off)) != OATK_OK) return rc;
+    if ((rc = mg_verdict_ranges(ctx, c, m)) != OATK_OK) return rc;
+    if ((rc = mg_reply_l2g(ctx, c, m)) != OATK_OK) return rc;
+    m->merged = true;
+    if (n_global) *n_global = m->n_global;
     return OATK_OK;
 }
 
@@ -893,247 +914,257 @@ static int mg_select_u32(oatk_hip_ctx *ctx, MultiState *m, const uint32_t *in, c
     *n_out = 0;
     if (!out.ensure((n + 1) * 4, ctx->stream)) { ctx->err = "hipMalloc failed (select)"; return OATK_E_NOMEM; }
     if (n == 0) return OATK_OK;
-    MENSURE(num, (64 * 65 + 64) * 8);
-    uint64_t *d_cnt = m->num.as<uint64_t>() + 64 * 65 + 8;
-    return prim_select(ctx, in, flag, n, out.as<uint32_t>(), d_cnt, n_out);
+    NUM_ENSURE();
+    return prim_select(ctx, in, flag, n, out.as<uint32_t>(), m->num.as<uint64_t>() + NUM_SELECT, n_out);
 }
 
-static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, uint32_t err_mer_c, uint32_t max_err_c, uint32_t err_arc_c,
-                           double max_arc_f, uint64_t *stats12, uint64_t *n_imported)
-{
-    using namespace oatk;
-    int rc;
-    if ((rc = comm_check(ctx, c, "oatk_hip_ec_sharded")) != OATK_OK) return rc;
-    if (!ctx->counted) { ctx->err = "oatk_hip_ec_sharded needs a resident scan + count"; return OATK_E_STATE; }
-    CK(hipSetDevice(ctx->device));
-    if (!ctx->multi || !ctx->multi->merged) { if ((rc = merge_counts_impl(ctx, c, nullptr)) != OATK_OK) return rc; }
-    MultiState *m = ctx->multi;
-    m->ec_done = false, m->table_root = -1;
-    const uint64_t ng = m->n_global, nl = ctx->n_scm_total, no = m->n_owned;
-    const uint32_t first_me = (uint32_t) m->first_id[c->rank];
-    const int nothing = ctx->n_occ == 0;            // a rank without syncmers corrects nothing and needs no k-mers
-    if (n_imported) *n_imported = 0;
-    const bool light = err_mer_c > 0 && err_arc_c >= err_mer_c && max_err_c >= err_mer_c && !getenv("OATK_DEBUG_FULL_GRAPH");
+// What the steps of one sharded round hand each other: the sizes of the whole table, this shard's table, this owner's range and the candidates' list, this owner's first
+// id, the coverage threshold, whether this rank has no syncmer at all (it corrects nothing and needs no k-mers), and which graph travels.
+struct EcRound { uint64_t ng, nl, no, nc; uint32_t first_me, err_mer_c; int nothing; bool light; };
+// room for n flags and n indices (DevBuf::ensure never shrinks: a smaller request after a larger one keeps the larger buffer)
+#define FLAG_ROOM(n) do { MENSURE(flag, (n) + 8); MENSURE(iota, ((n) + 1) * 4); } while (0)
 
-    // 0. coverage and s-mers over the global ids, as far as this rank will look: its own syncmers, and the candidates (seen >= err_mer_c times over
-    //    all shards) that every owner announces -- a few thousand at HiFi error rates.  With thresholds the light graph cannot serve, everything.
-    MENSURE(gcov, (ng + 1) * 4); MENSURE(S, (ng + 1) * 8); MENSURE(flag, (no > ng? no : ng) + 8); MENSURE(iota, ((no > ng? no : ng) + 1) * 4);
+// step 0, light: the candidates (seen >= err_mer_c times over all shards) that every owner announces -- a few thousand at HiFi error rates
+static int ec_cov_candidates(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, EcRound &R)
+{
+    const uint64_t no = R.no;
+    uint64_t nc_me = 0, nc = 0;
+    int rc;
+    hipLaunchKernelGGL(mg_iota_kernel, grid256(no), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), no);
+    hipLaunchKernelGGL(mg_cand_flag_kernel, grid256(no), dim3(256), 0, ctx->stream, m->own_cov.as<uint32_t>(), no, R.err_mer_c, m->flag.as<uint8_t>());
+    if ((rc = mg_select_u32(ctx, m, m->iota.as<uint32_t>(), m->flag.as<uint8_t>(), no, m->opack, &nc_me)) != OATK_OK) return rc;
+    MENSURE(cand_mine, (nc_me + 1) * 4); MENSURE(ccov_mine, (nc_me + 1) * 4); MENSURE(cs_mine, (nc_me + 1) * 8);
+    if (nc_me) hipLaunchKernelGGL(mg_cand_emit_kernel, grid256(nc_me), dim3(256), 0, ctx->stream, m->opack.as<uint32_t>(), nc_me, R.first_me, m->own_cov.as<uint32_t>(),
+                                  m->own_s.as<uint64_t>(), m->cand_mine.as<uint32_t>(), m->ccov_mine.as<uint32_t>(), m->cs_mine.as<uint64_t>());
+    // ids, coverage and s-mers of the candidates: rank order = id order, the list is ascending
+    if ((rc = comm_gather_cols(ctx, c, {{m->cand_mine.p, &m->cand, 4}, {m->ccov_mine.p, &m->cand_cov, 4}, {m->cs_mine.p, &m->cand_s, 8}}, nc_me, &nc)) != OATK_OK) return rc;
+    if (nc) {
+        hipLaunchKernelGGL(mg_scatter_kernel<uint32_t>, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), m->cand_cov.as<uint32_t>(), nc, m->gcov.as<uint32_t>());
+        hipLaunchKernelGGL(mg_scatter_kernel<uint64_t>, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), m->cand_s.as<uint64_t>(), nc, m->S.as<uint64_t>());
+    }
+    R.nc = nc;
+    return OATK_OK;
+}
+// step 0, full (thresholds the light graph cannot serve): every owner's range
+static int ec_cov_everything(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, const EcRound &R)
+{
+    int rc;
+    uint64_t cnt[64], bytes[64];
+    if ((rc = comm_allgather_u64(ctx, c, R.no, cnt)) != OATK_OK) return rc;
+    for (int r = 0; r < c->n; ++r) bytes[r] = cnt[r] * 4;
+    if ((rc = comm_allgatherv(ctx, c, m->own_cov.p, bytes, m->gcov.p)) != OATK_OK) return rc;
+    for (int r = 0; r < c->n; ++r) bytes[r] = cnt[r] * 8;
+    return comm_allgatherv(ctx, c, m->own_s.p, bytes, m->S.p);
+}
+// 0. coverage and s-mers over the global ids, as far as this rank will look: its own syncmers, and the candidates or everything
+static int ec_step0_cov_smers(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, EcRound &R)
+{
+    const uint64_t ng = R.ng, nl = R.nl;
+    int rc;
+    MENSURE(gcov, (ng + 1) * 4); MENSURE(S, (ng + 1) * 8); FLAG_ROOM(ng);      // (what the round flags -- an owner's range, candidates, distinct ids -- is never more than the table)
     CK(hipMemsetAsync(m->gcov.p, 0, (ng + 1) * 4, ctx->stream));
     CK(hipMemsetAsync(m->S.p, 0, (ng + 1) * 8, ctx->stream));
-    uint64_t nc = 0;
-    if (light) {
-        uint64_t nc_me = 0, chk = 0;
-        hipLaunchKernelGGL(mg_iota_kernel, grid256(no), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), no);
-        hipLaunchKernelGGL(mg_cand_flag_kernel, grid256(no), dim3(256), 0, ctx->stream, m->own_cov.as<uint32_t>(), no, err_mer_c, m->flag.as<uint8_t>());
-        if ((rc = mg_select_u32(ctx, m, m->iota.as<uint32_t>(), m->flag.as<uint8_t>(), no, m->opack, &nc_me)) != OATK_OK) return rc;
-        MENSURE(cand_mine, (nc_me + 1) * 4); MENSURE(ccov_mine, (nc_me + 1) * 4); MENSURE(cs_mine, (nc_me + 1) * 8);
-        if (nc_me) hipLaunchKernelGGL(mg_cand_emit_kernel, grid256(nc_me), dim3(256), 0, ctx->stream, m->opack.as<uint32_t>(), nc_me, first_me, m->own_cov.as<uint32_t>(),
-                                      m->own_s.as<uint64_t>(), m->cand_mine.as<uint32_t>(), m->ccov_mine.as<uint32_t>(), m->cs_mine.as<uint64_t>());
-        {   // ids, coverage and s-mers of the candidates: rank order = id order, the list is ascending
-            const void *src3[3] = {m->cand_mine.p, m->ccov_mine.p, m->cs_mine.p};
-            DevBuf *dst3[3] = {&m->cand, &m->cand_cov, &m->cand_s};
-            const uint32_t w3[3] = {4, 4, 8};
-            if ((rc = comm_gather_items_multi(ctx, c, 3, src3, w3, dst3, nc_me, &nc)) != OATK_OK) return rc;
-            (void) chk;
-        }
-        if (nc) {
-            hipLaunchKernelGGL(mg_scatter_kernel<uint32_t>, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), m->cand_cov.as<uint32_t>(), nc, m->gcov.as<uint32_t>());
-            hipLaunchKernelGGL(mg_scatter_kernel<uint64_t>, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), m->cand_s.as<uint64_t>(), nc, m->S.as<uint64_t>());
-        }
-    } else {
-        uint64_t cnt[64], bytes[64];
-        if ((rc = comm_allgather_u64(ctx, c, no, cnt)) != OATK_OK) return rc;
-        for (int r = 0; r < c->n; ++r) bytes[r] = cnt[r] * 4;
-        if ((rc = comm_allgatherv(ctx, c, m->own_cov.p, bytes, m->gcov.p)) != OATK_OK) return rc;
-        for (int r = 0; r < c->n; ++r) bytes[r] = cnt[r] * 8;
-        if ((rc = comm_allgatherv(ctx, c, m->own_s.p, bytes, m->S.p)) != OATK_OK) return rc;
-    }
-    m->n_cand = nc;
+    if ((rc = R.light? ec_cov_candidates(ctx, c, m, R) : ec_cov_everything(ctx, c, m, R)) != OATK_OK) return rc;
     if (nl) {
         hipLaunchKernelGGL(mg_scatter_kernel<uint32_t>, grid256(nl), dim3(256), 0, ctx->stream, m->l2g.as<uint32_t>(), m->lcov.as<uint32_t>(), nl, m->gcov.as<uint32_t>());
         hipLaunchKernelGGL(mg_scatter_kernel<uint64_t>, grid256(nl), dim3(256), 0, ctx->stream, m->l2g.as<uint32_t>(), ctx->scm_s.as<uint64_t>(), nl, m->S.as<uint64_t>());
     }
+    return OATK_OK;
+}
 
-    // 1. chains in global ids; the graph of all reads
-    if ((rc = oatk_hip_ec_set_global(ctx, ng, m->l2g.as<uint32_t>(), m->gcov.as<uint32_t>(), m->S.as<uint64_t>())) != OATK_OK) return rc;
-    uint64_t np_all = 0;
-    if (light) {
-        // The light graph (include/oatk_hip_ec.h): what travels is each shard's pairs between two candidates, sorted by key and run-length
-        // compressed into (key, distance, calls) segments -- a few per true arc instead of one per read -- and one flag per oriented candidate
-        // for arcs to rarer syncmers.  The per-rank cost does not grow with the number of shards.
-        EcState *e = ctx->ec;
-        const uint64_t *lk = nullptr;
-        const uint32_t *ld = nullptr;
-        uint64_t nk = 0, n_seg = 0;
-        if ((rc = ec_light_pairs(ctx, err_mer_c, &lk, &ld, &nk)) != OATK_OK) return rc;
-        EENSURE(g_keys2, (nk + 1) * 8); EENSURE(g_dist2, (nk + 1) * 4); EENSURE(g_head, nk + 8); EENSURE(g_hpos, (nk + 1) * 4); EENSURE(g_iota, (nk + 1) * 4);
-        if (nk) {
-            // stable: a key's distances stay in (read, slot) order, so a segment is a run of consecutive calls
-            PRIM(rocprim::radix_sort_pairs, const_cast<uint64_t *>(lk), e->g_keys2.as<uint64_t>(), const_cast<uint32_t *>(ld), e->g_dist2.as<uint32_t>(), nk, 0, 64, ctx->stream);
-            hipLaunchKernelGGL(egr_seg_head_kernel, grid256(nk), dim3(256), 0, ctx->stream, nk, e->g_keys2.as<uint64_t>(), e->g_dist2.as<uint32_t>(), e->g_head.as<uint8_t>());
-            hipLaunchKernelGGL(mg_iota_kernel, grid256(nk), dim3(256), 0, ctx->stream, e->g_iota.as<uint32_t>(), nk);
-            EENSURE(g_nruns, 64);
-            if ((rc = prim_select(ctx, e->g_iota.as<uint32_t>(), e->g_head.as<uint8_t>(), nk, e->g_hpos.as<uint32_t>(), e->g_nruns.as<uint64_t>() + 2, &n_seg)) != OATK_OK) return rc;
-        }
-        EENSURE(g_segk, (n_seg + 1) * 8); EENSURE(g_segv, (n_seg + 1) * 8);
-        if (n_seg) hipLaunchKernelGGL(egr_seg_emit_kernel, grid256(n_seg), dim3(256), 0, ctx->stream, n_seg, nk, e->g_hpos.as<uint32_t>(), e->g_keys2.as<uint64_t>(),
-                                      e->g_dist2.as<uint32_t>(), e->g_segk.as<uint64_t>(), e->g_segv.as<uint64_t>());
-        {
-            const void *src2[2] = {e->g_segk.p, e->g_segv.p};
-            DevBuf *dst2[2] = {&m->keys_all, &m->dist_all};
-            const uint32_t w2[2] = {8, 8};
-            if ((rc = comm_gather_items_multi(ctx, c, 2, src2, w2, dst2, n_seg, &np_all)) != OATK_OK) return rc;
-        }
-        rc = ec_graph_build(ctx, m->keys_all.as<uint64_t>(), nullptr, m->dist_all.as<uint64_t>(), np_all, true);
-    } else {
-        const void *d_keys = nullptr, *d_dist = nullptr;
-        uint64_t np = 0;
-        if ((rc = oatk_hip_ec_pairs(ctx, &d_keys, &d_dist, &np)) != OATK_OK) return rc;
-        {
-            const void *src2[2] = {d_keys, d_dist};
-            DevBuf *dst2[2] = {&m->keys_all, &m->dist_all};
-            const uint32_t w2[2] = {8, 4};
-            if ((rc = comm_gather_items_multi(ctx, c, 2, src2, w2, dst2, np, &np_all)) != OATK_OK) return rc;
-        }
-        rc = oatk_hip_ec_graph_from_pairs(ctx, m->keys_all.as<uint64_t>(), m->dist_all.as<uint32_t>(), np_all);
-    }
-    // (a refusal -- duplicate arcs -- is the same on every rank, a failure need not be: the verdict travels with the next counts, below; a rank that has none of its
-    //  own goes through the motions of the collective in between)
-    int rc_graph = rc;                                                        // a refusal (duplicate arcs) is the same on every rank: the graph is
-    if (light) {
-        // a candidate has arcs to rarer syncmers if it has them on any shard
-        EcState *e = ctx->ec;
-        if (nc) {
-            const uint64_t words = (2 * nc + 3) / 4;
-            MENSURE(opack, words * 4 + 16);
-            CK(hipMemsetAsync(m->opack.p, 0, words * 4, ctx->stream));
-            if (!rc_graph) hipLaunchKernelGGL(mg_other_pack_kernel, grid256(2 * nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), 2 * nc, e->g_other.as<uint8_t>(), m->opack.as<uint8_t>());
-            if ((rc = comm_allreduce(ctx, c, m->opack.p, words, false, false)) != OATK_OK) return rc;     // at most 64 ranks: the byte sums do not carry
-            if (!rc_graph) hipLaunchKernelGGL(mg_other_unpack_kernel, grid256(2 * nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), 2 * nc, m->opack.as<uint8_t>(), e->g_other.as<uint8_t>());
-        }
-        if (!rc_graph) e->light_c = err_mer_c;
-    }
-    if (!rc_graph) rc_graph = oatk_hip_ec_mark(ctx, err_mer_c, max_err_c, err_arc_c, max_arc_f);
+// step 1, light (include/oatk_hip_ec.h): what travels is each shard's pairs between two candidates, sorted by key and run-length compressed into (key, distance, calls)
+// segments -- a few per true arc instead of one per read -- and one flag per oriented candidate for arcs to rarer syncmers.  The per-rank cost does not grow with the
+// number of shards.  *verdict: the graph's (a refusal -- duplicate arcs -- is the same on every rank, a failure need not be); the return value is this rank's way there.
+static int ec_graph_light(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, const EcRound &R, int *verdict)
+{
+    using namespace oatk;
     EcState *e = ctx->ec;
+    const uint64_t nc = R.nc;
+    int rc;
+    const uint64_t *lk = nullptr;
+    const uint32_t *ld = nullptr;
+    uint64_t nk = 0, n_seg = 0, np_all = 0;
+    if ((rc = ec_light_pairs(ctx, R.err_mer_c, &lk, &ld, &nk)) != OATK_OK) return rc;
+    EENSURE(g_keys2, (nk + 1) * 8); EENSURE(g_dist2, (nk + 1) * 4); EENSURE(g_head, nk + 8); EENSURE(g_hpos, (nk + 1) * 4); EENSURE(g_iota, (nk + 1) * 4);
+    if (nk) {
+        // stable: a key's distances stay in (read, slot) order, so a segment is a run of consecutive calls
+        PRIM(rocprim::radix_sort_pairs, const_cast<uint64_t *>(lk), e->g_keys2.as<uint64_t>(), const_cast<uint32_t *>(ld), e->g_dist2.as<uint32_t>(), nk, 0, 64, ctx->stream);
+        hipLaunchKernelGGL(egr_seg_head_kernel, grid256(nk), dim3(256), 0, ctx->stream, nk, e->g_keys2.as<uint64_t>(), e->g_dist2.as<uint32_t>(), e->g_head.as<uint8_t>());
+        hipLaunchKernelGGL(mg_iota_kernel, grid256(nk), dim3(256), 0, ctx->stream, e->g_iota.as<uint32_t>(), nk);
+        EENSURE(g_nruns, 64);
+        if ((rc = prim_select(ctx, e->g_iota.as<uint32_t>(), e->g_head.as<uint8_t>(), nk, e->g_hpos.as<uint32_t>(), e->g_nruns.as<uint64_t>() + 2, &n_seg)) != OATK_OK) return rc;
+    }
+    EENSURE(g_segk, (n_seg + 1) * 8); EENSURE(g_segv, (n_seg + 1) * 8);
+    if (n_seg) hipLaunchKernelGGL(egr_seg_emit_kernel, grid256(n_seg), dim3(256), 0, ctx->stream, n_seg, nk, e->g_hpos.as<uint32_t>(), e->g_keys2.as<uint64_t>(),
+                                  e->g_dist2.as<uint32_t>(), e->g_segk.as<uint64_t>(), e->g_segv.as<uint64_t>());
+    if ((rc = comm_gather_cols(ctx, c, {{e->g_segk.p, &m->keys_all, 8}, {e->g_segv.p, &m->dist_all, 8}}, n_seg, &np_all)) != OATK_OK) return rc;
+    const int rc_graph = *verdict = ec_graph_build(ctx, m->keys_all.as<uint64_t>(), nullptr, m->dist_all.as<uint64_t>(), np_all, true);
+    // a candidate has arcs to rarer syncmers if it has them on any shard (a rank whose graph was refused goes through the motions of the collective)
+    if (nc) {
+        const uint64_t words = (2 * nc + 3) / 4;
+        MENSURE(opack, words * 4 + 16);
+        CK(hipMemsetAsync(m->opack.p, 0, words * 4, ctx->stream));
+        if (!rc_graph) hipLaunchKernelGGL(mg_other_pack_kernel, grid256(2 * nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), 2 * nc, e->g_other.as<uint8_t>(), m->opack.as<uint8_t>());
+        if ((rc = comm_allreduce(ctx, c, m->opack.p, words, false, false)) != OATK_OK) return rc;     // at most 64 ranks: the byte sums do not carry
+        if (!rc_graph) hipLaunchKernelGGL(mg_other_unpack_kernel, grid256(2 * nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), 2 * nc, m->opack.as<uint8_t>(), e->g_other.as<uint8_t>());
+    }
+    if (!rc_graph) e->light_c = R.err_mer_c;
+    return OATK_OK;
+}
+// step 1, full: every pair of every shard travels
+static int ec_graph_full(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, int *verdict)
+{
+    int rc;
+    const void *d_keys = nullptr, *d_dist = nullptr;
+    uint64_t np = 0, np_all = 0;
+    if ((rc = oatk_hip_ec_pairs(ctx, &d_keys, &d_dist, &np)) != OATK_OK) return rc;
+    if ((rc = comm_gather_cols(ctx, c, {{d_keys, &m->keys_all, 8}, {d_dist, &m->dist_all, 4}}, np, &np_all)) != OATK_OK) return rc;
+    *verdict = oatk_hip_ec_graph_from_pairs(ctx, m->keys_all.as<uint64_t>(), m->dist_all.as<uint32_t>(), np_all);
+    return OATK_OK;
+}
+// 1. chains in global ids; the graph of all reads; the marks.  *verdict is the graph's and the marks': step 2 takes it round with its counts
+static int ec_step1_graph(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, const EcRound &R, uint32_t max_err_c, uint32_t err_arc_c, double max_arc_f, int *verdict)
+{
+    int rc;
+    if ((rc = oatk_hip_ec_set_global(ctx, R.ng, m->l2g.as<uint32_t>(), m->gcov.as<uint32_t>(), m->S.as<uint64_t>())) != OATK_OK) return rc;
+    if ((rc = R.light? ec_graph_light(ctx, c, m, R, verdict) : ec_graph_full(ctx, c, m, verdict)) != OATK_OK) return rc;
+    if (!*verdict) *verdict = oatk_hip_ec_mark(ctx, R.err_mer_c, max_err_c, err_arc_c, max_arc_f);
+    return OATK_OK;
+}
 
-    // 2. good syncmers this rank has no k-mer for: somebody who has one sends it (the lowest such rank).  Only candidates can be good.
-    uint64_t n_need = 0, n_need_all = 0, nu = 0;
-    if (rc_graph) {
-        MENSURE(need, 64);
-    } else if (light) {
-        // flags over the candidate list instead of the whole table
-        MENSURE(flag, (nc > ng? nc : ng) + 8);
-        if (nc) hipLaunchKernelGGL(mg_need_cand_kernel, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), nc, (const uint8_t *) e->err_del.p,
-                                   e->vtx_hs_off.as<uint64_t>(), m->flag.as<uint8_t>(), nothing);
-        if ((rc = mg_select_u32(ctx, m, m->cand.as<uint32_t>(), m->flag.as<uint8_t>(), nc, m->need, &n_need)) != OATK_OK) return rc;
-    } else {
-        MENSURE(flag, ng + 8); MENSURE(iota, (ng + 1) * 4);
-        hipLaunchKernelGGL(mg_iota_kernel, grid256(ng), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), ng);
-        hipLaunchKernelGGL(mg_need_flag_kernel, grid256(ng), dim3(256), 0, ctx->stream, (const uint8_t *) e->err_del.p, e->vtx_hs_off.as<uint64_t>(), ng, m->flag.as<uint8_t>(), nothing);
-        if ((rc = mg_select_u32(ctx, m, m->iota.as<uint32_t>(), m->flag.as<uint8_t>(), ng, m->need, &n_need)) != OATK_OK) return rc;
+// step 2, light: flags over the candidate list instead of the whole table
+static int ec_need_light(oatk_hip_ctx *ctx, MultiState *m, const EcRound &R, uint64_t *n_need)
+{
+    EcState *e = ctx->ec;
+    const uint64_t nc = R.nc;
+    FLAG_ROOM(nc);
+    if (nc) hipLaunchKernelGGL(mg_need_cand_kernel, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), nc, (const uint8_t *) e->err_del.p,
+                               e->vtx_hs_off.as<uint64_t>(), m->flag.as<uint8_t>(), R.nothing);
+    return mg_select_u32(ctx, m, m->cand.as<uint32_t>(), m->flag.as<uint8_t>(), nc, m->need, n_need);
+}
+// step 2, full: flags over the whole table
+static int ec_need_full(oatk_hip_ctx *ctx, MultiState *m, const EcRound &R, uint64_t *n_need)
+{
+    EcState *e = ctx->ec;
+    const uint64_t ng = R.ng;
+    FLAG_ROOM(ng);
+    hipLaunchKernelGGL(mg_iota_kernel, grid256(ng), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), ng);
+    hipLaunchKernelGGL(mg_need_flag_kernel, grid256(ng), dim3(256), 0, ctx->stream, (const uint8_t *) e->err_del.p, e->vtx_hs_off.as<uint64_t>(), ng, m->flag.as<uint8_t>(), R.nothing);
+    return mg_select_u32(ctx, m, m->iota.as<uint32_t>(), m->flag.as<uint8_t>(), ng, m->need, n_need);
+}
+// the k-mers of the nu distinct ids somebody needs (m->uni): the owner of each (the lowest rank that has it) exports it, all of them travel to everybody, and every
+// rank imports what it lacks
+static int ec_import_kmers(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, const EcRound &R, uint64_t nu, uint64_t *n_imported)
+{
+    EcState *e = ctx->ec;
+    int rc;
+    const uint32_t nobody = (uint32_t) c->n;
+    MENSURE(owner, (nu + 1) * 4); MENSURE(bad, 64);
+    hipLaunchKernelGGL(mg_owner_kernel, grid256(nu), dim3(256), 0, ctx->stream, m->uni.as<uint32_t>(), nu, e->vtx_hs_off.as<uint64_t>(), (uint32_t) c->rank, nobody, m->owner.as<uint32_t>());
+    if ((rc = comm_allreduce(ctx, c, m->owner.p, nu, false, true)) != OATK_OK) return rc;
+    CK(hipMemsetAsync(m->bad.p, 0, 64, ctx->stream));
+    FLAG_ROOM(nu);
+    hipLaunchKernelGGL(mg_eq_flag_kernel, grid256(nu), dim3(256), 0, ctx->stream, m->owner.as<uint32_t>(), nu, (uint32_t) c->rank, m->flag.as<uint8_t>(), m->bad.as<uint32_t>(), nobody);
+    uint32_t orphan = 0;
+    CK(hipMemcpyAsync(&orphan, m->bad.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    uint64_t n_mine = 0;
+    if ((rc = mg_select_u32(ctx, m, m->uni.as<uint32_t>(), m->flag.as<uint8_t>(), nu, m->mine, &n_mine)) != OATK_OK) return rc;
+    if (orphan) { c->agreed = true; ctx->err = "sharded error correction: a live syncmer occurs on no shard"; return OATK_E_STATE; }      // (the same on every rank)
+    const uint32_t stride = (uint32_t) (((ctx->K + 3) / 4 + 8 + 15) / 16 * 16);
+    MENSURE(kout, (n_mine + 1) * (size_t) stride); MENSURE(krev, n_mine + 8);
+    if ((rc = oatk_hip_ec_export_kmers(ctx, m->mine.as<uint32_t>(), n_mine, m->kout.as<uint8_t>(), stride, m->krev.as<uint8_t>())) != OATK_OK) return rc;
+    uint64_t n_all = 0, n_imp = 0, chk = 0;
+    if ((rc = comm_gather_cols(ctx, c, {{m->mine.p, &m->ids_all, 4}, {m->krev.p, &m->rev_all, 1}, {m->kout.p, &m->km_all, stride}}, n_mine, &n_all)) != OATK_OK) return rc;
+    // of everything that travelled, what THIS rank lacks
+    FLAG_ROOM(n_all);
+    hipLaunchKernelGGL(mg_iota_kernel, grid256(n_all), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), n_all);
+    hipLaunchKernelGGL(mg_lack_kernel, grid256(n_all), dim3(256), 0, ctx->stream, m->ids_all.as<uint32_t>(), n_all, e->vtx_hs_off.as<uint64_t>(), m->flag.as<uint8_t>(), R.nothing);
+    if ((rc = mg_select_u32(ctx, m, m->iota.as<uint32_t>(), m->flag.as<uint8_t>(), n_all, m->lack, &n_imp)) != OATK_OK) return rc;
+    if (n_imp) {
+        MENSURE(ids_i, (n_imp + 1) * 4); MENSURE(rev_i, n_imp + 16); MENSURE(km_i, (n_imp + 1) * (size_t) stride);
+        hipLaunchKernelGGL(mg_rows_kernel, dim3((unsigned) n_imp), dim3(64), 0, ctx->stream, m->km_all.as<uint8_t>(), m->lack.as<uint32_t>(), n_imp, stride, m->km_i.as<uint8_t>());
+        // ids and strands are rows too (4 and 1 byte): gather them with the generic selects
+        if ((rc = mg_select_u32(ctx, m, m->ids_all.as<uint32_t>(), m->flag.as<uint8_t>(), n_all, m->ids_i, &chk)) != OATK_OK) return rc;
+        PRIM(rocprim::select, m->rev_all.as<uint8_t>(), m->flag.as<uint8_t>(), m->rev_i.as<uint8_t>(), m->num.as<uint64_t>() + NUM_SELECT8, n_all, ctx->stream);
+        if ((rc = oatk_hip_ec_import_kmers(ctx, m->ids_i.as<uint32_t>(), m->rev_i.as<uint8_t>(), m->km_i.as<uint8_t>(), n_imp, stride)) != OATK_OK) return rc;
     }
-    {   // the counts, and with them everybody's verdict on the graph and the marks
-        const void *src1[1] = {m->need.p};
-        DevBuf *dst1[1] = {&m->need_all};
-        const uint32_t w1[1] = {4};
-        uint64_t verdict[64];
-        if ((rc = comm_gather_items_multi(ctx, c, 1, src1, w1, dst1, n_need, &n_need_all, (uint64_t) (uint32_t) rc_graph, verdict)) != OATK_OK) return rc;
-        for (int r = 0; r < c->n; ++r)
-            if (verdict[r]) {
-                c->agreed = true;
-                if (!rc_graph) ctx->err = "EC graph: refused on rank " + std::to_string(r);
-                return rc_graph? rc_graph : (int) (int32_t) (uint32_t) verdict[r];
-            }
-    }
+    if (n_imported) *n_imported = n_imp;
+    return OATK_OK;
+}
+// 2. good syncmers this rank has no k-mer for: somebody who has one sends it (the lowest such rank).  Only candidates can be good.
+static int ec_step2_kmers(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, const EcRound &R, int rc_graph, uint64_t *n_imported)
+{
+    int rc;
+    uint64_t n_need = 0, n_need_all = 0, nu = 0, verdict[64];
+    if (rc_graph) MENSURE(need, 64);
+    else if ((rc = R.light? ec_need_light(ctx, m, R, &n_need) : ec_need_full(ctx, m, R, &n_need)) != OATK_OK) return rc;
+    // The counts, and with them everybody's verdict on the graph and the marks.  A refusal (duplicate arcs) is the same on every rank, a failure need not be, so a rank
+    // with a bad verdict of its own has gone through the motions of every collective up to here (an empty list of needs included) and leaves together with the others.
+    if ((rc = comm_gather_cols(ctx, c, {{m->need.p, &m->need_all, 4}}, n_need, &n_need_all, (uint64_t) (uint32_t) rc_graph, verdict)) != OATK_OK) return rc;
+    for (int r = 0; r < c->n; ++r)
+        if (verdict[r]) {
+            c->agreed = true;
+            if (!rc_graph) ctx->err = "EC graph: refused on rank " + std::to_string(r);
+            return rc_graph? rc_graph : (int) (int32_t) (uint32_t) verdict[r];
+        }
     if (n_need_all) {
-        MENSURE(need_srt, (n_need_all + 1) * 4); MENSURE(uni, (n_need_all + 1) * 4); MENSURE(num, (64 * 65 + 64) * 8);
+        MENSURE(need_srt, (n_need_all + 1) * 4); MENSURE(uni, (n_need_all + 1) * 4); NUM_ENSURE();
         PRIM(rocprim::radix_sort_keys, m->need_all.as<uint32_t>(), m->need_srt.as<uint32_t>(), n_need_all, 0, 32, ctx->stream);
-        uint64_t *d_cnt = m->num.as<uint64_t>() + 64 * 65 + 9;
+        uint64_t *d_cnt = m->num.as<uint64_t>() + NUM_UNIQUE;
         PRIM(rocprim::unique, m->need_srt.as<uint32_t>(), m->uni.as<uint32_t>(), d_cnt, n_need_all, rocprim::equal_to<uint32_t>(), ctx->stream);
         CK(hipMemcpyAsync(&nu, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
     }
-    if (nu) {
-        const uint32_t nobody = (uint32_t) c->n;
-        MENSURE(owner, (nu + 1) * 4); MENSURE(bad, 64);
-        hipLaunchKernelGGL(mg_owner_kernel, grid256(nu), dim3(256), 0, ctx->stream, m->uni.as<uint32_t>(), nu, e->vtx_hs_off.as<uint64_t>(), (uint32_t) c->rank, nobody, m->owner.as<uint32_t>());
-        if ((rc = comm_allreduce(ctx, c, m->owner.p, nu, false, true)) != OATK_OK) return rc;
-        CK(hipMemsetAsync(m->bad.p, 0, 64, ctx->stream));
-        MENSURE(flag, (nu > ng? nu : ng) + 8);
-        hipLaunchKernelGGL(mg_eq_flag_kernel, grid256(nu), dim3(256), 0, ctx->stream, m->owner.as<uint32_t>(), nu, (uint32_t) c->rank, m->flag.as<uint8_t>(), m->bad.as<uint32_t>(), nobody);
-        uint32_t orphan = 0;
-        CK(hipMemcpyAsync(&orphan, m->bad.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-        uint64_t n_mine = 0;
-        if ((rc = mg_select_u32(ctx, m, m->uni.as<uint32_t>(), m->flag.as<uint8_t>(), nu, m->mine, &n_mine)) != OATK_OK) return rc;
-        if (orphan) { c->agreed = true; ctx->err = "sharded error correction: a live syncmer occurs on no shard"; return OATK_E_STATE; }      // (the same on every rank)
-        const uint32_t stride = (uint32_t) (((ctx->K + 3) / 4 + 8 + 15) / 16 * 16);
-        MENSURE(kout, (n_mine + 1) * (size_t) stride); MENSURE(krev, n_mine + 8);
-        if ((rc = oatk_hip_ec_export_kmers(ctx, m->mine.as<uint32_t>(), n_mine, m->kout.as<uint8_t>(), stride, m->krev.as<uint8_t>())) != OATK_OK) return rc;
-        uint64_t n_all = 0;
-        {
-            const void *src3[3] = {m->mine.p, m->krev.p, m->kout.p};
-            DevBuf *dst3[3] = {&m->ids_all, &m->rev_all, &m->km_all};
-            const uint32_t w3[3] = {4, 1, stride};
-            if ((rc = comm_gather_items_multi(ctx, c, 3, src3, w3, dst3, n_mine, &n_all)) != OATK_OK) return rc;
-        }
-        // of everything that travelled, what THIS rank lacks
-        MENSURE(flag, (n_all > ng? n_all : ng) + 8); MENSURE(iota, ((n_all > ng? n_all : ng) + 1) * 4);
-        hipLaunchKernelGGL(mg_iota_kernel, grid256(n_all), dim3(256), 0, ctx->stream, m->iota.as<uint32_t>(), n_all);
-        hipLaunchKernelGGL(mg_lack_kernel, grid256(n_all), dim3(256), 0, ctx->stream, m->ids_all.as<uint32_t>(), n_all, e->vtx_hs_off.as<uint64_t>(), m->flag.as<uint8_t>(), nothing);
-        uint64_t n_imp = 0;
-        if ((rc = mg_select_u32(ctx, m, m->iota.as<uint32_t>(), m->flag.as<uint8_t>(), n_all, m->lack, &n_imp)) != OATK_OK) return rc;
-        if (n_imp) {
-            MENSURE(ids_i, (n_imp + 1) * 4); MENSURE(rev_i, n_imp + 16); MENSURE(km_i, (n_imp + 1) * (size_t) stride);
-            hipLaunchKernelGGL(mg_rows_kernel, dim3((unsigned) n_imp), dim3(64), 0, ctx->stream, m->km_all.as<uint8_t>(), m->lack.as<uint32_t>(), n_imp, stride, m->km_i.as<uint8_t>());
-            // ids and strands are rows too (4 and 1 byte): gather them with the generic selects
-            uint64_t chk = 0;
-            if ((rc = mg_select_u32(ctx, m, m->ids_all.as<uint32_t>(), m->flag.as<uint8_t>(), n_all, m->ids_i, &chk)) != OATK_OK) return rc;
-            {
-                uint64_t *d_cnt = m->num.as<uint64_t>() + 64 * 65 + 10;
-                PRIM(rocprim::select, m->rev_all.as<uint8_t>(), m->flag.as<uint8_t>(), m->rev_i.as<uint8_t>(), d_cnt, n_all, ctx->stream);
-            }
-            if ((rc = oatk_hip_ec_import_kmers(ctx, m->ids_i.as<uint32_t>(), m->rev_i.as<uint8_t>(), m->km_i.as<uint8_t>(), n_imp, stride)) != OATK_OK) return rc;
-        }
-        if (n_imported) *n_imported = n_imp;
-    }
+    return nu? ec_import_kmers(ctx, c, m, R, nu, n_imported) : OATK_OK;
+}
 
-    // 3. every rank corrects its own reads; the refreshed table (update_syncmer_db, syncerr.c:769-814) is partitioned like the merged one
-    rc = oatk_hip_ec_correct(ctx, max_edist);
+// step 3, light: a corrected chain holds the rank's own syncmers and candidates (what a path can be made of).  Candidates: one all-reduce over their list.
+// The rest: every shard tells each owner what it still holds of the owner's syncmers, along the routes of the table merge.
+static int ec_refresh_light(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, const EcRound &R)
+{
+    EcState *e = ctx->ec;
+    const uint64_t nc = R.nc, nl = R.nl, no = R.no, nr = m->recv_off[c->n];
+    int rc;
+    CK(hipMemsetAsync(m->ec_cov.p, 0, (no + 1) * 4, ctx->stream));
+    CK(hipMemsetAsync(m->ec_fwd.p, 0, (no + 1) * 4, ctx->stream));
+    MENSURE(pc, (2 * nc + 2) * 4); MENSURE(loc_c, (nl + 1) * 4); MENSURE(loc_f, (nl + 1) * 4);
+    MENSURE(rcv_c, (nr + 1) * 4); MENSURE(rcv_f, (nr + 1) * 4);
+    if (nc) hipLaunchKernelGGL(mg_pack_cand_kernel, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), nc, e->cov.as<uint32_t>(), e->fwd.as<uint32_t>(), m->pc.as<uint32_t>());
+    if ((rc = comm_allreduce(ctx, c, m->pc.p, 2 * nc, false, false)) != OATK_OK) return rc;
+    if (nl) hipLaunchKernelGGL(mg_local_contrib_kernel, grid256(nl), dim3(256), 0, ctx->stream, m->l2g.as<uint32_t>(), nl, m->gcov.as<uint32_t>(), R.err_mer_c, e->cov.as<uint32_t>(),
+                               e->fwd.as<uint32_t>(), m->loc_c.as<uint32_t>(), m->loc_f.as<uint32_t>());
+    if ((rc = comm_exchange_cols(ctx, c, {{m->loc_c.p, m->rcv_c.p, 4}, {m->loc_f.p, m->rcv_f.p, 4}}, m->send_off, m->recv_off)) != OATK_OK) return rc;
+    if (nr) hipLaunchKernelGGL(mg_owner_add_kernel, grid256(nr), dim3(256), 0, ctx->stream, m->grp_of.as<uint32_t>(), nr, m->rcv_c.as<uint32_t>(), m->rcv_f.as<uint32_t>(),
+                               m->ec_cov.as<uint32_t>(), m->ec_fwd.as<uint32_t>());
+    if (nc) hipLaunchKernelGGL(mg_owner_cand_kernel, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), nc, m->pc.as<uint32_t>(), R.first_me, (uint32_t) no,
+                               m->ec_cov.as<uint32_t>(), m->ec_fwd.as<uint32_t>());
+    return OATK_OK;
+}
+// step 3, full: every id may matter: two all-reduces over the whole table, of which the rank keeps its own range
+static int ec_refresh_full(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, const EcRound &R)
+{
+    EcState *e = ctx->ec;
+    const uint64_t ng = R.ng, no = R.no;
+    int rc;
+    MENSURE(loc_c, (ng + 1) * 4); MENSURE(loc_f, (ng + 1) * 4);
+    CK(hipMemcpyAsync(m->loc_c.p, e->cov.p, ng * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    CK(hipMemcpyAsync(m->loc_f.p, e->fwd.p, ng * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    if ((rc = comm_allreduce(ctx, c, m->loc_c.p, ng, false, false)) != OATK_OK) return rc;
+    if ((rc = comm_allreduce(ctx, c, m->loc_f.p, ng, false, false)) != OATK_OK) return rc;
+    CK(hipMemcpyAsync(m->ec_cov.p, m->loc_c.as<uint32_t>() + R.first_me, no * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    CK(hipMemcpyAsync(m->ec_fwd.p, m->loc_f.as<uint32_t>() + R.first_me, no * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    return OATK_OK;
+}
+// 3. every rank corrects its own reads; the refreshed table (update_syncmer_db, syncerr.c:769-814) is partitioned like the merged one
+static int ec_step3_correct(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, const EcRound &R, double max_edist, uint64_t *stats12)
+{
+    EcState *e = ctx->ec;
+    const uint64_t no = R.no;
+    int rc = oatk_hip_ec_correct(ctx, max_edist);
     if ((rc = comm_agree(ctx, c, rc, "correction")) != OATK_OK) return rc;
     MENSURE(ec_cov, (no + 1) * 4); MENSURE(ec_fwd, (no + 1) * 4); MENSURE(ec_del, no + 8); MENSURE(st64, 16 * 8);
     CK(hipMemcpyAsync(m->st64.p, e->stats_h, 12 * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (light) {
-        // a corrected chain holds the rank's own syncmers and candidates (what a path can be made of).  Candidates: one all-reduce over their list.
-        // The rest: every shard tells each owner what it still holds of the owner's syncmers, along the routes of the table merge.
-        CK(hipMemsetAsync(m->ec_cov.p, 0, (no + 1) * 4, ctx->stream));
-        CK(hipMemsetAsync(m->ec_fwd.p, 0, (no + 1) * 4, ctx->stream));
-        MENSURE(pc, (2 * nc + 2) * 4); MENSURE(loc_c, (nl + 1) * 4); MENSURE(loc_f, (nl + 1) * 4);
-        const uint64_t nr = m->recv_off[c->n];
-        MENSURE(rcv_c, (nr + 1) * 4); MENSURE(rcv_f, (nr + 1) * 4);
-        if (nc) hipLaunchKernelGGL(mg_pack_cand_kernel, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), nc, e->cov.as<uint32_t>(), e->fwd.as<uint32_t>(), m->pc.as<uint32_t>());
-        if ((rc = comm_allreduce(ctx, c, m->pc.p, 2 * nc, false, false)) != OATK_OK) return rc;
-        if (nl) hipLaunchKernelGGL(mg_local_contrib_kernel, grid256(nl), dim3(256), 0, ctx->stream, m->l2g.as<uint32_t>(), nl, m->gcov.as<uint32_t>(), err_mer_c, e->cov.as<uint32_t>(),
-                                   e->fwd.as<uint32_t>(), m->loc_c.as<uint32_t>(), m->loc_f.as<uint32_t>());
-        {
-            const void *out2[2] = {m->loc_c.p, m->loc_f.p};
-            void *in2[2] = {m->rcv_c.p, m->rcv_f.p};
-            const uint32_t w2[2] = {4, 4};
-            if ((rc = comm_exchange_multi(ctx, c, 2, out2, m->send_off, in2, m->recv_off, w2)) != OATK_OK) return rc;
-        }
-        if (nr) hipLaunchKernelGGL(mg_owner_add_kernel, grid256(nr), dim3(256), 0, ctx->stream, m->grp_of.as<uint32_t>(), nr, m->rcv_c.as<uint32_t>(), m->rcv_f.as<uint32_t>(),
-                                   m->ec_cov.as<uint32_t>(), m->ec_fwd.as<uint32_t>());
-        if (nc) hipLaunchKernelGGL(mg_owner_cand_kernel, grid256(nc), dim3(256), 0, ctx->stream, m->cand.as<uint32_t>(), nc, m->pc.as<uint32_t>(), first_me, (uint32_t) no,
-                                   m->ec_cov.as<uint32_t>(), m->ec_fwd.as<uint32_t>());
-    } else {
-        // every id may matter: two all-reduces over the whole table, of which the rank keeps its own range
-        MENSURE(loc_c, (ng + 1) * 4); MENSURE(loc_f, (ng + 1) * 4);
-        CK(hipMemcpyAsync(m->loc_c.p, e->cov.p, ng * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        CK(hipMemcpyAsync(m->loc_f.p, e->fwd.p, ng * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        if ((rc = comm_allreduce(ctx, c, m->loc_c.p, ng, false, false)) != OATK_OK) return rc;
-        if ((rc = comm_allreduce(ctx, c, m->loc_f.p, ng, false, false)) != OATK_OK) return rc;
-        CK(hipMemcpyAsync(m->ec_cov.p, m->loc_c.as<uint32_t>() + first_me, no * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        CK(hipMemcpyAsync(m->ec_fwd.p, m->loc_f.as<uint32_t>() + first_me, no * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    }
+    if ((rc = R.light? ec_refresh_light(ctx, c, m, R) : ec_refresh_full(ctx, c, m, R)) != OATK_OK) return rc;
     if ((rc = comm_allreduce(ctx, c, m->st64.p, 12, true, false)) != OATK_OK) return rc;
     hipLaunchKernelGGL(mg_del_kernel, grid256(no), dim3(256), 0, ctx->stream, m->ec_fwd.as<uint32_t>(), no, m->ec_del.as<uint8_t>());
     uint64_t st[12];
@@ -1141,6 +1172,26 @@ static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, ui
     CK(hipStreamSynchronize(ctx->stream));
     CK(hipGetLastError());
     if (stats12) memcpy(stats12, st, sizeof(st));
+    return OATK_OK;
+}
+
+static int ec_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, double max_edist, uint32_t err_mer_c, uint32_t max_err_c, uint32_t err_arc_c,
+                           double max_arc_f, uint64_t *stats12, uint64_t *n_imported)
+{
+    int rc, rc_graph = OATK_OK;
+    if ((rc = comm_check(ctx, c, "oatk_hip_ec_sharded")) != OATK_OK) return rc;
+    if (!ctx->counted) { ctx->err = "oatk_hip_ec_sharded needs a resident scan + count"; return OATK_E_STATE; }
+    CK(hipSetDevice(ctx->device));
+    if (!ctx->multi || !ctx->multi->merged) { if ((rc = merge_counts_impl(ctx, c, nullptr)) != OATK_OK) return rc; }
+    MultiState *m = ctx->multi;
+    m->ec_done = false, m->table_root = -1;
+    if (n_imported) *n_imported = 0;
+    const bool light = err_mer_c > 0 && err_arc_c >= err_mer_c && max_err_c >= err_mer_c && !getenv("OATK_DEBUG_FULL_GRAPH");
+    EcRound R = {m->n_global, ctx->n_scm_total, m->n_owned, 0, (uint32_t) m->first_id[c->rank], err_mer_c, ctx->n_occ == 0, light};
+    if ((rc = ec_step0_cov_smers(ctx, c, m, R)) != OATK_OK) return rc;
+    if ((rc = ec_step1_graph(ctx, c, m, R, max_err_c, err_arc_c, max_arc_f, &rc_graph)) != OATK_OK) return rc;
+    if ((rc = ec_step2_kmers(ctx, c, m, R, rc_graph, n_imported)) != OATK_OK) return rc;      // (a bad rc_graph comes back from here, agreed on by every rank)
+    if ((rc = ec_step3_correct(ctx, c, m, R, max_edist, stats12)) != OATK_OK) return rc;
     m->ec_done = true;
     return OATK_OK;
 }

@@ -98,14 +98,7 @@ __global__ void mgt_seg_head_kernel(uint64_t n, const uint64_t *skeys, const uin
     const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) head[i] = skeys[i] != EGR_INVALID && (i == 0 || skeys[i] != skeys[i - 1] || sdist[i] != sdist[i - 1]);
 }
-// a segment ends where the next one begins or where the fillers (sorted behind every pair) start
-__global__ void mgt_seg_emit_kernel(uint64_t n_seg, uint64_t n_valid, const uint32_t *head_pos, const uint64_t *skeys, const uint32_t *sdist, uint64_t *okey, uint64_t *oval)
-{
-    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_seg) return;
-    const uint64_t p = head_pos[i], q = i + 1 < n_seg? head_pos[i + 1] : n_valid;
-    okey[i] = skeys[p], oval[i] = (uint64_t) sdist[p] | (q - p) << 32;
-}
+// where the fillers (sorted behind every pair) start: the last segment ends there (egr_seg_emit_kernel)
 __global__ void mgt_first_invalid_kernel(const uint64_t *skeys, uint64_t n, uint64_t *out)
 {
     uint64_t lo = 0, hi = n;
@@ -262,8 +255,8 @@ static int asm_graph_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint32_t min_
         n_runs = nrn && last == EGR_INVALID? nrn - 1 : nrn;            // the fillers sort behind every pair and stay at home
     }
     uint64_t n_all = 0, chk = 0;
-    if ((rc = comm_gather_items(ctx, c, m->x[MX_U].p, n_runs, 8, m->x[MX_UA], &n_all)) != OATK_OK) return rc;
-    if ((rc = comm_gather_items(ctx, c, m->x[MX_C].p, n_runs, 4, m->x[MX_CA], &chk)) != OATK_OK) return rc;
+    if ((rc = comm_gather_cols(ctx, c, {{m->x[MX_U].p, &m->x[MX_UA], 8}}, n_runs, &n_all)) != OATK_OK) return rc;
+    if ((rc = comm_gather_cols(ctx, c, {{m->x[MX_C].p, &m->x[MX_CA], 4}}, n_runs, &chk)) != OATK_OK) return rc;
     // the same weighted keys on every rank: the same graph, the same verdict
     rc = ag_build(ctx, m->x[MX_UA].as<uint64_t>(), m->x[MX_CA].as<uint32_t>(), n_all, m->n_global, d_cov, d_del, min_k_cov, min_a_cov_f, n_vtx, n_arc);
     if (rc == OATK_E_SPLIT) c->agreed = true;
@@ -352,11 +345,11 @@ static int overlap_hist_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint32_t m
     uint64_t n_valid = 0;
     if (n) { CK(hipMemcpyAsync(&n_valid, m->x[MX_NR].as<uint64_t>() + 4, 8, hipMemcpyDeviceToHost, ctx->stream)); CK(hipStreamSynchronize(ctx->stream)); }
     XENSURE(MX_SEGK, (n_seg + 1) * 8); XENSURE(MX_SEGV, (n_seg + 1) * 8);
-    if (n_seg) hipLaunchKernelGGL(mgt_seg_emit_kernel, grid256(n_seg), dim3(256), 0, ctx->stream, n_seg, n_valid, m->x[MX_HPOS].as<uint32_t>(), g->keys2.as<uint64_t>(), g->dist2.as<uint32_t>(),
+    if (n_seg) hipLaunchKernelGGL(egr_seg_emit_kernel, grid256(n_seg), dim3(256), 0, ctx->stream, n_seg, n_valid, m->x[MX_HPOS].as<uint32_t>(), g->keys2.as<uint64_t>(), g->dist2.as<uint32_t>(),
                                   m->x[MX_SEGK].as<uint64_t>(), m->x[MX_SEGV].as<uint64_t>());
     uint64_t n_all = 0, chk = 0;
-    if ((rc = comm_gather_items(ctx, c, m->x[MX_SEGK].p, n_seg, 8, m->x[MX_SKA], &n_all)) != OATK_OK) return rc;        // rank order = call order
-    if ((rc = comm_gather_items(ctx, c, m->x[MX_SEGV].p, n_seg, 8, m->x[MX_SVA], &chk)) != OATK_OK) return rc;
+    if ((rc = comm_gather_cols(ctx, c, {{m->x[MX_SEGK].p, &m->x[MX_SKA], 8}}, n_seg, &n_all)) != OATK_OK) return rc;        // rank order = call order
+    if ((rc = comm_gather_cols(ctx, c, {{m->x[MX_SEGV].p, &m->x[MX_SVA], 8}}, n_seg, &chk)) != OATK_OK) return rc;
     rc = ovl_build(ctx, m->x[MX_SKA].as<uint64_t>(), nullptr, m->x[MX_SVA].as<uint64_t>(), n_all, n_pairs, n_entries);
     if (rc == OATK_E_SPLIT) c->agreed = true;           // (identical input on every rank)
     return rc;
@@ -415,8 +408,8 @@ static int stat_sharded_one(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, cons
     }
     XENSURE(MX_ST_RU, (nrecv + 1) * 8); XENSURE(MX_ST_RC, (nrecv + 1) * 4); XENSURE(MX_ST_SU, (nrecv + 1) * 8); XENSURE(MX_ST_SC, (nrecv + 1) * 4);
     XENSURE(MX_ST_OU, (nrecv + 1) * 8); XENSURE(MX_ST_OC, (nrecv + 1) * 4);
-    if ((rc = comm_exchange(ctx, c, m->x[MX_ST_U].p, send_off, m->x[MX_ST_RU].p, recv_off, 8)) != OATK_OK) return rc;
-    if ((rc = comm_exchange(ctx, c, m->x[MX_ST_C].p, send_off, m->x[MX_ST_RC].p, recv_off, 4)) != OATK_OK) return rc;
+    if ((rc = comm_exchange_cols(ctx, c, {{m->x[MX_ST_U].p, m->x[MX_ST_RU].p, 8}}, send_off, recv_off)) != OATK_OK) return rc;
+    if ((rc = comm_exchange_cols(ctx, c, {{m->x[MX_ST_C].p, m->x[MX_ST_RC].p, 4}}, send_off, recv_off)) != OATK_OK) return rc;
     uint32_t n_own = 0;
     CK(hipMemsetAsync(m->x[MX_ST_HIST].p, 0, (OATK_STAT_MAX_DEPTH + 2) * 8, ctx->stream));
     if (nrecv) {
@@ -441,7 +434,7 @@ static int stat_sharded_one(oatk_hip_ctx *ctx, oatk_comm *c, MultiState *m, cons
     *no_singleton = 0;
     if (*uniq_out && hist_out[1] == 0) {                  // (the same test on every rank) replay the reference's count table over every distinct key
         uint64_t n_all = 0;
-        if ((rc = comm_gather_items(ctx, c, m->x[MX_ST_OC].p, n_own, 4, m->x[MX_ST_CALL], &n_all)) != OATK_OK) return rc;
+        if ((rc = comm_gather_cols(ctx, c, {{m->x[MX_ST_OC].p, &m->x[MX_ST_CALL], 4}}, n_own, &n_all)) != OATK_OK) return rc;
         std::vector<uint32_t> cc(n_all);
         if (n_all) CK(hipMemcpyAsync(cc.data(), m->x[MX_ST_CALL].p, (size_t) n_all * 4, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));

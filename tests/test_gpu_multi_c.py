@@ -324,3 +324,123 @@ def test_a_rank_that_fails_mid_way_releases_its_peers(tmp_path):
     env = dict(os.environ, OATK_RCCL_LIB=lib, OATK_DEBUG_FAIL_RANK="1,5")
     p = subprocess.run([sys.executable, os.path.join(here, "mock_rccl_abort.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0 and p.stdout.strip().startswith(b"ok"), (p.returncode, p.stdout[-300:], p.stderr.decode(errors="replace")[-1500:])
+
+
+def in_threads(world, work):
+    """work(rank) on one thread per rank; no thread may be left in a collective, no rank may raise"""
+    errs = []
+
+    def guarded(rank):
+        try:
+            work(rank)
+        except Exception as ex:                          # noqa: BLE001
+            errs.append((rank, ex))
+
+    th = [threading.Thread(target=guarded, args=(r,)) for r in range(world)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=300)
+    assert not any(t.is_alive() for t in th), "a rank hangs in a collective"
+    assert not errs, errs
+
+
+# What oatk_hip_ec_sharded enters on CASES[3] (a rank without syncmers, candidates, no rank short of a k-mer: nc > 0, nu == 0), as oatk_comm_traffic counts
+# it: all-gathers of numbers, all-gathers of ranges, all-reduces, exchanges.  Recorded by running the test below on the commit BEFORE the round was split into
+# one function per step (ec_sharded_impl as one function): the split must not add or drop a collective.
+EC_SHARDED_COLLECTIVES = {"light": (4, 3, 3, 1), "full": (4, 4, 3, 0)}
+
+
+@pytest.mark.parametrize("graph", ["light", "full"])
+def test_every_rank_enters_the_same_collectives(graph, monkeypatch):
+    """A rank that enters one collective more or fewer than its peers hangs them, so the number of collectives of a call is a property of the call, not of
+    a rank's data: the rank of CASES[3] that holds no read counts what the others count.  The table merge enters two plans and the verdict (3 all-gathers of
+    numbers), the three-column exchange and three single ones (4), whatever the data; the correction round's figures depend on nc, nu and the graph form."""
+    if graph == "full":
+        monkeypatch.setenv("OATK_DEBUG_FULL_GRAPH", "1")
+    K, S, c, mk, frac = CASES[3][:5]
+    reads = mk()
+    bounds = [int(round(f * len(reads))) for f in frac]
+    world = len(bounds) - 1
+    L = _lib.load()
+    grp = L.oatk_comm_group_create(world)
+    assert grp
+    merge, ec, imported = [None] * world, [None] * world, [0] * world
+
+    def work(rank):
+        h = HipSyncasm(0)
+        comm = L.oatk_comm_group_rank(grp, rank)
+        seq, off, lens = pack_reads(reads[bounds[rank]:bounds[rank + 1]])
+        h.scan_host(seq, off, lens, K, S, sid0=bounds[rank])
+        h.count()
+        t = (C.c_uint64 * 8)()
+        L.oatk_comm_traffic(comm, None, 1)
+        h.merge_counts(comm)
+        L.oatk_comm_traffic(comm, t, 1)
+        merge[rank] = list(t)
+        _, imported[rank] = h.ec_sharded(comm, 0.02, c, 0.35)
+        L.oatk_comm_traffic(comm, t, 1)
+        ec[rank] = list(t)
+        L.oatk_comm_destroy(comm)
+        h.close()
+
+    try:
+        in_threads(world, work)
+    finally:
+        L.oatk_comm_group_destroy(grp)
+    print("traffic %s merge_counts %s ec_sharded %s imported %s" % (graph, merge, ec, imported))
+    assert bounds[1] == bounds[2]                  # the input is what it is chosen for: a rank without a read
+    assert [tuple(t[0::2]) for t in merge] == [(3, 0, 0, 4)] * world
+    assert [tuple(t[0::2]) for t in ec] == [EC_SHARDED_COLLECTIVES[graph]] * world
+
+
+@pytest.mark.parametrize("graph", ["light", "full"])
+def test_a_refused_graph_is_refused_by_every_rank(hip, graph, monkeypatch):
+    """The graph's verdict is reached in step 1 of the round and travels with step 2's counts: every rank returns OATK_E_SPLIT together (the refusal is
+    requested: OATK_DEBUG_REFUSE, bit 1), nobody is left in a collective and the communicator is not poisoned -- the same handles and communicator run the
+    round again once the request is gone, and the result is one handle's."""
+    if graph == "full":
+        monkeypatch.setenv("OATK_DEBUG_FULL_GRAPH", "1")
+    K, S, c = CASES[0][:3]
+    reads = A.hifi_like(120, 30000, 4000, seed=307, err=0.004)
+    world = 2
+    L = _lib.load()
+    grp = L.oatk_comm_group_create(world)
+    assert grp
+    hs, comms, rcs, out = [None] * world, [None] * world, [None] * world, [None] * world
+
+    def round_of(rank):
+        st, ni = np.zeros(12, np.uint64), C.c_uint64()
+        return L.oatk_hip_ec_sharded(hs[rank].h, comms[rank], 0.02, c, 10 * c, c, 0.35, st.ctypes.data, C.byref(ni)), st
+
+    def refused(rank):
+        hs[rank], comms[rank] = HipSyncasm(0), L.oatk_comm_group_rank(grp, rank)
+        lo, hi = len(reads) * rank // world, len(reads) * (rank + 1) // world
+        seq, off, lens = pack_reads(reads[lo:hi])
+        hs[rank].scan_host(seq, off, lens, K, S, sid0=lo)
+        hs[rank].count()
+        rcs[rank] = round_of(rank)[0]
+
+    def again(rank):
+        rc, st = round_of(rank)
+        assert rc == _lib.OK, hs[rank].L.oatk_hip_last_error(hs[rank].h)
+        out[rank] = (hs[rank].multi_range(), st, {k: hs[rank].fetch(k) for k in ("MG_H", "EC_KMER", "MG_EC_COV")})
+
+    try:
+        monkeypatch.setenv("OATK_DEBUG_REFUSE", "1")
+        in_threads(world, refused)
+        assert rcs == [_lib.E_SPLIT] * world
+        monkeypatch.delenv("OATK_DEBUG_REFUSE")
+        in_threads(world, again)
+    finally:
+        for rank in range(world):
+            if comms[rank]:
+                L.oatk_comm_destroy(comms[rank])
+            if hs[rank]:
+                hs[rank].close()
+        L.oatk_comm_group_destroy(grp)
+    cnt, st, want = single(hip, reads, K, S, c)
+    assert out[0][0][2] == cnt["n_scm"] and out[0][1][:11].tolist() == st[:11].tolist()
+    assert np.array_equal(np.concatenate([o[2]["MG_H"] for o in out]), cnt["h"])
+    assert np.array_equal(np.concatenate([o[2]["EC_KMER"] for o in out]), want["EC_KMER"])
+    assert np.array_equal(np.concatenate([o[2]["MG_EC_COV"] for o in out]), want["EC_SCM_COV"])
