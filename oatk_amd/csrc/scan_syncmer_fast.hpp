@@ -17,6 +17,10 @@
 //    only for the positions where some lane of the wave passes it -- about one per wave and tile on random sequence (closed syncmers have
 //    density 2/(w+1) = 1/486), every position inside a tandem repeat, at the same price per position.  (Until r03h the wave decided its
 //    candidates together, one after the other: 11.5 % of the kernel's time for two positions in a thousand.)
+//  * in front of the eight positions stands the same condition for the lane's whole chunk, once per kind (r24): the chunk's minimum against the Close
+//    bound (exact), the minima of the window starts against the two Open bounds (necessary).  A wave in which no lane passes either -- one tile in three
+//    -- skips the positions; otherwise the loop runs in the form of the kinds the wave holds (Close only, Open only, both), the other half of the rule
+//    being dead code there.  Ranks and the wave's count of syncmers are worked out only in a wave that found some, from the lane mask where no lane has two.
 //  * the ring holds TOP WORDS only (16 KB + pad words; whole hashes were 33 KB and four workgroups per CU).  Top words that tie send a
 //    position to the rule on full 64-bit hashes, lane by lane: a value whose top word equals the one it is compared with is hashed again from the
 //    read's packed bases, and the whole chunks of the window come from 64-bit chunk minima the hashing phase leaves in a 4 KB ring.
@@ -60,6 +64,7 @@ static inline int syncmer_fast_ring(int K, int S)
 #define OATK_DPP_ROW_BCAST15 0x142
 #define OATK_DPP_ROW_BCAST31 0x143
 #define OATK_ICMP_ULE 37                  // llvm::CmpInst::ICMP_ULE, for __builtin_amdgcn_uicmp
+#define OATK_ICMP_NE 33                   // llvm::CmpInst::ICMP_NE
 
 template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ uint32_t dpp_u32(uint32_t old, uint32_t src)
@@ -470,18 +475,23 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
 #pragma unroll
                 for (int j = 0; j < 2 * C - SH; ++j) W[j] = all[SH + j];
             }
-            // the minimum of the chunk before the lane's own (Open with o < r): the neighbour lane's, or for lane 0 the last chunk of the wave before
-            uint32_t cprev = 0xFFFFFFFFu;
-            if (RR > 0) {
-                const uint32_t lb = ld32(suf32, (o_cs - 4u) & (uint32_t) (NCH * 4 - 1));         // (the suffix minimum of a block's last chunk is that chunk's own)
-                cprev = dpp_u32<0x138>(lb, cmin_keep);       // wave_shr:1 with old = lb: lane 0 has no source lane and keeps lb -- one v_mov_dpp, no select
-            }
             // per position: a cheap necessary condition -- a minimum and two compares whose results are LANE MASKS in scalar registers, or'ed and tested there --
             // and the rule itself only where some lane of the wave passes it: about one position per wave and tile on random sequence.
             // (r04: written on the masks themselves.  As `bool c = ...; if (__ballot(c))` the compiler rebuilt c as a vector 0/1 and compared that again, and
             //  carried the end-of-read test of the two edge waves of a read through every wave under a saved exec mask: eleven VALU per position, not three.)
             const bool edge = !(wb + 1 >= K && (uint32_t) (wb + OATK_WAVE * C) <= hl);         // k-mers that do not fit the read: E + 1 < K, E >= hoco_l
-            auto decide = [&](auto at_edge) __attribute__((always_inline)) {
+            // KIND: which candidates the WAVE may hold (bit 0 Close, bit 1 Open; decided below, where the forms are chosen).  The half of the rule that belongs
+            // to a kind no lane of the wave has a candidate of is dead code in that form.
+            auto decide = [&](auto at_edge, auto kind_tag) __attribute__((always_inline)) {
+                constexpr int KIND = decltype(kind_tag)::value;
+                // the minimum of the chunk before the lane's own (Open with o < r): the neighbour lane's, or for lane 0 the last chunk of the wave before.  Fetched
+                // here, by the forms that know Open (the branch that leads here is the wave's: every lane is present for the shift) -- a wave without a
+                // candidate, and one with Close candidates only, never looks at it (r24)
+                uint32_t cprev = 0xFFFFFFFFu;
+                if ((KIND & 2) && RR > 0) {
+                    const uint32_t lb = ld32(suf32, (o_cs - 4u) & (uint32_t) (NCH * 4 - 1));         // (the suffix minimum of a block's last chunk is that chunk's own)
+                    cprev = dpp_u32<0x138>(lb, cmin_keep);       // wave_shr:1 with old = lb: lane 0 has no source lane and keeps lb -- one v_mov_dpp, no select
+                }
 #pragma unroll
                 for (int o = 0; o < C; ++o) {
                     const uint32_t yhi = y[o], fhi = W[o];
@@ -489,7 +499,7 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
                     const uint32_t fy = fb < yhi? fb : yhi;
                     // (the compares as the intrinsic that returns the lane mask: as `__ballot(bool)` the two of position 0, which both copies of this loop
                     //  share, were hoisted above the branch that chooses the copy and came back as v_cndmask 0 / 1 + v_cmp_ne each -- r04's pathology, r21)
-                    uint64_t cand = __builtin_amdgcn_uicmp(yhi, backF, OATK_ICMP_ULE) | __builtin_amdgcn_uicmp(fhi, fy, OATK_ICMP_ULE);
+                    uint64_t cand = ((KIND & 1)? __builtin_amdgcn_uicmp(yhi, backF, OATK_ICMP_ULE) : 0ULL) | ((KIND & 2)? __builtin_amdgcn_uicmp(fhi, fy, OATK_ICMP_ULE) : 0ULL);
                     bool fits = true;
                     if (decltype(at_edge)::value) {
                         fits = (uint32_t) (i0 + o) < hl && i0 + o + 1 >= K;
@@ -499,7 +509,7 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
                     if (!a.want_n) cand = 0;                // (timing experiment: nothing survives the filter)
 #endif
                     if (cand) {
-                        const bool c = (yhi <= backF || fhi <= fy) && fits;
+                        const bool c = (((KIND & 1) && yhi <= backF) || ((KIND & 2) && fhi <= fy)) && fits;
                         uint32_t pmin = 0xFFFFFFFFu;        // the lane's own positions before E
 #pragma unroll
                         for (int j = 0; j < o; ++j) pmin = y[j] < pmin? y[j] : pmin;
@@ -514,19 +524,49 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
                             for (int j = RR; j < RR + C; ++j) head = W[j] < head? W[j] : head;
                         }
                         const uint32_t hb = head < backF? head : backF, bh = hb < pmin? hb : pmin;
-                        const bool cl = yhi < bh, tie_c = yhi == bh;
+                        const bool cl = (KIND & 1) && yhi < bh, tie_c = (KIND & 1) && yhi == bh;
                         // Open: M[lo] against everything else in the window and M[E]
                         const uint32_t tailp = o < RR? (cprev < pmin? cprev : pmin) : pmin;
                         const uint32_t rf = rest < fb? rest : fb, rh = rf < tailp? rf : tailp;
-                        const bool le = fhi <= rh && fhi <= yhi, op = fhi < rh && fhi < yhi;
+                        const bool le = (KIND & 2) && fhi <= rh && fhi <= yhi, op = (KIND & 2) && fhi < rh && fhi < yhi;
                         const bool tie = tie_c || (le && !op);
                         const uint32_t k = tie? 0u : (cl && op? 0u : (cl? 1u : (op? 2u : 0u)));
-                        if (c) kinds |= k << (2 * o), tiemask |= (tie? 1u : 0u) << o;
+                        // (a single-kind form takes the result by select: there c's lane mask IS cand, and under `if (c)` the compiler folds the two tests into one
+                        //  exec mask and leaves the bodies of positions 0 and 1, which are short, without a branch round them -- eighteen VALU issued by every
+                        //  wave that enters the form.  With the select the body stays behind the wave's branch on cand, as in the form that knows both.  r24)
+                        if (KIND == 3) { if (c) kinds |= k << (2 * o), tiemask |= (tie? 1u : 0u) << o; }
+                        else kinds |= (c? k : 0u) << (2 * o), tiemask |= (c && tie? 1u : 0u) << o;
                     }
                 }
             };
-            // (two copies, chosen by a scalar branch: the ordinary one knows nothing of read ends)
-            if (edge) decide(std::true_type()); else decide(std::false_type());
+            // The filter in two stages (r24).  Before any position is looked at, the lane asks of its whole chunk whether a candidate of either kind can be in it:
+            //   Close: `yhi <= backF` holds at some position of the chunk if and only if the chunk's minimum does -- cmin_keep, the minimum of this very y[]
+            //          (taken after the edge form set the positions where no s-mer ends to MAX).  One compare, exact.
+            //   Open:  position o needs W[o] <= min(fb, y[o]) with fb = fwd0 where o + SH < C and fwd1 otherwise.  Without y[o] that is a necessary condition
+            //          per group of positions: min(W[o]: o + SH < C) <= fwd0, or min(W[o]: the rest) <= fwd1 (no second group when SH = 0).
+            // Both are lane masks, or'ed and tested in scalar registers.  On random sequence a wave-tile holds 512 / 486 = 1.05 closed syncmers, so no lane of the
+            // wave passes either test in about one tile of three (e^-1.05): the eight positions are skipped whole.  Otherwise the loop runs in the form of the
+            // kinds the WAVE holds -- a form without a kind computes exactly what the full form does, because the dropped half is false in every lane:
+            //   no Open mask in the wave: W[o] > fb at every position of every lane.  rh <= rf <= fb, so `fhi <= rh` is false: le, op and the Open half of
+            //          cand and c are false, and tie is tie_c.
+            //   no Close mask in the wave: yhi > backF at every position of every lane.  bh <= hb <= backF, so `yhi < bh` and `yhi == bh` would both give
+            //          yhi <= backF: cl and tie_c are false, and so is the Close half of cand and c.
+            // The waves at a read's ends keep the form that knows both: two waves per read, and a third copy of the edge loop would buy nothing.
+            uint32_t wA = 0xFFFFFFFFu, wB = 0xFFFFFFFFu;
+#pragma unroll
+            for (int o = 0; o < C; ++o) { if (o + SH < C) wA = W[o] < wA? W[o] : wA; else wB = W[o] < wB? W[o] : wB; }
+            const uint64_t c_any = __builtin_amdgcn_uicmp(cmin_keep, backF, OATK_ICMP_ULE);
+            const uint64_t o_any = __builtin_amdgcn_uicmp(wA, fwd0, OATK_ICMP_ULE) | (SH? __builtin_amdgcn_uicmp(wB, fwd1, OATK_ICMP_ULE) : 0ULL);
+            using KClose = std::integral_constant<int, 1>;
+            using KOpen = std::integral_constant<int, 2>;
+            using KBoth = std::integral_constant<int, 3>;
+            if (c_any | o_any) {
+                // (the ordinary forms know nothing of read ends)
+                if (edge) decide(std::true_type(), KBoth());
+                else if (!o_any) decide(std::false_type(), KClose());
+                else if (!c_any) decide(std::false_type(), KOpen());
+                else decide(std::false_type(), KBoth());
+            }
         }
         // Top words tied: ~2^-28 per candidate on random sequence, but the rule rather than the exception inside tandem repeats
         // (telomeres, microsatellites), where the window minimum comes back every period and every lane of the wave holds ties.
@@ -610,11 +650,25 @@ __global__ __launch_bounds__(NT, OATK_SYF_WAVES) void syncmer_fast_kernel(SynArg
 #if OATK_SYF_EXP == 5
         kinds &= (uint32_t) -a.want_n;                  // (timing experiment: candidates are decided, none becomes a syncmer)
 #endif
-        const uint32_t ns = (uint32_t) __builtin_popcount((kinds | kinds >> 1) & 0x5555u);
-        const uint32_t incl = wave_incl_sum_dpp(ns, lane);
-        const uint32_t wtot = (uint32_t) __builtin_amdgcn_readlane((int) incl, 63);
+        // A lane's rank among the wave's syncmers and the wave's total, only where the wave found any (one tile in three finds none: r24): the count of zero
+        // is still stored -- the other waves read it --, and pend_rank is only looked at by lanes that hold a syncmer.  Where no lane holds two, the rank is the
+        // number of lanes with one below this lane and the total a scalar popcount of the mask; the wave scan is kept for what is left.
+        uint32_t wtot = 0, rank = 0;
+        const uint64_t has = __builtin_amdgcn_uicmp(kinds, 0u, OATK_ICMP_NE);
+        if (has) {
+            const uint32_t each = (kinds | kinds >> 1) & 0x5555u;            // one bit per syncmer of the lane
+            if (__builtin_amdgcn_uicmp(each & (each - 1u), 0u, OATK_ICMP_NE)) {
+                const uint32_t ns = (uint32_t) __builtin_popcount(each);
+                const uint32_t incl = wave_incl_sum_dpp(ns, lane);
+                wtot = (uint32_t) __builtin_amdgcn_readlane((int) incl, 63);
+                rank = incl - ns;
+            } else {
+                rank = __builtin_amdgcn_mbcnt_hi((uint32_t) (has >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) has, 0u));
+                wtot = (uint32_t) __builtin_popcountll(has);
+            }
+        }
         if (lane == 0) w_cnt[par][wid] = wtot;
-        pend_kinds = kinds, pend_rank = incl - ns, pend_I0 = I0, pend_wtot = wtot, pend_par = par, pend_any = 1u;
+        pend_kinds = kinds, pend_rank = rank, pend_I0 = I0, pend_wtot = wtot, pend_par = par, pend_any = 1u;
         par ^= 1u;
     }
     if (I0 < hl) {

@@ -5,7 +5,7 @@ tools/isa_mix.py counts the whole loop body, rare paths included; this walks the
 The path is given as one letter per conditional branch met on the way: T taken, N not taken.  Run it without --path first: it walks with N everywhere and
 prints every conditional branch it meets with its line in the listing, which is how a path is found (read the listing around each).  Instructions skipped
 under a cleared exec mask behind `s_cbranch_execz` are NOT issued when the branch is taken; instructions between `s_and_saveexec` and `s_or_b64 exec` with no
-branch round them are issued and counted.
+branch round them are issued and counted.  Blocks of the loop that the compiler has placed behind the loop's last line are followed there and back.
 
     python tools/isa_tile_path.py --form 2048,true,128,6 --path TNNT... [--header path/to/scan_syncmer_fast.hpp] [--marks]
 
@@ -90,11 +90,13 @@ def main():
             if taken:
                 if tgt == head:
                     break
-                assert head <= tgt <= back, "the path leaves the loop at listing line %d" % no
+                # (a block of the loop may stand BEHIND the loop's last line: the compiler moves blocks it holds to be cold there, and they come back with an
+                #  s_branch.  Such a block is followed like any other; a path that has left the loop for good runs into s_endpgm or the step limit.)
                 pc = tgt
                 continue
+        assert pc != back, "the path falls out of the loop at listing line %d (the loop's last branch is not taken)" % no
+        assert op != "s_endpgm", "the path leaves the loop and ends the kernel at listing line %d" % no
         pc += 1
-        assert pc <= back, "the path falls out of the loop"
     print("path: %d VALU, %.1f weighted issue cycles (%.2f per instruction)" % (n, cyc, cyc / n))
     for name, k in by.most_common():
         print("  %-28s %4d" % (name, k))
