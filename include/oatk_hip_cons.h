@@ -2,7 +2,7 @@
  * include/oatk_hip_cons.h -- C ABI of the base-space syncmer consensus on the device (scg_syncmer_consensus, syncasm.c:888-1003).
  *
  * Call after oatk_hip_count (reads as scanned) or after oatk_hip_ec (corrected chains: corrected entries are skipped, :958-959).
- * Reads sharded over GPUs are not supported yet: the totals of a syncmer are sums over all shards.
+ * With reads sharded over GPUs the totals of a syncmer are sums over all shards: oatk_hip_consensus_sharded (include/oatk_hip_multi.h) adds them up.
  */
 #ifndef OATK_HIP_CONS_H
 #define OATK_HIP_CONS_H
@@ -44,7 +44,32 @@ int oatk_hip_overlap_hist(oatk_hip_ctx *ctx, uint64_t *n_pairs, uint64_t *n_entr
 int oatk_hip_overlap_pairs(oatk_hip_ctx *ctx, const void **d_keys, const void **d_dist, uint64_t *n);
 int oatk_hip_overlap_hist_from_pairs(oatk_hip_ctx *ctx, const uint64_t *d_keys, const uint32_t *d_dist, uint64_t n, uint64_t *n_pairs, uint64_t *n_entries);
 
-enum { OATK_BUF_CONS_SEL = 140, OATK_BUF_CONS_SLOT, OATK_BUF_CONS_RL, OATK_BUF_CONS_MSEQ, OATK_BUF_CONS_FIRST, OATK_BUF_CONS_TOT };
+/* The strings of scg_consensus (syncasm.c:716-823) from the tables oatk_hip_consensus(ctx, min_cov) left resident: the text of every sequence of a plan, where
+ * a sequence is a list of pieces (syncmer id << 1 | rev, beg) -- what scg_unitig_consensus (:1004-1046) hands to scg_syncmer_consensus (:888-1001) one after the
+ * other -- and a piece reads as that function writes it: max(-beg, 0) letters N, then positions max(beg, 0) .. k - 1 of the oriented k-mer of the syncmer's first
+ * uncorrected occurrence, each base 1 + CONS_RL times in base space and once with hoco_seq; N's throughout when CONS_FIRST is ~0.  Only the plan goes to the
+ * device and only the text comes back; CONS_RL stays where it is.  Results stay resident:
+ *   CONS_STR        u8[total]        ASCII, the sequences back to back
+ *   CONS_STR_OFF    u64[n_seq + 1]   where sequence i starts in CONS_STR
+ *   CONS_STR_LEN    u64[n_seq]       what scg_unitig_consensus returns, also for a sequence with want_bytes 0; ~0 when refused
+ *   CONS_STR_STATUS u8[n_seq]        1: a piece's syncmer has no prepared consensus (CONS_SLOT is ~0); the sequence is refused
+ * Length-only and refused sequences take no bytes of CONS_STR; *n_refused counts the refused ones and the call still returns OATK_OK.
+ * OATK_E_STATE: no oatk_hip_consensus on the resident batch, or reads sharded over GPUs (oatk_hip_ec_set_global).  OATK_E_ARG, nothing launched: the offsets do
+ * not ascend from 0 to n_piece, an id is not below the number of syncmers, or a beg is not below k (the reference asserts that). */
+typedef struct { uint64_t n_seq, n_piece;
+                 const uint64_t *seq_off;     /* [n_seq + 1] pieces of sequence i                      */
+                 const uint64_t *piece_v;     /* [n_piece] syncmer id << 1 | rev                       */
+                 const int32_t  *piece_beg;   /* [n_piece] < k, may be negative                        */
+                 const uint8_t  *want_bytes;  /* [n_seq] 0: length only (arc overlaps), NULL = all 1   */
+} oatk_cons_plan_t;                           /* HOST pointers, graph-sized */
+int oatk_hip_consensus_strings(oatk_hip_ctx *ctx, const oatk_cons_plan_t *plan, int hoco_seq,
+                               uint64_t *total_bytes, uint64_t *n_refused);
+/* milliseconds the length kernel and the fill kernel of the last oatk_hip_consensus_strings took (0 unless oatk_hip_set_timing was on), and the pieces of its plan
+ * (n_piece may be NULL) */
+int oatk_hip_consensus_strings_times(oatk_hip_ctx *ctx, float *ms2, uint64_t *n_piece);
+
+enum { OATK_BUF_CONS_SEL = 140, OATK_BUF_CONS_SLOT, OATK_BUF_CONS_RL, OATK_BUF_CONS_MSEQ, OATK_BUF_CONS_FIRST, OATK_BUF_CONS_TOT,
+       OATK_BUF_CONS_STR, OATK_BUF_CONS_STR_OFF, OATK_BUF_CONS_STR_LEN, OATK_BUF_CONS_STR_STATUS };
 enum { OATK_BUF_OVL_KEY = 150, OATK_BUF_OVL_OFF, OATK_BUF_OVL_DIST, OATK_BUF_OVL_CNT, OATK_BUF_OVL_TAIL };
 
 #ifdef __cplusplus

@@ -213,6 +213,18 @@ int oatk_calc_syncmer_overlap(const oatk_overlap_t *o, uint64_t v, uint64_t w, o
 int64_t oatk_scg_unitig_consensus(const oatk_consensus_t *cs, const oatk_overlap_t *o, const oatk_sr_db_t *sr_db, const uint64_t *v, uint64_t n,
                                   oatk_kstring_t *c_seq, int hoco_seq);
 
+/* scg_consensus (syncasm.c:716-823) as a whole, after oatk_hip_consensus(ctx, min_cov) on the resident batch and with the pair tables `o` of the same batch:
+ * the text of every live unitig (the positions of its syncmers from oatk_calc_syncmer_overlap, the skip loop of :1030-1039 making pieces of them), the consensus
+ * length of every live arc's overlap -- its ln syncmers (:785-787) or the overlap of its two end syncmers (:794-800) -- all in ONE device call
+ * (include/oatk_hip_cons.h: oatk_hip_consensus_strings); only the text and three graph-sized arrays come back, the run-length table stays on the device.  Then the
+ * graph is written as the reference writes it: asmg_clean_consensus, vtx.len, vtx.cov (kept when set, else utg_avg_cov, :630-664), vtx.seq when save_seq
+ * (malloc'ed and NUL-terminated: scg_destroy frees it), arc.ls = min(l, len_v, len_w) on the arc and its complement, and to fo (may be NULL) the H, S and L lines
+ * of :738, :766 and :814-815.  `g` is declared below (oatk_scg_t).  OATK_E_SPLIT: a syncmer of the graph has no prepared consensus (coverage below min_cov), or a
+ * piece would begin at or behind position k; OATK_E_ARG: an arc without its complement, or ln beyond its unitig.  Unless OATK_OK is returned the graph is exactly
+ * as it was and nothing was written to fo: the caller runs the original. */
+struct oatk_scg_s;
+int oatk_scg_consensus(oatk_hip_ctx *ctx, const oatk_overlap_t *o, const oatk_sr_db_t *sr_db, struct oatk_scg_s *g, int hoco_seq, int save_seq, FILE *fo);
+
 /* scg_read_alignment (alignment.c:596-691) on the device (include/oatk_hip_align.h): `g` is the reference's scg_t with its unitig graph
  * and syncmer -> unitig index as they are at the time of the call, `ra_v` the previous alignments (read when for_unzip, replaced by the
  * new ones).  The reads aligned are the chains resident in ctx, which must be the whole of sr_db.  Layout-compatible mirrors of syncasm.h:51-80.
@@ -220,7 +232,7 @@ int64_t oatk_scg_unitig_consensus(const oatk_consensus_t *cs, const oatk_overlap
  * 128 fragments, 6 equally good predecessors, 48 fragments in a chain) and got no alignment: the caller runs the original routine for
  * them (none on HiFi data so far).  With skipped == NULL the call is all or nothing: if any read was skipped it returns OATK_E_SPLIT
  * (*n_skipped set) and leaves ra_v as it was, so the caller can run the original routine on the untouched state. */
-typedef struct {
+typedef struct oatk_scg_s {
     oatk_syncmer_db_t *scm_db;
     oatk_asmg_t *utg_asmg;
     void *scm_u;           /* uint128_t *: scm_id[49] | scm_rev[1] | utg_id[42] | utg_pos[36] */

@@ -25,7 +25,8 @@ BUF.update({name: 100 + i for i, name in enumerate([
 BUF.update({name: 160 + i for i, name in enumerate(["INGEST_SEQ", "INGEST_OFF", "INGEST_LEN", "INGEST_HDR"])})
 FMT_AUTO, FMT_FASTA, FMT_FASTQ = 0, 1, 2
 # include/oatk_hip_cons.h
-BUF.update({name: 140 + i for i, name in enumerate(["CONS_SEL", "CONS_SLOT", "CONS_RL", "CONS_MSEQ", "CONS_FIRST", "CONS_TOT"])})
+BUF.update({name: 140 + i for i, name in enumerate(["CONS_SEL", "CONS_SLOT", "CONS_RL", "CONS_MSEQ", "CONS_FIRST", "CONS_TOT",
+                                                    "CONS_STR", "CONS_STR_OFF", "CONS_STR_LEN", "CONS_STR_STATUS"])})
 # include/oatk_hip_align.h
 BUF.update({name: 200 + i for i, name in enumerate(["RA_ALN_SID", "RA_ALN_OFF", "RA_ALN_S", "RA_FRG_UID", "RA_FRG_UBEG", "RA_FRG_UEND", "RA_FRG_SBEG", "RA_FRG_SEND", "RA_SKIPPED"])})
 BUF.update({name: 150 + i for i, name in enumerate(["OVL_KEY", "OVL_OFF", "OVL_DIST", "OVL_CNT", "OVL_TAIL"])})
@@ -54,7 +55,7 @@ EXPORTS = [
     "oatk_hip_asm_graph", "oatk_hip_asm_pairs", "oatk_hip_asm_graph_from_pairs", "oatk_hip_overlap_hist", "oatk_hip_overlap_pairs", "oatk_hip_overlap_hist_from_pairs", "oatk_hip_read_alignment", "oatk_hip_debug_align_two_pass",
     "oatk_hip_ra_utg_coverage", "oatk_hip_ra_arc_coverage", "oatk_hip_debug_racov_cap", "oatk_hip_ra_utg_coverage_sharded", "oatk_hip_ra_arc_coverage_sharded",
     "oatk_hip_ra_triplet_scores", "oatk_hip_ra_triplet_scores_sharded",
-    "oatk_hip_ec_keep_seq", "oatk_hip_ec_corrected_reads",
+    "oatk_hip_ec_keep_seq", "oatk_hip_ec_corrected_reads", "oatk_hip_consensus_strings", "oatk_hip_consensus_strings_times",
     "oatk_hip_inflate_bgzf", "oatk_hip_inflate_bgzf_host", "oatk_hip_inflate_last_byte", "oatk_hip_ingest_names",
     "oatk_hip_ingest_bam", "oatk_hip_ingest_bam_host", "oatk_hip_ingest_bam_stats", "oatk_hip_ingest_bam_times",
 ]
@@ -135,6 +136,12 @@ class RacovAln(C.Structure):
 class RacovReads(C.Structure):
     """oatk_racov_reads_t: the reads' chains back to back"""
     _fields_ = [("n_reads", C.c_uint64), ("off", C.c_void_p), ("k_mer", C.c_void_p)]
+
+
+class ConsPlan(C.Structure):
+    """oatk_cons_plan_t (include/oatk_hip_cons.h): the sequences whose text oatk_hip_consensus_strings makes, host pointers"""
+    _fields_ = [("n_seq", C.c_uint64), ("n_piece", C.c_uint64), ("seq_off", C.c_void_p), ("piece_v", C.c_void_p), ("piece_beg", C.c_void_p),
+                ("want_bytes", C.c_void_p)]
 
 
 class StatRaw(C.Structure):
@@ -247,6 +254,8 @@ def load():
     L.oatk_hip_ec_reserve_import.argtypes = [vp, C.c_uint64]
     L.oatk_hip_consensus.argtypes = [vp, C.c_uint32]
     L.oatk_hip_consensus_ids.argtypes = [vp, vp, C.c_uint64]
+    L.oatk_hip_consensus_strings.argtypes = [vp, C.POINTER(ConsPlan), C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.oatk_hip_consensus_strings_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
     L.oatk_hip_ingest.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.oatk_hip_ingest_host.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.oatk_hip_scan_ingested.argtypes = [vp, C.c_uint64, C.c_int, C.c_int]

@@ -76,6 +76,7 @@ struct oatk_hip_ctx {
     DevBuf tmp;           // rocprim temporary storage
     struct EcState *ec = nullptr;   // error-correction buffers (api_ec.inc)
     struct ConsState *cons = nullptr;   // consensus buffers (api_cons.inc)
+    struct ConsStrState *cstr = nullptr;   // consensus strings (api_consstr.inc)
     struct IngState *ing = nullptr;     // record scan buffers (api_ingest.inc)
     struct InfState *inf = nullptr;     // BGZF inflater buffers (api_inflate.inc)
     struct StatState *stat = nullptr;   // scan statistics buffers (api_stat.inc)
@@ -131,6 +132,7 @@ static void t_collect(oatk_hip_ctx *ctx, int first, int last)
 #include "api_ec.inc"
 #include "api_graph.inc"
 #include "api_cons.inc"
+#include "api_consstr.inc"
 #include "api_ovl.inc"
 #include "api_align.inc"
 #include "api_ingest.inc"
@@ -188,6 +190,7 @@ void oatk_hip_destroy(oatk_hip_ctx *ctx)
     (void) hipStreamSynchronize(ctx->stream);
     ec_state_free(ctx);
     cons_state_free(ctx);
+    consstr_state_free(ctx);
     ing_state_free(ctx);
     inf_state_free(ctx);
     stat_state_free(ctx);
@@ -484,6 +487,7 @@ static void scan_reset_downstream(oatk_hip_ctx *ctx)
     ctx->slots_packed = false;                 // (an append changes the per-slot arrays under the slot records)
     if (ctx->ec) ctx->ec->done = ctx->ec->marked = ctx->ec->graph_resident = ctx->ec->global = false;
     if (ctx->cons) ctx->cons->done = false;
+    if (ctx->cstr) ctx->cstr->done = false;
     if (ctx->ag) ctx->ag->done = false;
     if (ctx->ovl) ctx->ovl->done = false;
     if (ctx->ra) ctx->ra->done = false;
@@ -788,6 +792,7 @@ int oatk_hip_buffer(oatk_hip_ctx *ctx, int which, const void **d_ptr, uint64_t *
                 case OATK_BUF_SCM_OCC: p = ctx->scm_occ.p, b = occ * 8; break;
                 default:
                     if (which >= OATK_BUF_CONS_SEL && which <= OATK_BUF_CONS_TOT) return cons_buffer(ctx, which, d_ptr, bytes);
+                    if (which >= OATK_BUF_CONS_STR && which <= OATK_BUF_CONS_STR_STATUS) return consstr_buffer(ctx, which, d_ptr, bytes);
                     if (which >= OATK_BUF_AG_SCM_DEL && which <= OATK_BUF_AG_ARC_LINK) return ag_buffer(ctx, which, d_ptr, bytes);
                     if (which >= OATK_BUF_OVL_KEY && which <= OATK_BUF_OVL_TAIL) return ovl_buffer(ctx, which, d_ptr, bytes);
                     if (which >= OATK_BUF_RA_ALN_SID && which <= OATK_BUF_RA_SKIPPED) return ra_buffer(ctx, which, d_ptr, bytes);
