@@ -54,7 +54,7 @@ int oatk_hip_overlap_hist_from_pairs(oatk_hip_ctx *ctx, const uint64_t *d_keys, 
  *   CONS_STR_LEN    u64[n_seq]       what scg_unitig_consensus returns, also for a sequence with want_bytes 0; ~0 when refused
  *   CONS_STR_STATUS u8[n_seq]        1: a piece's syncmer has no prepared consensus (CONS_SLOT is ~0); the sequence is refused
  * Length-only and refused sequences take no bytes of CONS_STR; *n_refused counts the refused ones and the call still returns OATK_OK.
- * OATK_E_STATE: no oatk_hip_consensus on the resident batch, or reads sharded over GPUs (oatk_hip_ec_set_global).  OATK_E_ARG, nothing launched: the offsets do
+ * OATK_E_STATE: no oatk_hip_consensus on the resident batch, or reads sharded over GPUs (oatk_hip_ec_set_global; their form is oatk_hip_consensus_strings_sharded, include/oatk_hip_multi.h).  OATK_E_ARG, nothing launched: the offsets do
  * not ascend from 0 to n_piece, an id is not below the number of syncmers, or a beg is not below k (the reference asserts that). */
 typedef struct { uint64_t n_seq, n_piece;
                  const uint64_t *seq_off;     /* [n_seq + 1] pieces of sequence i                      */

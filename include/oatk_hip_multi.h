@@ -40,6 +40,7 @@
 #define OATK_HIP_MULTI_H
 
 #include "oatk_hip.h"
+#include "oatk_hip_cons.h"      /* oatk_cons_plan_t */
 
 #ifdef __cplusplus
 extern "C" {
@@ -131,7 +132,23 @@ int oatk_hip_overlap_hist_sharded(oatk_hip_ctx *ctx, oatk_comm *comm, uint32_t m
 struct oatk_stat_raw_s;
 int oatk_hip_stat_sharded(oatk_hip_ctx *ctx, oatk_comm *comm, struct oatk_stat_raw_s *out);
 
+/* oatk_hip_consensus_strings (include/oatk_hip_cons.h) for sharded reads, after oatk_hip_consensus_sharded; every rank makes the call with the same plan and is
+ * left with the same CONS_STR, CONS_STR_OFF, CONS_STR_LEN and CONS_STR_STATUS, byte for byte what one handle holding all the reads makes.  CONS_FIRST names a
+ * read of whichever rank, and only that rank holds the bases of the k-mer: the FIRST call after a consensus has every rank write the k-mers it holds into a
+ * table of all selected slots, zeros elsewhere, and all-reduces the table once (sum, 64-bit words: one rank contributes to a row) -- n_sel * 8 * ceil(k / 32)
+ * bytes, a sixteenth of the run-length totals oatk_hip_consensus_sharded all-reduces.  Later calls on the same consensus make no collective; the next
+ * consensus, sharded or not, drops the table.  CONS_KMER u8[n_sel * 8 * ceil(k / 32)]: per slot of CONS_SLOT the syncmer's k-mer in its forward
+ * orientation, four codes to a byte, the first in the top bits, zeros behind position k - 1 (and throughout where CONS_FIRST is ~0).
+ * The collective does not depend on the plan.  A plan the one-handle call refuses is refused here alike (OATK_E_ARG, no string kernel launched) by the rank that
+ * holds it, after the table: ranks that disagree about the plan do not wait for each other, and the communicator stays usable.  OATK_E_STATE: reads not
+ * sharded, or no oatk_hip_consensus_sharded on them (a call-order error: the communicator is aborted, as everywhere in this header). */
+int oatk_hip_consensus_strings_sharded(oatk_hip_ctx *ctx, oatk_comm *comm, const oatk_cons_plan_t *plan, int hoco_seq,
+                                       uint64_t *total_bytes, uint64_t *n_refused);
+/* milliseconds the k-mer kernel of the table at hand took (0 unless oatk_hip_set_timing was on) and the table's bytes; either may be NULL */
+int oatk_hip_consensus_kmer_time(oatk_hip_ctx *ctx, float *ms, uint64_t *table_bytes);
+
 enum { OATK_BUF_MG_G_H = 230, OATK_BUF_MG_G_S, OATK_BUF_MG_G_COV, OATK_BUF_MG_G_DEL, OATK_BUF_MG_G_OCC_OFF, OATK_BUF_MG_G_OCC, OATK_BUF_MG_POS_GKID };
+enum { OATK_BUF_CONS_KMER = 240 };
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,14 @@ oatk_asmg_t *oatk_multi_make_syncmer_asmg(oatk_multi *m, oatk_syncmer_db_t *scm_
  * the pairs whose two syncmers are alive and seen >= min_cov times -- every pair of neighbours in the graph made with that min_k_cov */
 oatk_consensus_t *oatk_multi_consensus_fetch(oatk_multi *m, uint32_t min_cov, int k, int *rc);
 oatk_overlap_t *oatk_multi_overlap_fetch(oatk_multi *m, uint32_t min_cov, int *rc);
+/* the consensus sums over all handles (oatk_hip_consensus_sharded), left resident: nothing is copied to the host */
+int oatk_multi_consensus(oatk_multi *m, uint32_t min_cov);
+/* scg_consensus (syncasm.c:716-823) as oatk_scg_consensus (include/oatk_syncasm.h) makes it on one handle, word for word, from the tables oatk_multi_consensus
+ * left resident: positions from `o`, one plan for the whole graph, the text made on every handle (oatk_hip_consensus_strings_sharded; the first call after a
+ * consensus exchanges the syncmers' own k-mers once, later calls nothing) and fetched from handle 0 -- the run-length table never leaves the devices.  Writes
+ * vtx.len, vtx.cov, vtx.seq (save_seq), arc.ls and, with fo, the GFA lines.  OATK_E_SPLIT: a syncmer of the graph has no prepared consensus, or a piece would
+ * begin at or behind position k; unless the code is OATK_OK the graph and fo are untouched. */
+int oatk_multi_scg_consensus(oatk_multi *m, const oatk_overlap_t *o, const oatk_sr_db_t *sr_db, oatk_scg_t *g, int hoco_seq, int save_seq, FILE *fo);
 /* scg_read_alignment (alignment.c:596): every handle aligns its own reads against the same graph, no exchange */
 int oatk_multi_scg_read_alignment(oatk_multi *m, oatk_sr_db_t *sr_db, oatk_scg_ra_v *ra_v, oatk_scg_t *g, int for_unzip, uint64_t *n_skipped);
 /* scg_ra_utg_coverage (syncasm.c:1882) and scg_ra_arc_coverage up to its refinement (:2067-2138), as oatk_scg_ra_utg_coverage / oatk_scg_ra_arc_coverage

@@ -38,6 +38,7 @@ BUF.update({name: 180 + i for i, name in enumerate([
 # include/oatk_hip_multi.h
 BUF.update({name: 220 + i for i, name in enumerate(["MG_H", "MG_S", "MG_COV", "MG_L2G", "MG_EC_COV", "MG_EC_DEL", "MG_LCOV"])})
 BUF.update({name: 230 + i for i, name in enumerate(["MG_G_H", "MG_G_S", "MG_G_COV", "MG_G_DEL", "MG_G_OCC_OFF", "MG_G_OCC", "MG_POS_GKID"])})
+BUF["CONS_KMER"] = 240
 TIMERS = ["hpc", "syncmer", "syncmer_n", "scan_post", "count_place", "count_sort", "count_group", "kmer_hash", "ec_graph", "ec_mark", "ec_solve", "ec_refresh"]
 
 EXPORTS = [
@@ -56,13 +57,14 @@ EXPORTS = [
     "oatk_hip_ra_utg_coverage", "oatk_hip_ra_arc_coverage", "oatk_hip_debug_racov_cap", "oatk_hip_ra_utg_coverage_sharded", "oatk_hip_ra_arc_coverage_sharded",
     "oatk_hip_ra_triplet_scores", "oatk_hip_ra_triplet_scores_sharded",
     "oatk_hip_ec_keep_seq", "oatk_hip_ec_corrected_reads", "oatk_hip_consensus_strings", "oatk_hip_consensus_strings_times",
+    "oatk_hip_consensus_strings_sharded", "oatk_hip_consensus_kmer_time",
     "oatk_hip_inflate_bgzf", "oatk_hip_inflate_bgzf_host", "oatk_hip_inflate_last_byte", "oatk_hip_ingest_names",
     "oatk_hip_ingest_bam", "oatk_hip_ingest_bam_host", "oatk_hip_ingest_bam_stats", "oatk_hip_ingest_bam_times",
 ]
 
 # the N-handle mirror in liboatk_host.so (include/oatk_multi.h) of entry points listed above; EXPORTS itself is checked against liboatk_hip.so
 HOST_EXPORTS = ["oatk_multi_scg_ra_utg_coverage", "oatk_multi_scg_ra_arc_coverage", "oatk_scg_multiplex_plan", "oatk_multi_scg_multiplex_plan",
-                "oatk_triplet_table_free", "oatk_multi_read_error_correction_fo", "oatk_bgzf_index", "oatk_host_set_device_inflate", "oatk_host_inflate_counts"]
+                "oatk_triplet_table_free", "oatk_multi_read_error_correction_fo", "oatk_multi_consensus", "oatk_multi_scg_consensus", "oatk_bgzf_index", "oatk_host_set_device_inflate", "oatk_host_inflate_counts"]
 
 
 def load_host():
@@ -86,6 +88,11 @@ def load_host():
     H.oatk_multi_read_error_correction_fo.argtypes = [vp, vp, vp, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, vp, vp]      # (..., FILE *fo, stats12)
     H.oatk_multi_make_syncmer_asmg.restype = vp
     H.oatk_multi_make_syncmer_asmg.argtypes = [vp, vp, C.c_uint32, C.c_double, C.POINTER(C.c_int)]
+    H.oatk_multi_overlap_fetch.restype = vp
+    H.oatk_multi_overlap_fetch.argtypes = [vp, C.c_uint32, C.POINTER(C.c_int)]
+    H.oatk_overlap_destroy.argtypes = [vp]
+    H.oatk_multi_consensus.argtypes = [vp, C.c_uint32]
+    H.oatk_multi_scg_consensus.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp]      # (m, overlap tables, sr_db, scg, hoco_seq, save_seq, FILE *fo)
     H.oatk_multi_scg_read_alignment.argtypes = [vp, vp, vp, vp, C.c_int, C.POINTER(C.c_uint64)]
     H.oatk_multi_scg_ra_utg_coverage.argtypes = [vp, vp, vp, vp, C.c_int]
     H.oatk_multi_scg_ra_arc_coverage.argtypes = [vp, vp, vp, vp, C.c_int]
@@ -256,6 +263,8 @@ def load():
     L.oatk_hip_consensus_ids.argtypes = [vp, vp, C.c_uint64]
     L.oatk_hip_consensus_strings.argtypes = [vp, C.POINTER(ConsPlan), C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.oatk_hip_consensus_strings_times.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+    L.oatk_hip_consensus_strings_sharded.argtypes = [vp, vp, C.POINTER(ConsPlan), C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.oatk_hip_consensus_kmer_time.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
     L.oatk_hip_ingest.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.oatk_hip_ingest_host.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.oatk_hip_scan_ingested.argtypes = [vp, C.c_uint64, C.c_int, C.c_int]

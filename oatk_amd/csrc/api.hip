@@ -141,6 +141,7 @@ static void t_collect(oatk_hip_ctx *ctx, int first, int last)
 #include "api_stat.inc"
 #include "api_multi.inc"
 #include "api_multi_tail.inc"
+#include "api_consstr_multi.inc"
 #include "api_racov.inc"
 #include "api_multiplex.inc"
 
@@ -793,6 +794,7 @@ int oatk_hip_buffer(oatk_hip_ctx *ctx, int which, const void **d_ptr, uint64_t *
                 default:
                     if (which >= OATK_BUF_CONS_SEL && which <= OATK_BUF_CONS_TOT) return cons_buffer(ctx, which, d_ptr, bytes);
                     if (which >= OATK_BUF_CONS_STR && which <= OATK_BUF_CONS_STR_STATUS) return consstr_buffer(ctx, which, d_ptr, bytes);
+                    if (which == OATK_BUF_CONS_KMER) return conskmer_buffer(ctx, d_ptr, bytes);
                     if (which >= OATK_BUF_AG_SCM_DEL && which <= OATK_BUF_AG_ARC_LINK) return ag_buffer(ctx, which, d_ptr, bytes);
                     if (which >= OATK_BUF_OVL_KEY && which <= OATK_BUF_OVL_TAIL) return ovl_buffer(ctx, which, d_ptr, bytes);
                     if (which >= OATK_BUF_RA_ALN_SID && which <= OATK_BUF_RA_SKIPPED) return ra_buffer(ctx, which, d_ptr, bytes);

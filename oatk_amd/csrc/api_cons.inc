@@ -7,6 +7,13 @@ struct ConsState {
     uint64_t n_sel = 0, n_scm = 0;
     int K = 0;
     bool done = false;
+    // sharded reads: every selected syncmer's own k-mer (api_consstr.inc: oatk_hip_consensus_strings_sharded makes it once per consensus)
+    DevBuf kmer;
+    uint64_t kmer_stride = 0;
+    bool kmer_valid = false;
+    hipEvent_t kmer_ev[2] = {nullptr, nullptr};
+    float kmer_ms = 0.f;
+    ~ConsState() { for (hipEvent_t e : kmer_ev) if (e) (void) hipEventDestroy(e); }
 };
 
 static void cons_state_free(oatk_hip_ctx *ctx)
@@ -76,7 +83,7 @@ extern "C" int oatk_hip_consensus_ids(oatk_hip_ctx *ctx, const uint32_t *d_ids, 
     CK(hipSetDevice(ctx->device));
     if (!ctx->cons) ctx->cons = new ConsState();
     ConsState *c = ctx->cons;
-    c->done = false;
+    c->done = false, c->kmer_valid = false;
     c->n_scm = 0, c->K = ctx->K, c->n_sel = n;          // CONS_SLOT is not kept for a caller-chosen list
     CENSURE(sel, (n + 1) * 4);
     if (n) CK(hipMemcpyAsync(c->sel.p, d_ids, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
@@ -112,7 +119,7 @@ extern "C" int oatk_hip_consensus(oatk_hip_ctx *ctx, uint32_t min_cov)
     CK(hipSetDevice(ctx->device));
     if (!ctx->cons) ctx->cons = new ConsState();
     ConsState *c = ctx->cons;
-    c->done = false;
+    c->done = false, c->kmer_valid = false;
     const bool after_ec = ctx->ec && ctx->ec->done;
     EcState *e = ctx->ec;
     const uint64_t ns = ctx->n_scm_total;

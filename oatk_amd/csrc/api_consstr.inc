@@ -49,18 +49,23 @@ static const char *consstr_plan_error(const oatk_cons_plan_t *p, uint64_t n_scm,
     return nullptr;
 }
 
-extern "C" int oatk_hip_consensus_strings(oatk_hip_ctx *ctx, const oatk_cons_plan_t *plan, int hoco_seq, uint64_t *total_bytes, uint64_t *n_refused)
+// the consensus tables and this handle's reads as a piece is opened from them (cons_str_core.hpp); T.kmer stays unset
+static oatk_cstr::Tables consstr_tables(oatk_hip_ctx *ctx, ConsState *c)
+{
+    const bool after_ec = ctx->ec && ctx->ec->done;      // the chains cons_run handed to cons_rl_kernel: CONS_FIRST indexes them
+    EcState *e = ctx->ec;
+    oatk_cstr::Tables T;
+    T.n_scm = c->n_scm, T.k = c->K, T.slot = c->slot.as<uint32_t>(), T.rl = c->rl.as<uint32_t>(), T.m_seq = c->m_seq.as<uint32_t>();
+    T.first = c->first.as<uint64_t>(), T.sid0 = ctx->sid0, T.off = ctx->d_off, T.hoco_s = ctx->hoco_s.as<uint8_t>();
+    T.chain_off = after_ec? e->new_off.as<uint64_t>() : ctx->scm_off.as<uint64_t>();
+    T.m_pos = after_ec? e->new_m.as<uint32_t>() : ctx->pos_mpos.as<uint32_t>();
+    return T;
+}
+
+// the string phases of a checked plan over the tables T: what oatk_hip_consensus_strings and oatk_hip_consensus_strings_sharded (api_consstr_multi.inc) both run
+static int consstr_run(oatk_hip_ctx *ctx, const oatk_cons_plan_t *plan, int hoco_seq, const oatk_cstr::Tables &T, uint64_t *total_bytes, uint64_t *n_refused)
 {
     using namespace oatk;
-    if (!ctx) return OATK_E_NODEV;
-    if (!plan) { ctx->err = "oatk_hip_consensus_strings: no plan"; return OATK_E_ARG; }
-    if (ctx->ec && ctx->ec->global) { ctx->err = "oatk_hip_consensus_strings: reads are sharded; the strings are made from one handle's tables"; return OATK_E_STATE; }
-    ConsState *c = ctx->cons;
-    if (!ctx->counted || !c || !c->done || (c->n_scm == 0 && c->n_sel != 0)) {      // (oatk_hip_consensus_ids keeps no CONS_SLOT)
-        ctx->err = "oatk_hip_consensus_strings needs oatk_hip_consensus done on the resident batch";
-        return OATK_E_STATE;
-    }
-    if (const char *why = consstr_plan_error(plan, c->n_scm, c->K)) { ctx->err = why; return OATK_E_ARG; }
     CK(hipSetDevice(ctx->device));
     if (!ctx->cstr) ctx->cstr = new ConsStrState();
     ConsStrState *g = ctx->cstr;
@@ -78,13 +83,8 @@ extern "C" int oatk_hip_consensus_strings(oatk_hip_ctx *ctx, const oatk_cons_pla
     }
     if (ns && plan->want_bytes) CK(hipMemcpyAsync(g->want.p, plan->want_bytes, ns, hipMemcpyHostToDevice, ctx->stream));
 
-    const bool after_ec = ctx->ec && ctx->ec->done;      // the chains cons_run handed to cons_rl_kernel: CONS_FIRST indexes them
-    EcState *e = ctx->ec;
     CstrArgs a;
-    a.T.n_scm = c->n_scm, a.T.k = c->K, a.T.slot = c->slot.as<uint32_t>(), a.T.rl = c->rl.as<uint32_t>(), a.T.m_seq = c->m_seq.as<uint32_t>();
-    a.T.first = c->first.as<uint64_t>(), a.T.sid0 = ctx->sid0, a.T.off = ctx->d_off, a.T.hoco_s = ctx->hoco_s.as<uint8_t>();
-    a.T.chain_off = after_ec? e->new_off.as<uint64_t>() : ctx->scm_off.as<uint64_t>();
-    a.T.m_pos = after_ec? e->new_m.as<uint32_t>() : ctx->pos_mpos.as<uint32_t>();
+    a.T = T;
     a.n_seq = ns, a.n_piece = np, a.seq_off = g->seq_off.as<uint64_t>(), a.piece_v = g->piece_v.as<uint64_t>(), a.piece_beg = g->piece_beg.as<int32_t>();
     a.want = plan->want_bytes? g->want.as<uint8_t>() : nullptr, a.hoco_seq = hoco_seq;
     a.piece_len = g->piece_len.as<uint64_t>(), a.piece_bad = g->piece_bad.as<uint8_t>(), a.piece_put = g->piece_put.as<uint64_t>(), a.piece_at = g->piece_at.as<uint64_t>();
@@ -115,6 +115,23 @@ extern "C" int oatk_hip_consensus_strings(oatk_hip_ctx *ctx, const oatk_cons_pla
     if (total_bytes) *total_bytes = total;
     if (n_refused) *n_refused = refused;
     return OATK_OK;
+}
+
+extern "C" int oatk_hip_consensus_strings(oatk_hip_ctx *ctx, const oatk_cons_plan_t *plan, int hoco_seq, uint64_t *total_bytes, uint64_t *n_refused)
+{
+    if (!ctx) return OATK_E_NODEV;
+    if (!plan) { ctx->err = "oatk_hip_consensus_strings: no plan"; return OATK_E_ARG; }
+    if (ctx->ec && ctx->ec->global) {
+        ctx->err = "oatk_hip_consensus_strings: reads are sharded; oatk_hip_consensus_strings_sharded makes the strings from all shards (include/oatk_hip_multi.h)";
+        return OATK_E_STATE;
+    }
+    ConsState *c = ctx->cons;
+    if (!ctx->counted || !c || !c->done || (c->n_scm == 0 && c->n_sel != 0)) {      // (oatk_hip_consensus_ids keeps no CONS_SLOT)
+        ctx->err = "oatk_hip_consensus_strings needs oatk_hip_consensus done on the resident batch";
+        return OATK_E_STATE;
+    }
+    if (const char *why = consstr_plan_error(plan, c->n_scm, c->K)) { ctx->err = why; return OATK_E_ARG; }
+    return consstr_run(ctx, plan, hoco_seq, consstr_tables(ctx, c), total_bytes, n_refused);
 }
 
 extern "C" int oatk_hip_consensus_strings_times(oatk_hip_ctx *ctx, float *ms2, uint64_t *n_piece)

@@ -285,7 +285,7 @@ static int consensus_sharded_impl(oatk_hip_ctx *ctx, oatk_comm *c, uint32_t min_
     if ((rc = mgt_dense(ctx, c, m)) != OATK_OK) return rc;
     if (!ctx->cons) ctx->cons = new ConsState();
     ConsState *cs = ctx->cons;
-    cs->done = false;
+    cs->done = false, cs->kmer_valid = false;
     const uint64_t ng = m->n_global;
     uint64_t n_sel = 0;
     cs->n_scm = ng, cs->K = ctx->K, cs->n_sel = 0;

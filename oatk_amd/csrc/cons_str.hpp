@@ -5,6 +5,7 @@
 //   cstr_len_kernel    one wave per piece: lanes stride over the positions and add up 1 + rl, a wave reduction gives the piece's length; unprepared pieces flagged
 //   cstr_seq_kernel    one wave per sequence: its length and status, and its pieces' lengths masked (0 where the sequence takes no bytes) for the scan
 //   (one exclusive scan over the pieces: where each starts in CONS_STR)
+//   cstr_kmer_kernel   sharded reads only, once per consensus: one wave per selected slot writes the syncmer's own k-mer where this rank holds it, zeros elsewhere
 //   cstr_fill_kernel   one wave per piece, 64 positions at a time: a lane loads its position's base and count, a wave prefix sum puts the 64 start offsets in LDS,
 //                      and the stores are output-stationary -- lane l writes bytes l, l + 64, ... of the tile's text and finds each one's source position in the
 //                      starts by bisection -- so a run of 700 bases goes out as eleven coalesced 64-byte stores, not as one lane's loop
@@ -83,6 +84,35 @@ __global__ void cstr_off_kernel(CstrArgs a)
 {
     const uint64_t s = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (s <= a.n_seq) a.str_off[s] = a.piece_at[s < a.n_seq? a.seq_off[s] : a.n_piece];
+}
+
+// Reads sharded over several handles: CONS_FIRST may name a read of another rank, whose bases this rank does not hold.  Every rank writes the k-mer table of ALL
+// selected slots -- the row of a slot whose first uncorrected occurrence lies in one of its own reads holds that occurrence's k-mer in the syncmer's forward
+// orientation (cons_str_core.hpp: kmer_word), every other row zeros -- so that the sum of the ranks' tables is the table and no rank has to know who owns what.
+// One wave per slot; lane l writes words l, l + 64, ... of the row (k above 1024: more than one): the stores of a wave are consecutive.  Every word of every row is
+// written at every run.
+struct CstrKmerArgs {
+    oatk_cstr::Tables T;          // the reads' side; T.kmer is not read
+    uint64_t n_sel, n_reads;
+    uint32_t row_words;           // 32-bit words per row: 2 * ceil(k / 32)
+    uint32_t *kmer;               // [n_sel * row_words]
+};
+
+__global__ __launch_bounds__(64 * CSTR_WAVES) void cstr_kmer_kernel(CstrKmerArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t slot = (uint64_t) blockIdx.x * CSTR_WAVES + (threadIdx.x >> 6);
+    if (slot >= a.n_sel) return;
+    uint32_t *row = a.kmer + slot * a.row_words;
+    const uint64_t o = a.T.first[slot];
+    const bool mine = o != ~0ULL && (o >> 32) >= a.T.sid0 && (o >> 32) - a.T.sid0 < a.n_reads;
+    if (!mine) {
+        for (uint32_t j = lane; j < a.row_words; j += 64) row[j] = 0;
+        return;
+    }
+    const uint8_t *hs;
+    const uint32_t mp = oatk_cstr::first_entry(a.T, o, hs);
+    for (uint32_t j = lane; j < a.row_words; j += 64) row[j] = oatk_cstr::kmer_word(hs, mp >> 1, mp & 1u, a.T.k, j);
 }
 
 __global__ __launch_bounds__(64 * CSTR_WAVES) void cstr_fill_kernel(CstrArgs a)

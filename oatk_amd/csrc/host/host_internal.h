@@ -6,6 +6,9 @@
 #ifndef OATK_HOST_INTERNAL_H
 #define OATK_HOST_INTERNAL_H
 
+#include <stdio.h>
+
+#include "oatk_hip_cons.h"
 #include "oatk_hip_racov.h"
 #include "oatk_inflate.h"
 #include "oatk_hip_stat.h"
@@ -48,6 +51,14 @@ uint64_t oatk_host_multiplex_pairs(const oatk_scg_t *g);
 int oatk_host_multiplex_decide(const oatk_scg_t *g, const uint64_t *pair_off, const uint64_t *pair_in, const uint64_t *pair_out, const double *score,
                                const uint8_t *have, uint32_t max_n_scm, double min_n_r, double min_d_f, uint8_t *multi_vtx, int *updated, oatk_triplet_table *tab);
 
+/* host/scgcons_host.c split at its one device call, for host/multi_host.c: the plan of scg_consensus over g (NULL with OATK_E_SPLIT / OATK_E_ARG where
+ * oatk_scg_consensus declines before the device), the plan as oatk_hip_consensus_strings(_sharded) takes it, and -- after that call, with what it returned -- the
+ * strings resident in ctx fetched and the graph and the GFA lines written as the reference writes them; unless it returns OATK_OK, g and fo are untouched */
+typedef struct oatk_scgcons_plan oatk_scgcons_plan_t;
+oatk_scgcons_plan_t *oatk_host_scgcons_plan(const oatk_overlap_t *o, const oatk_sr_db_t *sr_db, const oatk_scg_t *g, int *rc);
+const oatk_cons_plan_t *oatk_host_scgcons_device_plan(const oatk_scgcons_plan_t *sp);
+int oatk_host_scgcons_write(oatk_hip_ctx *ctx, const oatk_scgcons_plan_t *sp, uint64_t total, uint64_t refused, oatk_scg_t *g, int save_seq, FILE *fo);
+void oatk_host_scgcons_plan_free(oatk_scgcons_plan_t *sp);
 
 typedef struct { uint8_t *p, *end; } oatk_name_bump_t;
 char *oatk_host_name_dup(const uint8_t *src, size_t len, oatk_name_bump_t *b, const void *owner);

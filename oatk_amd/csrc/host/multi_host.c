@@ -432,6 +432,32 @@ oatk_consensus_t *oatk_multi_consensus_fetch(oatk_multi *m, uint32_t min_cov, in
     return *rc? 0 : oatk_host_consensus_from_resident(m->ctx[0], k, rc);
 }
 
+int oatk_multi_consensus(oatk_multi *m, uint32_t min_cov) { return m? run_ranks(m, cons_rank, &min_cov) : OATK_E_NODEV; }
+
+/* scg_consensus: the plan is made once and fanned out; after the first call on a consensus the handles exchange nothing, and handle 0's text is everybody's */
+typedef struct { const oatk_cons_plan_t *plan; int hoco_seq; uint64_t total[64], refused[64]; } cstr_arg_t;
+static int cstr_rank(oatk_multi *m, int rank, void *arg)
+{
+    cstr_arg_t *a = (cstr_arg_t *) arg;
+    return oatk_hip_consensus_strings_sharded(m->ctx[rank], m->comm[rank], a->plan, a->hoco_seq, &a->total[rank], &a->refused[rank]);
+}
+
+int oatk_multi_scg_consensus(oatk_multi *m, const oatk_overlap_t *o, const oatk_sr_db_t *sr_db, oatk_scg_t *g, int hoco_seq, int save_seq, FILE *fo)
+{
+    if (!m || !o || !sr_db || !g || !g->utg_asmg || !g->scm_db) return OATK_E_ARG;
+    int rc = OATK_OK;
+    oatk_scgcons_plan_t *sp = oatk_host_scgcons_plan(o, sr_db, g, &rc);
+    if (!sp) return rc;
+    cstr_arg_t *a = (cstr_arg_t *) calloc(1, sizeof(cstr_arg_t));
+    if (!a) { oatk_host_scgcons_plan_free(sp); return OATK_E_NOMEM; }
+    a->plan = oatk_host_scgcons_device_plan(sp), a->hoco_seq = hoco_seq;
+    rc = run_ranks(m, cstr_rank, a);
+    if (!rc) { rc = oatk_host_scgcons_write(m->ctx[0], sp, a->total[0], a->refused[0], g, save_seq, fo); note_err(m, 0, rc); }
+    free(a);
+    oatk_host_scgcons_plan_free(sp);
+    return rc;
+}
+
 typedef struct { uint32_t c; uint64_t np[64], ne[64]; } ovl_arg_t;
 static int ovl_rank(oatk_multi *m, int rank, void *arg)
 {

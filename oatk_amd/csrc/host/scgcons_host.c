@@ -159,29 +159,41 @@ static void *fetch(oatk_hip_ctx *ctx, int which, uint64_t want_bytes, int *rc)
 
 #define NO_SEQ UINT64_MAX
 
-int oatk_scg_consensus(oatk_hip_ctx *ctx, const oatk_overlap_t *o, const oatk_sr_db_t *sr_db, oatk_scg_t *g, int hoco_seq, int save_seq, FILE *fo)
+/* ---- the two halves around the one device call (host_internal.h): oatk_scg_consensus below and oatk_multi_scg_consensus (multi_host.c) run both ---- */
+struct oatk_scgcons_plan {
+    plan_t p;
+    oatk_cons_plan_t dev;                                                  /* p as the device call takes it */
+    uint64_t *arc_seq, *vtx_seq;                                           /* the sequence that gives an arc its length (NO_SEQ: 0) / a unitig its text */
+};
+
+void oatk_host_scgcons_plan_free(oatk_scgcons_plan_t *sp)
 {
-    if (!ctx || !o || !sr_db || !g || !g->utg_asmg || !g->scm_db) return OATK_E_ARG;
-    oatk_asmg_t *u = g->utg_asmg;
+    if (!sp) return;
+    plan_free(&sp->p);
+    free(sp->arc_seq); free(sp->vtx_seq); free(sp);
+}
+
+const oatk_cons_plan_t *oatk_host_scgcons_device_plan(const oatk_scgcons_plan_t *sp) { return &sp->dev; }
+
+/* the plan: unitigs (:739-743), then arcs (:779-807); NULL and a code when the graph cannot be served */
+oatk_scgcons_plan_t *oatk_host_scgcons_plan(const oatk_overlap_t *o, const oatk_sr_db_t *sr_db, const oatk_scg_t *g, int *rc_out)
+{
+    const oatk_asmg_t *u = g->utg_asmg;
     const int k = sr_db->k;
     const uint64_t nv = u->n_vtx, na = u->n_arc;
     uint64_t i;
     int rc = OATK_OK;
-    plan_t p;
-    memset(&p, 0, sizeof(p));
-    uint64_t *arc_seq = (uint64_t *) xmalloc(na * 8);                      /* the sequence that gives an arc its length, NO_SEQ: 0 */
-    uint64_t *vtx_seq = (uint64_t *) xmalloc(nv * 8);
-    char *text = 0;
-    uint64_t *off = 0, *len = 0;
-    uint8_t *status = 0;
-
-    /* ---- the plan: unitigs (:739-743), then arcs (:779-807) ---- */
+    oatk_scgcons_plan_t *sp = (oatk_scgcons_plan_t *) xmalloc(sizeof(*sp));
+    memset(sp, 0, sizeof(*sp));
+    plan_t *p = &sp->p;
+    uint64_t *arc_seq = sp->arc_seq = (uint64_t *) xmalloc(na * 8);
+    uint64_t *vtx_seq = sp->vtx_seq = (uint64_t *) xmalloc(nv * 8);
     for (i = 0; i < nv && !rc; ++i) {
         const oatk_asmg_vtx_t *s = &u->vtx[i];
         vtx_seq[i] = NO_SEQ;
         if (s->del) continue;
-        if (!plan_unitig(&p, o, s->a, s->n, k)) rc = OATK_E_SPLIT;
-        else vtx_seq[i] = plan_seq(&p, 1);
+        if (!plan_unitig(p, o, s->a, s->n, k)) rc = OATK_E_SPLIT;
+        else vtx_seq[i] = plan_seq(p, 1);
     }
     for (i = 0; i < na && !rc; ++i) {
         const oatk_asmg_arc_t *a = &u->arc[i];
@@ -191,8 +203,8 @@ int oatk_scg_consensus(oatk_hip_ctx *ctx, const oatk_overlap_t *o, const oatk_sr
         if (a->ln > 0) {                                                   /* the overlapping syncmers' own consensus length */
             const oatk_asmg_vtx_t *s = &u->vtx[a->v >> 1];
             if (a->ln > s->n) { rc = OATK_E_ARG; break; }
-            if (!plan_unitig(&p, o, (a->v & 1)? s->a : s->a + (s->n - a->ln), a->ln, k)) rc = OATK_E_SPLIT;
-            else arc_seq[i] = plan_seq(&p, 0);
+            if (!plan_unitig(p, o, (a->v & 1)? s->a : s->a + (s->n - a->ln), a->ln, k)) rc = OATK_E_SPLIT;
+            else arc_seq[i] = plan_seq(p, 0);
         } else {                                                           /* the overlap of the two end syncmers */
             const oatk_asmg_vtx_t *s = &u->vtx[a->v >> 1], *t = &u->vtx[a->w >> 1];
             if (s->n == 0 || t->n == 0) { rc = OATK_E_ARG; break; }
@@ -201,22 +213,33 @@ int oatk_scg_consensus(oatk_hip_ctx *ctx, const oatk_overlap_t *o, const oatk_sr
             z = a->w & 1;
             const uint64_t w = t->a[(t->n - 1) * z] ^ z;
             const int l = oatk_calc_syncmer_overlap(o, v, w, NULL);
-            if (l < k) plan_piece(&p, v, l), arc_seq[i] = plan_seq(&p, 0);
+            if (l < k) plan_piece(p, v, l), arc_seq[i] = plan_seq(p, 0);
         }
     }
+    *rc_out = rc;
+    if (rc) { oatk_host_scgcons_plan_free(sp); return NULL; }
+    const oatk_cons_plan_t dev = {p->n_seq, p->n_piece, p->seq_off, p->piece_v, p->piece_beg, p->want};
+    sp->dev = dev;
+    return sp;
+}
 
-    /* ---- one device call; the text and three small arrays back ---- */
-    uint64_t total = 0, refused = 0;
-    if (!rc) {
-        oatk_cons_plan_t plan = {p.n_seq, p.n_piece, p.seq_off, p.piece_v, p.piece_beg, p.want};
-        rc = oatk_hip_consensus_strings(ctx, &plan, hoco_seq, &total, &refused);
-    }
-    if (!rc && refused) rc = OATK_E_SPLIT;
+/* after the device call on sp's plan (total, refused: what it returned): the text and three small arrays back from ctx, then vtx.len, vtx.cov, vtx.seq, arc.ls and the
+ * GFA lines.  The graph and fo are written only when every sequence was served. */
+int oatk_host_scgcons_write(oatk_hip_ctx *ctx, const oatk_scgcons_plan_t *sp, uint64_t total, uint64_t refused, oatk_scg_t *g, int save_seq, FILE *fo)
+{
+    oatk_asmg_t *u = g->utg_asmg;
+    const uint64_t nv = u->n_vtx, na = u->n_arc, n_seq = sp->p.n_seq;
+    const uint64_t *arc_seq = sp->arc_seq, *vtx_seq = sp->vtx_seq;
+    uint64_t i;
+    int rc = refused? OATK_E_SPLIT : OATK_OK;
+    char *text = 0;
+    uint64_t *off = 0, *len = 0;
+    uint8_t *status = 0;
     if (!rc) text = (char *) fetch(ctx, OATK_BUF_CONS_STR, total, &rc);
-    if (!rc) off = (uint64_t *) fetch(ctx, OATK_BUF_CONS_STR_OFF, (p.n_seq + 1) * 8, &rc);
-    if (!rc) len = (uint64_t *) fetch(ctx, OATK_BUF_CONS_STR_LEN, p.n_seq * 8, &rc);
-    if (!rc) status = (uint8_t *) fetch(ctx, OATK_BUF_CONS_STR_STATUS, p.n_seq, &rc);
-    for (i = 0; i < p.n_seq && !rc; ++i) if (status[i] || len[i] == UINT64_MAX) rc = OATK_E_SPLIT;
+    if (!rc) off = (uint64_t *) fetch(ctx, OATK_BUF_CONS_STR_OFF, (n_seq + 1) * 8, &rc);
+    if (!rc) len = (uint64_t *) fetch(ctx, OATK_BUF_CONS_STR_LEN, n_seq * 8, &rc);
+    if (!rc) status = (uint8_t *) fetch(ctx, OATK_BUF_CONS_STR_STATUS, n_seq, &rc);
+    for (i = 0; i < n_seq && !rc; ++i) if (status[i] || len[i] == UINT64_MAX) rc = OATK_E_SPLIT;
     for (i = 0; i < nv && !rc; ++i)
         if (vtx_seq[i] != NO_SEQ && off[vtx_seq[i] + 1] - off[vtx_seq[i]] != len[vtx_seq[i]]) rc = OATK_E_STATE;
 
@@ -254,7 +277,19 @@ int oatk_scg_consensus(oatk_hip_ctx *ctx, const oatk_overlap_t *o, const oatk_sr
             }
         }
     }
-    free(text); free(off); free(len); free(status); free(arc_seq); free(vtx_seq);
-    plan_free(&p);
+    free(text); free(off); free(len); free(status);
+    return rc;
+}
+
+int oatk_scg_consensus(oatk_hip_ctx *ctx, const oatk_overlap_t *o, const oatk_sr_db_t *sr_db, oatk_scg_t *g, int hoco_seq, int save_seq, FILE *fo)
+{
+    if (!ctx || !o || !sr_db || !g || !g->utg_asmg || !g->scm_db) return OATK_E_ARG;
+    int rc = OATK_OK;
+    oatk_scgcons_plan_t *sp = oatk_host_scgcons_plan(o, sr_db, g, &rc);
+    if (!sp) return rc;
+    uint64_t total = 0, refused = 0;
+    rc = oatk_hip_consensus_strings(ctx, &sp->dev, hoco_seq, &total, &refused);      /* one device call */
+    if (!rc) rc = oatk_host_scgcons_write(ctx, sp, total, refused, g, save_seq, fo);
+    oatk_host_scgcons_plan_free(sp);
     return rc;
 }

@@ -22,7 +22,7 @@ _DTYPES = {
     "EC_CSEQ_LEN": np.uint32, "EC_CSEQ_OFF": np.uint64, "EC_CSEQ": np.uint8, "EC_BLOCK_QEND": np.uint32,
     "INGEST_SEQ": np.uint8, "INGEST_OFF": np.uint64, "INGEST_LEN": np.uint32, "INGEST_HDR": np.uint64,
     "CONS_SEL": np.uint32, "CONS_SLOT": np.uint32, "CONS_RL": np.uint32, "CONS_MSEQ": np.uint32, "CONS_FIRST": np.uint64, "CONS_TOT": np.uint64,
-    "CONS_STR": np.uint8, "CONS_STR_OFF": np.uint64, "CONS_STR_LEN": np.uint64, "CONS_STR_STATUS": np.uint8,
+    "CONS_STR": np.uint8, "CONS_STR_OFF": np.uint64, "CONS_STR_LEN": np.uint64, "CONS_STR_STATUS": np.uint8, "CONS_KMER": np.uint8,
     "EG_IDX_P": np.uint64, "EG_IDX_N": np.uint32, "EG_ARC_V": np.uint64, "EG_ARC_W": np.uint64, "EG_ARC_LS": np.uint32,
     "EG_ARC_COV": np.uint32, "EG_ARC_COMP": np.uint8, "EG_OTHER": np.uint8,
     "RA_ALN_SID": np.uint32, "RA_ALN_OFF": np.uint64, "RA_ALN_S": np.float64, "RA_FRG_UID": np.uint64, "RA_FRG_UBEG": np.uint32,
@@ -494,26 +494,50 @@ class HipSyncasm:
         fetch CONS_SEL / CONS_SLOT / CONS_RL / CONS_MSEQ / CONS_FIRST"""
         self._check(self.L.oatk_hip_consensus(self.h, min_cov), "oatk_hip_consensus")
 
-    def consensus_strings(self, seq_off, piece_v, piece_beg, hoco, want_bytes=None):
-        """the text of scg_consensus' sequences from the tables consensus() left resident (oatk_hip_consensus_strings): sequence i is made of the pieces
-        seq_off[i] .. seq_off[i + 1], a piece is (syncmer id << 1 | rev, beg < k).  Returns (bytes, off, length, status): the text of all sequences back to
-        back, where each starts, what scg_unitig_consensus returns for it (also where want_bytes is 0; ~0 when refused) and 1 for a refused one.
-        self.cons_strings = (total bytes, refused sequences) of the call."""
+    def _cons_plan(self, who, seq_off, piece_v, piece_beg, want_bytes):
+        """oatk_cons_plan_t over host arrays; the arrays are returned with it and must outlive the call"""
         seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
         piece_v = np.ascontiguousarray(piece_v, dtype=np.uint64)
         piece_beg = np.ascontiguousarray(piece_beg, dtype=np.int32)
         want = None if want_bytes is None else np.ascontiguousarray(want_bytes, dtype=np.uint8)
         n_seq = max(len(seq_off) - 1, 0)
         if want is not None and len(want) != n_seq:
-            raise ValueError("consensus_strings: one want_bytes entry per sequence")
+            raise ValueError(who + ": one want_bytes entry per sequence")
         if len(piece_v) != len(piece_beg):
-            raise ValueError("consensus_strings: one beg per piece")
+            raise ValueError(who + ": one beg per piece")
         plan = _lib.ConsPlan(n_seq, len(piece_v), seq_off.ctypes.data if len(seq_off) else None, piece_v.ctypes.data if len(piece_v) else None,
                              piece_beg.ctypes.data if len(piece_beg) else None, want.ctypes.data if want is not None and n_seq else None)
+        return plan, (seq_off, piece_v, piece_beg, want)
+
+    def consensus_strings(self, seq_off, piece_v, piece_beg, hoco, want_bytes=None):
+        """the text of scg_consensus' sequences from the tables consensus() left resident (oatk_hip_consensus_strings): sequence i is made of the pieces
+        seq_off[i] .. seq_off[i + 1], a piece is (syncmer id << 1 | rev, beg < k).  Returns (bytes, off, length, status): the text of all sequences back to
+        back, where each starts, what scg_unitig_consensus returns for it (also where want_bytes is 0; ~0 when refused) and 1 for a refused one.
+        self.cons_strings = (total bytes, refused sequences) of the call."""
+        plan, keep = self._cons_plan("consensus_strings", seq_off, piece_v, piece_beg, want_bytes)
         total, refused = C.c_uint64(), C.c_uint64()
         self._check(self.L.oatk_hip_consensus_strings(self.h, C.byref(plan), 1 if hoco else 0, C.byref(total), C.byref(refused)), "oatk_hip_consensus_strings")
+        del keep
         self.cons_strings = (int(total.value), int(refused.value))
         return self.fetch("CONS_STR"), self.fetch("CONS_STR_OFF"), self.fetch("CONS_STR_LEN"), self.fetch("CONS_STR_STATUS")
+
+    def consensus_strings_sharded(self, comm, seq_off, piece_v, piece_beg, hoco, want_bytes=None):
+        """consensus_strings for reads sharded over several handles, after consensus_sharded(comm, ...) (oatk_hip_consensus_strings_sharded): every rank makes
+        the call with the same plan and gets the same four arrays, those of one handle holding all the reads.  The first call after a consensus exchanges the
+        syncmers' own k-mers (one all-reduce; fetch CONS_KMER), later calls exchange nothing."""
+        plan, keep = self._cons_plan("consensus_strings_sharded", seq_off, piece_v, piece_beg, want_bytes)
+        total, refused = C.c_uint64(), C.c_uint64()
+        self._check(self.L.oatk_hip_consensus_strings_sharded(self.h, comm, C.byref(plan), 1 if hoco else 0, C.byref(total), C.byref(refused)),
+                    "oatk_hip_consensus_strings_sharded")
+        del keep
+        self.cons_strings = (int(total.value), int(refused.value))
+        return self.fetch("CONS_STR"), self.fetch("CONS_STR_OFF"), self.fetch("CONS_STR_LEN"), self.fetch("CONS_STR_STATUS")
+
+    def consensus_kmer_time(self):
+        """(k-mer kernel ms, table bytes) of the k-mer table consensus_strings_sharded made last; the time is measured when set_timing() is on"""
+        ms, b = C.c_float(), C.c_uint64()
+        self._check(self.L.oatk_hip_consensus_kmer_time(self.h, C.byref(ms), C.byref(b)), "oatk_hip_consensus_kmer_time")
+        return float(ms.value), int(b.value)
 
     def consensus_strings_times(self):
         """(length kernel ms, fill kernel ms, pieces) of the last consensus_strings; the times are measured when set_timing() is on"""
