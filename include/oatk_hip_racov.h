@@ -112,6 +112,30 @@ int oatk_hip_ra_triplet_scores(oatk_hip_ctx *ctx, const oatk_racov_graph_t *g, c
 int oatk_hip_ra_triplet_scores_sharded(oatk_hip_ctx *ctx, oatk_comm *comm, const oatk_racov_graph_t *g, const oatk_racov_aln_t *aln, uint64_t *pair_off,
                                        uint64_t n_pair_cap, uint64_t *n_pair, uint64_t *pair_in, uint64_t *pair_out, double *score, uint8_t *have);
 
+/* ---- the repeat units of the mini-circle path finder (extract_minicircles_with_anchor, path_finder.c:539-693), one handle ----
+ * For every alignment record -- the resident ones (aln == NULL) or uploaded ones, of which only off and uid are read -- the unit the reference's
+ * minicircle_analysis_thread finds round the unitig anchor_utg: beg << 33 | end << 1 | rev, or UINT64_MAX when the record has fewer than two
+ * fragments on the anchor, two of different orientation, or does not repeat the unit over its whole length (:545-607).  Then the valid records'
+ * paths as the reference collects them (:657-671: (uint32_t) uid[beg .. end]; a reverse unit with elements 1 .. nv - 1 reversed and every
+ * element ^ 1, so that every path starts with anchor_utg << 1), reduced to the distinct ones in path_cmpfunc order (:620-638, :677-693).
+ * Resident afterwards (ids for oatk_hip_buffer), until the next call that succeeds:
+ *   MC_UNIT      u64[n_aln]           the unit of every record
+ *   MC_PATH_OFF  u64[n_path + 1]      path p is MC_PATH_V[MC_PATH_OFF[p] .. MC_PATH_OFF[p + 1])
+ *   MC_PATH_V    u32[n_path_vtx]
+ *   MC_PATH_CNT  u64[n_path]          the number of records that gave path p (their sum is *n_valid)
+ * n_aln == 0: OATK_OK, all zero.  OATK_E_STATE: aln == NULL and no resident alignment.  OATK_E_ARG: anchor_utg >= 2^31; uploaded offsets that do
+ * not ascend from 0 to n_frg; a uid of 2^32 or more inside a unit (the reference truncates it silently); a record of 2^31 fragments or more.
+ * Whatever is refused leaves the resident results of the previous call as they were, and the three counts unwritten. */
+int oatk_hip_ra_minicircle_units(oatk_hip_ctx *ctx, const oatk_racov_aln_t *aln, uint64_t anchor_utg, uint64_t *n_valid, uint64_t *n_path,
+                                 uint64_t *n_path_vtx);
+enum { OATK_BUF_MC_UNIT = 250, OATK_BUF_MC_PATH_OFF, OATK_BUF_MC_PATH_V, OATK_BUF_MC_PATH_CNT };
+/* device time of the last call's three phases (units; valid records and their paths; distinct paths), ms, between events on the handle's stream,
+ * and the number of compare rounds the distinct paths took (1 unless two different paths shared a hash) */
+int oatk_hip_ra_minicircle_times(oatk_hip_ctx *ctx, float *ms3, uint64_t *rounds);
+/* Test hook: the distinct paths are grouped by the low `bits` of their 64-bit hash only, so that different paths meet in a group; 0 = default (all
+ * 64).  Results never depend on it: every member of a group is compared with its head element by element. */
+int oatk_hip_debug_mc_hash_bits(oatk_hip_ctx *ctx, unsigned bits);
+
 /* Test hook: the most LCS-matrix cells (4 bytes each) the unitig coverage may hold at once, over all reads; 0 = default (2^31, 8 GiB). */
 int oatk_hip_debug_racov_cap(oatk_hip_ctx *ctx, uint64_t cells);
 

@@ -267,6 +267,20 @@ int oatk_scg_multiplex_plan(oatk_hip_ctx *ctx, const oatk_scg_ra_v *ra_v, const 
                             double min_d_f, uint8_t *multi_vtx, int *updated, oatk_triplet_table *tab);
 void oatk_triplet_table_free(oatk_triplet_table *tab);
 
+/* extract_minicircles_with_anchor (path_finder.c:640-730) of the mini-circle path finder, oatk -M: the one pass over every alignment record, the
+ * collection, sort and deduplication of the repeat units run on the device (include/oatk_hip_racov.h: oatk_hip_ra_minicircle_units; with
+ * OATK_RACOV_RESIDENT_ALN from what oatk_scg_read_alignment left in ctx, nothing is uploaded); only the distinct paths come back.  out->a[i] is the
+ * reference's paths->a[i] -- nv, v[] (malloc'ed), len, wlen -- in path_cmpfunc order, cnt the number of records that walked that unit; out->n is the
+ * reference's return value.  Free it with oatk_mc_paths_free.  scg is not changed.  OATK_E_ARG: anchor_sid is no unitig, a unit holds a uid of 2^32 or
+ * more, or two consecutive vertices of a path (the last and the first included) have no live arc, which the reference asserts; out is then untouched.
+ * oatk_mc_path_stats is the second half alone (:696-727): len and wlen of paths whose nv and v are set, from the unitig graph; no device is involved,
+ * and nothing is written unless it returns OATK_OK. */
+typedef struct { uint32_t nv; uint32_t *v; uint32_t len; double wlen; uint64_t cnt; } oatk_mc_path;
+typedef struct { uint64_t n, m; oatk_mc_path *a; } oatk_mc_paths;
+int oatk_extract_minicircles(oatk_hip_ctx *ctx, const oatk_scg_ra_v *ra_v, const oatk_scg_t *scg, uint64_t anchor_sid, unsigned flags, oatk_mc_paths *out);
+int oatk_mc_path_stats(const oatk_asmg_t *g, oatk_mc_paths *paths);
+void oatk_mc_paths_free(oatk_mc_paths *paths);
+
 /* same destructors as the reference (syncmer.c:1047-1110) for objects that are not handed to it */
 void oatk_sr_db_clean(oatk_sr_db_t *sr_db);
 

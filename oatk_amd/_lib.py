@@ -39,6 +39,8 @@ BUF.update({name: 180 + i for i, name in enumerate([
 BUF.update({name: 220 + i for i, name in enumerate(["MG_H", "MG_S", "MG_COV", "MG_L2G", "MG_EC_COV", "MG_EC_DEL", "MG_LCOV"])})
 BUF.update({name: 230 + i for i, name in enumerate(["MG_G_H", "MG_G_S", "MG_G_COV", "MG_G_DEL", "MG_G_OCC_OFF", "MG_G_OCC", "MG_POS_GKID"])})
 BUF["CONS_KMER"] = 240
+# include/oatk_hip_racov.h
+BUF.update({name: 250 + i for i, name in enumerate(["MC_UNIT", "MC_PATH_OFF", "MC_PATH_V", "MC_PATH_CNT"])})
 TIMERS = ["hpc", "syncmer", "syncmer_n", "scan_post", "count_place", "count_sort", "count_group", "kmer_hash", "ec_graph", "ec_mark", "ec_solve", "ec_refresh"]
 
 EXPORTS = [
@@ -56,6 +58,7 @@ EXPORTS = [
     "oatk_hip_asm_graph", "oatk_hip_asm_pairs", "oatk_hip_asm_graph_from_pairs", "oatk_hip_overlap_hist", "oatk_hip_overlap_pairs", "oatk_hip_overlap_hist_from_pairs", "oatk_hip_read_alignment", "oatk_hip_debug_align_two_pass",
     "oatk_hip_ra_utg_coverage", "oatk_hip_ra_arc_coverage", "oatk_hip_debug_racov_cap", "oatk_hip_ra_utg_coverage_sharded", "oatk_hip_ra_arc_coverage_sharded",
     "oatk_hip_ra_triplet_scores", "oatk_hip_ra_triplet_scores_sharded",
+    "oatk_hip_ra_minicircle_units", "oatk_hip_ra_minicircle_times", "oatk_hip_debug_mc_hash_bits",
     "oatk_hip_ec_keep_seq", "oatk_hip_ec_corrected_reads", "oatk_hip_consensus_strings", "oatk_hip_consensus_strings_times",
     "oatk_hip_consensus_strings_sharded", "oatk_hip_consensus_kmer_time",
     "oatk_hip_inflate_bgzf", "oatk_hip_inflate_bgzf_host", "oatk_hip_inflate_last_byte", "oatk_hip_ingest_names",
@@ -64,7 +67,8 @@ EXPORTS = [
 
 # the N-handle mirror in liboatk_host.so (include/oatk_multi.h) of entry points listed above; EXPORTS itself is checked against liboatk_hip.so
 HOST_EXPORTS = ["oatk_multi_scg_ra_utg_coverage", "oatk_multi_scg_ra_arc_coverage", "oatk_scg_multiplex_plan", "oatk_multi_scg_multiplex_plan",
-                "oatk_triplet_table_free", "oatk_multi_read_error_correction_fo", "oatk_multi_consensus", "oatk_multi_scg_consensus", "oatk_bgzf_index", "oatk_host_set_device_inflate", "oatk_host_inflate_counts"]
+                "oatk_triplet_table_free", "oatk_multi_read_error_correction_fo", "oatk_multi_consensus", "oatk_multi_scg_consensus", "oatk_bgzf_index", "oatk_host_set_device_inflate", "oatk_host_inflate_counts",
+                "oatk_extract_minicircles", "oatk_mc_path_stats", "oatk_mc_paths_free"]
 
 
 def load_host():
@@ -100,6 +104,10 @@ def load_host():
     H.oatk_multi_scg_multiplex_plan.argtypes = [vp, vp, vp, C.c_uint32, C.c_double, C.c_double, vp, C.POINTER(C.c_int), C.POINTER(TripletTable)]
     H.oatk_triplet_table_free.restype = None
     H.oatk_triplet_table_free.argtypes = [C.POINTER(TripletTable)]
+    H.oatk_extract_minicircles.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint, C.POINTER(McPaths)]
+    H.oatk_mc_path_stats.argtypes = [vp, C.POINTER(McPaths)]
+    H.oatk_mc_paths_free.restype = None
+    H.oatk_mc_paths_free.argtypes = [C.POINTER(McPaths)]
     H.oatk_host_debug_window.argtypes = [C.c_uint64]
     H.oatk_bgzf_index.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]      # include/oatk_inflate.h
     return H
@@ -113,6 +121,16 @@ INF_OK, INF_STREAM, INF_LENGTH, INF_CRC = range(4)
 class TripletTable(C.Structure):
     """oatk_triplet_table (include/oatk_syncasm.h): the entries of scg_multiplex's tri_s that its lookups find"""
     _fields_ = [("n", C.c_uint64), ("m", C.c_uint64), ("l_in", C.POINTER(C.c_uint64)), ("l_out", C.POINTER(C.c_uint64)), ("val", C.POINTER(C.c_double))]
+
+
+class McPath(C.Structure):
+    """oatk_mc_path (include/oatk_syncasm.h): one distinct repeat unit round the anchor, the reference's path_t fields that extract_minicircles_with_anchor sets"""
+    _fields_ = [("nv", C.c_uint32), ("v", C.POINTER(C.c_uint32)), ("len", C.c_uint32), ("wlen", C.c_double), ("cnt", C.c_uint64)]
+
+
+class McPaths(C.Structure):
+    """oatk_mc_paths"""
+    _fields_ = [("n", C.c_uint64), ("m", C.c_uint64), ("a", C.POINTER(McPath))]
 
 
 class EcGraph(C.Structure):
@@ -290,6 +308,9 @@ def load():
     u64p = C.POINTER(C.c_uint64)
     L.oatk_hip_ra_triplet_scores.argtypes = [vp, C.POINTER(RacovGraph), C.POINTER(RacovAln), vp, C.c_uint64, u64p, vp, vp, vp, vp]
     L.oatk_hip_ra_triplet_scores_sharded.argtypes = [vp, vp, C.POINTER(RacovGraph), C.POINTER(RacovAln), vp, C.c_uint64, u64p, vp, vp, vp, vp]
+    L.oatk_hip_ra_minicircle_units.argtypes = [vp, C.POINTER(RacovAln), C.c_uint64, u64p, u64p, u64p]
+    L.oatk_hip_ra_minicircle_times.argtypes = [vp, C.POINTER(C.c_float), u64p]
+    L.oatk_hip_debug_mc_hash_bits.argtypes = [vp, C.c_uint]
     L.oatk_hip_overlap_pairs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.oatk_hip_overlap_hist_from_pairs.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.oatk_hip_overlap_hist.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

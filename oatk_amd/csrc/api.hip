@@ -84,6 +84,7 @@ struct oatk_hip_ctx {
     struct OvlState *ovl = nullptr;     // pair-distance tables (api_ovl.inc)
     struct RaState *ra = nullptr;       // read alignment buffers (api_align.inc)
     struct RcState *rc = nullptr;       // coverage from read alignments (api_racov.inc)
+    struct McState *mc = nullptr;       // mini-circle repeat units (api_minicircle.inc)
     struct MultiState *multi = nullptr; // merged table / sharded correction (api_multi.inc)
 };
 
@@ -144,6 +145,7 @@ static void t_collect(oatk_hip_ctx *ctx, int first, int last)
 #include "api_consstr_multi.inc"
 #include "api_racov.inc"
 #include "api_multiplex.inc"
+#include "api_minicircle.inc"
 
 static void staging_free(oatk_hip_ctx *ctx)
 {
@@ -199,6 +201,7 @@ void oatk_hip_destroy(oatk_hip_ctx *ctx)
     ovl_state_free(ctx);
     ra_state_free(ctx);
     rc_state_free(ctx);
+    mc_state_free(ctx);
     multi_state_free(ctx);
     for (int i = 0; i <= OATK_T_COUNT_; ++i) {
         (void) hipEventDestroy(ctx->ev[i][0]);
@@ -764,6 +767,7 @@ int oatk_hip_buffer(oatk_hip_ctx *ctx, int which, const void **d_ptr, uint64_t *
     if (which >= OATK_BUF_INGEST_SEQ && which <= OATK_BUF_INGEST_HDR) return ing_buffer(ctx, which, d_ptr, bytes);      // precedes any scan
     if (which >= OATK_BUF_MG_H && which <= OATK_BUF_MG_LCOV) return multi_buffer(ctx, which, d_ptr, bytes);
     if (which >= OATK_BUF_MG_G_H && which <= OATK_BUF_MG_POS_GKID) return multi_tail_buffer(ctx, which, d_ptr, bytes);
+    if (which >= OATK_BUF_MC_UNIT && which <= OATK_BUF_MC_PATH_CNT) return mc_buffer(ctx, which, d_ptr, bytes);      // (uploaded alignments need no scan)
     if (!ctx->scanned) { ctx->err = "no resident scan"; return OATK_E_STATE; }
     const uint64_t n = ctx->n_reads, occ = ctx->n_occ, ns = ctx->n_scm_total;
     const void *p = nullptr;

@@ -32,6 +32,7 @@ _DTYPES = {
     "MG_H": np.uint64, "MG_S": np.uint64, "MG_COV": np.uint32, "MG_L2G": np.uint32, "MG_EC_COV": np.uint32, "MG_EC_DEL": np.uint8, "MG_LCOV": np.uint32,
     "AG_SCM_DEL": np.uint8, "AG_VTX_SCM": np.uint32, "AG_VTX_COV": np.uint32, "AG_IDX_P": np.uint64, "AG_IDX_N": np.uint32,
     "AG_ARC_V": np.uint64, "AG_ARC_W": np.uint64, "AG_ARC_COV": np.uint32, "AG_ARC_COMP": np.uint8, "AG_ARC_LINK": np.uint64,
+    "MC_UNIT": np.uint64, "MC_PATH_OFF": np.uint64, "MC_PATH_V": np.uint32, "MC_PATH_CNT": np.uint64,
 }
 
 
@@ -606,6 +607,29 @@ class HipSyncasm:
     def ra_triplet_scores_sharded(self, comm, graph, aln=None, n_pair_cap=None):
         """ra_triplet_scores with the reads sharded by record: the same result on every rank, bit for bit the one-handle call's"""
         return self._triplet_scores(comm, graph, aln, n_pair_cap)
+
+    def ra_minicircle_units(self, anchor, aln=None):
+        """the repeat units of the mini-circle path finder round unitig `anchor` (extract_minicircles_with_anchor, path_finder.c:539-693): returns
+        (unit, path_off, path_v, path_cnt) -- per alignment record beg << 33 | end << 1 | rev or 2^64 - 1, and the distinct canonical paths in
+        path_cmpfunc order with the number of records behind each.  aln: a dict with off and uid (the other fields of a flat alignment are not
+        read), None = the resident alignments of the last read_alignment."""
+        a = keep = None
+        if aln is not None:
+            keep = [np.ascontiguousarray(aln["off"], dtype=np.uint64), np.ascontiguousarray(aln["uid"], dtype=np.uint64)]
+            a = _lib.RacovAln(max(len(keep[0]), 1) - 1, len(keep[1]), None, keep[0].ctypes.data, None, keep[1].ctypes.data, None, None, None, None)
+        nv, n_path, n_vtx = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.oatk_hip_ra_minicircle_units(self.h, None if a is None else C.byref(a), int(anchor), C.byref(nv), C.byref(n_path), C.byref(n_vtx)),
+                    "oatk_hip_ra_minicircle_units")
+        return self.fetch("MC_UNIT"), self.fetch("MC_PATH_OFF"), self.fetch("MC_PATH_V"), self.fetch("MC_PATH_CNT")
+
+    def ra_minicircle_times(self):
+        """(ms of the last ra_minicircle_units' three device phases -- units, paths, distinct --, compare rounds of the distinct paths)"""
+        ms, rounds = (C.c_float * 3)(), C.c_uint64()
+        self._check(self.L.oatk_hip_ra_minicircle_times(self.h, ms, C.byref(rounds)), "oatk_hip_ra_minicircle_times")
+        return [float(x) for x in ms], int(rounds.value)
+
+    def debug_mc_hash_bits(self, bits):
+        self._check(self.L.oatk_hip_debug_mc_hash_bits(self.h, bits), "oatk_hip_debug_mc_hash_bits")
 
     def _racov_aln(self, aln):
         if aln is None:
