@@ -71,7 +71,7 @@ struct oatk_hip_ctx {
 
     // count outputs / scratch
     DevBuf n_scm64, scm_off, pos_hash, pos_lo, pos_smer, pos_mpos, pos_kid;
-    DevBuf key_hash, key_sorted, iota, perm, head, head_idx, newclus, clus_id, bad_head, tag, tmp_perm, flags, kloc, smer_sorted, slot_rec, scm_loc;
+    DevBuf key_hash, key_sorted, iota, perm, head, newclus, clus_id, bad_head, tag, tmp_perm, flags, kloc, smer_sorted, slot_rec, scm_loc;
     DevBuf scm_h, scm_s, scm_cov, scm_occ_off, scm_occ;
     DevBuf tmp;           // rocprim temporary storage
     struct EcState *ec = nullptr;   // error-correction buffers (api_ec.inc)
@@ -479,6 +479,7 @@ __global__ void append_rebase_kernel(const uint64_t *src, uint64_t *dst, uint64_
     uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = src[i] + add;
 }
+
 __global__ void append_iota_kernel(uint32_t *iota, uint64_t first, uint64_t n)
 {
     uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -636,7 +637,7 @@ int oatk_hip_count(oatk_hip_ctx *ctx)
     if (n == 0) { ctx->counted = true; return OATK_OK; }
     const unsigned nb = (unsigned) ((n + 255) / 256);
 
-    ENSURE(key_sorted, n * 8); ENSURE(perm, n * 4); ENSURE(head, n * 4); ENSURE(head_idx, n * 4); ENSURE(newclus, n * 4); ENSURE(kloc, n * 8);
+    ENSURE(key_sorted, n * 8); ENSURE(perm, n * 4); ENSURE(head, n * 4); ENSURE(newclus, n * 4);
     if (ctx->seq_bytes >> 4 >= 0xFFFFFFFFULL) { ctx->err = "batch too large for 32-bit hoco word indices (64 GB of bases)"; return OATK_E_ARG; }
     ENSURE(clus_id, n * 4); ENSURE(bad_head, n * 4); ENSURE(tag, n * 4); ENSURE(tmp_perm, n * 4); ENSURE(flags, 64);
     ENSURE(pos_kid, n * 8); ENSURE(scm_occ, n * 8);
@@ -655,7 +656,7 @@ sort_again:
         const unsigned lo_bit = full_sort? 0u : (unsigned) OATK_SORT_LOW_BITS;
         PRIM(rocprim::radix_sort_pairs, ctx->key_hash.as<uint64_t>(), ctx->key_sorted.as<uint64_t>(), ctx->iota.as<uint32_t>(), ctx->perm.as<uint32_t>(), n, lo_bit, 64, ctx->stream);
         if (!full_sort) {
-            uint32_t *owner = ctx->head.as<uint32_t>();              // (free until mark_heads_kernel)
+            uint32_t *owner = ctx->head.as<uint32_t>();              // (free until pair_sum_kernel<true>)
             CK(hipMemsetAsync(owner, 0xFF, n * 4, ctx->stream));
             hipLaunchKernelGGL(sort_repair_find_kernel, dim3(nb), dim3(256), 0, ctx->stream, ctx->key_sorted.as<uint64_t>(), (uint32_t) n, owner, ctx->flags.as<uint32_t>());
             hipLaunchKernelGGL(sort_repair_kernel, dim3(nb), dim3(256), 0, ctx->stream, ctx->key_sorted.as<uint64_t>(), ctx->perm.as<uint32_t>(), (uint32_t) n, owner,
@@ -669,10 +670,9 @@ sort_again:
     g.sorted_key = ctx->key_sorted.as<uint64_t>(), g.perm = ctx->perm.as<uint32_t>(), g.n_rec = (uint32_t) n;
     g.pos_lo = ctx->pos_lo.as<uint64_t>(), g.pos_mpos = ctx->pos_mpos.as<uint32_t>(), g.hoco_s = ctx->hoco_s.as<uint8_t>();
     g.off = ctx->d_off, g.sid0 = ctx->sid0, g.K = ctx->K;
-    g.head = ctx->head.as<uint32_t>(), g.head_idx = ctx->head_idx.as<uint32_t>(), g.newclus = ctx->newclus.as<uint32_t>();
-    g.loc = ctx->kloc.as<uint64_t>();
-    ENSURE(smer_sorted, n * 8);
-    g.pos_smer = ctx->pos_smer.as<uint64_t>(), g.occ_sorted = ctx->scm_occ.as<uint64_t>(), g.smer_sorted = ctx->smer_sorted.as<uint64_t>();
+    g.head = ctx->head.as<uint32_t>(), g.newclus = ctx->newclus.as<uint32_t>();
+    g.loc = nullptr, g.smer_sorted = nullptr;          // (the pessimistic order's: below)
+    g.pos_smer = ctx->pos_smer.as<uint64_t>(), g.occ_sorted = ctx->scm_occ.as<uint64_t>();
     g.flags = ctx->flags.as<uint32_t>();
     ENSURE(slot_rec, n * 32);
     g.slot_rec = ctx->slot_rec.as<uint4>();
@@ -681,14 +681,13 @@ sort_again:
         ctx->slots_packed = true;
     }
     hipLaunchKernelGGL((pair_sum_kernel<false>), dim3(2048), dim3(256), 0, ctx->stream, ctx->key_hash.as<uint64_t>(), (const uint32_t *) nullptr, (uint32_t) n, ctx->flags.as<uint32_t>(), 8,
-                       (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr);
-    // Optimistic order (round 4): heads -> ids -> ONE pass through the permutation (the verification's gathers + the table's and the reads' ids) -> verification.
-    // A hash group with two k-mers (never seen outside the forced-collision tests) takes the pessimistic order afterwards: split, gather again, ids again, write again.
+                       (uint32_t *) nullptr, (uint32_t *) nullptr);
+    // Optimistic order: heads -> ids -> ONE pass through the permutation that gathers, writes the table's and the reads' ids and verifies k-mers and s-mers
+    // (count.hpp: gather_verify_kernel).  A hash group with two k-mers (never seen outside the forced-collision tests) takes the pessimistic order afterwards:
+    // split, gather again, ids again, write again, s-mers again.
     // (the pass over the sorted keys that checks the sort also marks the heads)
     hipLaunchKernelGGL((pair_sum_kernel<true>), dim3(2048), dim3(256), 0, ctx->stream, ctx->key_sorted.as<uint64_t>(), ctx->perm.as<uint32_t>(), (uint32_t) n, ctx->flags.as<uint32_t>(), 12,
-                       g.head, g.newclus, g.head_idx);
-    // head_idx := index of the latest head at or before i
-    PRIM(rocprim::inclusive_scan, ctx->head_idx.as<uint32_t>(), ctx->head_idx.as<uint32_t>(), n, rocprim::maximum<uint32_t>(), ctx->stream);
+                       g.head, g.newclus);
     uint32_t n_scm = 0;
     FinishArgs f;
     auto ids = [&]() -> int {               // clus_id := number of heads at or before i (= id + 1); n_scm; room for the table
@@ -707,9 +706,9 @@ sort_again:
         return OATK_OK;
     };
     { int rc = ids(); if (rc) return rc; }
-    hipLaunchKernelGGL(gather_finish_kernel, dim3(nb), dim3(256), 0, ctx->stream, g, f, ctx->clus_id.as<uint32_t>(), n_scm);
     CK(hipMemsetAsync(ctx->bad_head.p, 0, n * 4, ctx->stream));
-    hipLaunchKernelGGL(verify_group_kernel, dim3((unsigned) ((n + 8 * OATK_VG_STRIP - 1) / (8 * OATK_VG_STRIP))), dim3(256), 0, ctx->stream, g, ctx->bad_head.as<uint32_t>());
+    hipLaunchKernelGGL(gather_verify_kernel, dim3((unsigned) ((n + OATK_OP_TILE - 1) / OATK_OP_TILE)), dim3(OATK_OP_TILE), 0, ctx->stream, g, f, ctx->clus_id.as<uint32_t>(), n_scm,
+                       ctx->bad_head.as<uint32_t>());
     // (clus_id holds id + 1, and every reader takes it so)
     uint32_t fl[16];
     CK(hipMemcpyAsync(fl, ctx->flags.p, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
@@ -729,13 +728,17 @@ sort_again:
     }
     if (fl[0]) {
         ctx->collisions = 1;
+        ENSURE(kloc, n * 8); ENSURE(smer_sorted, n * 8);
+        g.loc = ctx->kloc.as<uint64_t>(), g.smer_sorted = ctx->smer_sorted.as<uint64_t>();
         hipLaunchKernelGGL(split_collisions_kernel, dim3(nb), dim3(256), 0, ctx->stream, g, ctx->bad_head.as<uint32_t>(), ctx->perm.as<uint32_t>(),
                            ctx->tag.as<uint32_t>(), ctx->tmp_perm.as<uint32_t>());
         hipLaunchKernelGGL(regather_kernel, dim3(nb), dim3(256), 0, ctx->stream, g);
         { int rc = ids(); if (rc) return rc; }
         hipLaunchKernelGGL(finish_heads_kernel, dim3(nb), dim3(256), 0, ctx->stream, f, n_scm);
+        // (the one-pass check compared s-mers inside HASH groups: decided again on the final clusters)
+        CK(hipMemsetAsync(ctx->flags.as<uint32_t>() + 1, 0, 4, ctx->stream));
+        hipLaunchKernelGGL(check_smer_kernel, dim3(nb), dim3(256), 0, ctx->stream, f);
     }
-    hipLaunchKernelGGL(check_smer_kernel, dim3(nb), dim3(256), 0, ctx->stream, f);
     hipLaunchKernelGGL(cov_kernel, dim3((n_scm + 255) / 256), dim3(256), 0, ctx->stream, ctx->scm_occ_off.as<uint64_t>(), ctx->scm_cov.as<uint32_t>(), n_scm);
     t_end(ctx, OATK_T_COUNT_GROUP);
     CK(hipGetLastError());

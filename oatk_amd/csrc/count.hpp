@@ -8,14 +8,15 @@
 //      per-read arrays (m_pos, s_mer, hash) AND a sequence already ordered by the low 64 key bits.  The
 //      scan's k-mer hash kernel does it as it finishes a record (kmer_hash.hpp).
 //   2. one stable 64-bit radix sort of (hash -> slot) finishes the 128-bit order.
-//   3. mark_heads / verify_group: equal-hash neighbours are compared base-for-base with their group head
-//      (one wave per record, one 32-base word per lane) -- the collision check the reference performs.
+//   3. gather_verify: equal-hash neighbours are compared base-for-base (half a wave per strip of eight records,
+//      one 32-base word per lane) -- the collision check the reference performs -- in the pass that writes the table.
 //   4. split_collisions: groups that really hold different k-mers (never seen in practice; forced in tests
 //      by masking hash bits) are partitioned in first-seen order by one lane per group.
 //   5. IDs = prefix sum of new-cluster flags; coverage, CSR occurrence lists, s-mer consistency
 //      (syncmer.c:1365-1376) and the per-read k_mer = id << 1 rewrite (:1378) are one pass each.
 #pragma once
 #include "common.hpp"
+#include "count_onepass_core.hpp"
 
 namespace oatk {
 
@@ -55,10 +56,10 @@ struct GroupArgs {
     uint64_t sid0;
     int K;
     uint32_t *head;               // 1 where a new equal-hash group starts
-    uint32_t *head_idx;           // sorted index of the group head (filled by a max-scan)
     uint32_t *newclus;            // 1 where a new syncmer (cluster) starts; starts as a copy of head
     uint32_t *flags;              // [0] some group holds different k-mers, [1] s-mer mismatch, [2] too many clusters
     uint64_t *loc;                // where the k-mer of sorted record i lives: (32-bit word index of its read's hoco string) << 32 | pos << 1 | rev
+                                  // (loc and smer_sorted exist in the pessimistic order only: regather_kernel)
     // what else the sort permutation is followed for, fetched while it is followed the first time: the occurrence word (sid | index | strand)
     // and the s-mer of every sorted record -- finish_heads and check_smer then read them in order instead of gathering them again
     const uint64_t *pos_smer;
@@ -143,14 +144,13 @@ __device__ __forceinline__ void pair_sums(uint64_t key, uint32_t slot, uint64_t 
     s1 = x;
 }
 // perm == nullptr: the pairs are (key[i], i) -- the sort's input; otherwise (key[i], perm[i]) and the keys are checked to ascend.
-// HEADS (the sort's output only): the pass that compares every sorted key with the one in front of it also says where an equal-hash group starts -- head,
-// newclus and head_idx as the optimistic order wants them (round 4: with the ids known from a scan of these flags BEFORE the verification -- on the
-// assumption, checked afterwards, that no hash group holds two k-mers -- one pass through the permutation both gathers what verify_group needs and writes
-// what finish_heads_kernel wrote in a second pass (gather_finish_kernel); a collision falls back to the two passes below).  The three arrays are only
-// touched when HEADS is set.
+// HEADS (the sort's output only): the pass that compares every sorted key with the one in front of it also says where an equal-hash group starts -- head
+// and newclus as the optimistic order wants them (round 4: with the ids known from a scan of these flags BEFORE the verification -- on the
+// assumption, checked in the same pass, that no hash group holds two k-mers -- one pass through the permutation gathers, writes what finish_heads_kernel
+// writes and verifies (gather_verify_kernel); a collision falls back to the passes below).  The two arrays are only touched when HEADS is set.
 template <bool HEADS>
 __global__ __launch_bounds__(256) void pair_sum_kernel(const uint64_t *key, const uint32_t *perm, uint32_t n, uint32_t *flags, int at,
-                                                       uint32_t *head, uint32_t *newclus, uint32_t *head_idx)
+                                                       uint32_t *head, uint32_t *newclus)
 {
     __shared__ uint64_t part[2][4];
     uint64_t s0 = 0, s1 = 0;
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void pair_sum_kernel(const uint64_t *key, cons
             if (k[u] < kp[u]) inv = true;
             if (HEADS) {
                 const uint32_t i = (uint32_t) (i0 + u * stride), h = i == 0 || k[u] != kp[u];
-                head[i] = h, newclus[i] = h, head_idx[i] = h? i : 0u;
+                head[i] = h, newclus[i] = h;
             }
         }
     }
@@ -190,21 +190,7 @@ __global__ __launch_bounds__(256) void pair_sum_kernel(const uint64_t *key, cons
     }
 }
 
-__global__ void mark_heads_kernel(GroupArgs a)
-{
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n_rec) return;
-    uint32_t h = i == 0 || a.sorted_key[i] != a.sorted_key[i - 1];
-    a.head[i] = h;
-    a.newclus[i] = h;
-    a.head_idx[i] = h? i : 0u;
-    // the gathers verify_group would otherwise chain in front of every k-mer read, done here once, a lane per record
-    const uint32_t p = a.perm[i];
-    const uint4 r0 = a.slot_rec[2 * (size_t) p], r1 = a.slot_rec[2 * (size_t) p + 1];
-    a.loc[i] = (uint64_t) r1.y << 32 | r1.x;
-    a.occ_sorted[i] = (uint64_t) r0.y << 32 | r0.x, a.smer_sorted[i] = (uint64_t) r0.w << 32 | r0.z;
-}
-// after a split of colliding groups the permutation has changed inside them: fetch again
+// after a split of colliding groups the permutation has changed inside them: fetch what finish_heads and check_smer read in order
 __global__ void regather_kernel(GroupArgs a)
 {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -213,77 +199,6 @@ __global__ void regather_kernel(GroupArgs a)
     const uint4 r0 = a.slot_rec[2 * (size_t) p], r1 = a.slot_rec[2 * (size_t) p + 1];
     a.loc[i] = (uint64_t) r1.y << 32 | r1.x;
     a.occ_sorted[i] = (uint64_t) r0.y << 32 | r0.x, a.smer_sorted[i] = (uint64_t) r0.w << 32 | r0.z;
-}
-
-// Is the k-mer of every sorted record that is not a group head identical to its head's?  Half a wave (32 lanes x 32 bases cover k <= 1024
-// in one step) takes a STRIP of eight consecutive records.  The kernel is a chain of dependent gathers -- head flag and head index, the two
-// locators, the k-mer words -- and its rate is (bytes in flight) / (HBM latency): with two records per half wave and a wave that retires
-// after them it moved 1.5 TB/s at full occupancy (9.0 ms at config 3).  A strip pays the first two levels once for eight records (lane r of
-// the half wave fetches record r's, the values travel by shuffle) and has the sixteen k-mer word loads of the strip in flight together.
-#ifndef OATK_VG_STRIP
-#define OATK_VG_STRIP 8
-#endif
-#ifndef OATK_VFY_WAVES
-#define OATK_VFY_WAVES 1
-#endif
-__global__ __launch_bounds__(256, OATK_VFY_WAVES) void verify_group_kernel(GroupArgs a, uint32_t *bad_head)
-{
-    const uint32_t hl = threadIdx.x & 31, half0 = threadIdx.x & 32;       // lane in the half wave; first lane of the half wave within the wave
-    const uint32_t i0 = (uint32_t) OATK_VG_STRIP * (blockIdx.x * (blockDim.x >> 5) + (threadIdx.x >> 5));
-    // level 1 + 2: lane r < 8 of the half wave owns record i0 + r
-    uint32_t my_h = 0;
-    uint64_t my_lp = 0, my_lq = 0;
-    bool my_live = false;
-    if (hl < OATK_VG_STRIP) {
-        const uint32_t i = i0 + hl;
-        my_live = i < a.n_rec && !a.head[i];
-        if (my_live) {
-            my_h = a.head_idx[i];
-            my_lp = a.loc[i];
-            my_lq = a.loc[my_h];
-        }
-    }
-    const uint64_t live_mask = (__ballot(my_live) >> half0) & ((1ULL << OATK_VG_STRIP) - 1ULL);
-    if (live_mask == 0) return;                                           // (a strip of heads: singletons, most of the error k-mers)
-    const uint32_t *hs32 = (const uint32_t *) a.hoco_s;
-    const int nw = (a.K + 31) / 32;
-    uint32_t diff = 0;                                                    // bit r: this lane saw record r differ from its head
-    // A strip usually lies inside ONE group (a solid syncmer occurs once per read that covers it: tens of records at HiFi depth): then its
-    // records share their head, whose k-mer is fetched and realigned once instead of eight times.  Decided for the wave (both strips).
-    const uint32_t first_live = (uint32_t) __builtin_ctzll(live_mask);
-    const uint64_t lq0 = (uint64_t) __shfl((long long) my_lq, (int) (half0 + first_live));
-    const bool one_head = __ballot(my_live && my_lq != lq0) == 0;
-    for (int w0 = 0; w0 < nw; w0 += 32) {                                 // (uniform trip count: every lane takes part in the shuffles, k < 225 idles lanes in the loads only)
-        const int wd = w0 + (int) hl;
-        const bool in = wd < nw;
-        uint64_t p[OATK_VG_STRIP], q[OATK_VG_STRIP];
-        if (one_head) {
-            const uint64_t q0 = in? kmer_word_global(hs32 + (lq0 >> 32), (uint32_t) lq0 >> 1, (uint32_t) lq0 & 1u, a.K, wd) : 0;
-#pragma unroll
-            for (int r = 0; r < OATK_VG_STRIP; ++r) {                     // every load of the strip is issued before the first comparison
-                const uint64_t lp = (uint64_t) __shfl((long long) my_lp, (int) (half0 + r));
-                const bool live = in && ((live_mask >> r) & 1u);
-                p[r] = live? kmer_word_global(hs32 + (lp >> 32), (uint32_t) lp >> 1, (uint32_t) lp & 1u, a.K, wd) : q0;
-            }
-#pragma unroll
-            for (int r = 0; r < OATK_VG_STRIP; ++r) diff |= (uint32_t) (p[r] != q0) << r;
-        } else {
-#pragma unroll
-            for (int r = 0; r < OATK_VG_STRIP; ++r) {
-                const uint64_t lp = (uint64_t) __shfl((long long) my_lp, (int) (half0 + r)), lq = (uint64_t) __shfl((long long) my_lq, (int) (half0 + r));
-                const bool live = in && ((live_mask >> r) & 1u);
-                p[r] = live? kmer_word_global(hs32 + (lp >> 32), (uint32_t) lp >> 1, (uint32_t) lp & 1u, a.K, wd) : 0;
-                q[r] = live? kmer_word_global(hs32 + (lq >> 32), (uint32_t) lq >> 1, (uint32_t) lq & 1u, a.K, wd) : 0;
-            }
-#pragma unroll
-            for (int r = 0; r < OATK_VG_STRIP; ++r) diff |= (uint32_t) (p[r] != q[r]) << r;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < OATK_VG_STRIP; ++r) {
-        const uint64_t bad = (__ballot((diff >> r) & 1u) >> half0) & 0xFFFFFFFFULL;
-        if (bad && hl == (uint32_t) r) a.flags[0] = 1u, bad_head[my_h] = 1u;   // lane r holds record r's head index
-    }
 }
 
 // one lane per colliding group: first-seen clustering, then a stable partition of the group's slice of perm
@@ -337,11 +252,11 @@ struct FinishArgs {
     const uint32_t *newclus;
     const uint32_t *clus_id1;     // inclusive scan of newclus: id + 1
     uint32_t n_rec;
-    const uint64_t *sorted_key, *smer_sorted;     // smer_sorted: the s-mer of every sorted record (mark_heads_kernel)
+    const uint64_t *sorted_key, *smer_sorted;     // smer_sorted: the s-mer of every sorted record (regather_kernel)
     uint64_t *scm_h, *scm_s;
     uint64_t *scm_occ_off;        // [n_scm + 1]
-    uint64_t *scm_occ;            // [n_rec]: written by mark_heads_kernel (GroupArgs::occ_sorted)
-    const uint64_t *loc;          // k-mer locator of every sorted record (mark_heads_kernel)
+    uint64_t *scm_occ;            // [n_rec]: written by gather_verify_kernel / regather_kernel (GroupArgs::occ_sorted)
+    const uint64_t *loc;          // k-mer locator of every sorted record (regather_kernel)
     uint64_t *scm_loc;            // [n_scm] where a syncmer's k-mer can be read: the locator of its first occurrence (what the EC graph's vertices need)
     uint64_t *pos_kid;            // id << 1 per slot
     uint32_t *flags;
@@ -362,27 +277,95 @@ __global__ void finish_heads_kernel(FinishArgs a, uint32_t n_scm)
     if (i == a.n_rec - 1) a.scm_occ_off[n_scm] = a.n_rec;
 }
 
-// mark_heads_kernel's gathers and finish_heads_kernel's writes in one pass (clus_id1 = id + 1, straight from the inclusive scan of the head flags)
-__global__ void gather_finish_kernel(GroupArgs g, FinishArgs a, const uint32_t *clus_id1, uint32_t n_scm)
+// The optimistic order in ONE pass over the sorted records (clus_id1 = id + 1, straight from the inclusive scan of the head flags): a tile of
+// OATK_OP_TILE records per workgroup, in two halves.
+//   Gather and finish, a lane per record: follow perm into the 32-byte slot record, write the occurrence word, the read's id, and at a head the
+//   table's row.  The record's k-mer locator and s-mer go to LDS and nowhere else; lane 0 also fetches the record in front of the tile when the
+//   tile's first record is no head.
+//   Check: is every record that is no head identical to its PREDECESSOR in sorted order -- k-mer and s-mer?  Equality is transitive, so that says
+//   the same as "identical to its group head", and the predecessor's locator and s-mer lie one LDS slot to the left (count_onepass_core.hpp).
+//   The s-mers are compared by the lane that gathered the record.  The k-mers go by STRIPs of eight consecutive records, half a wave per strip
+//   (32 lanes x 32 bases cover k <= 1024 in one step, one 32-base word per lane): a strip inside one group -- the usual case: a solid syncmer
+//   occurs once per read that covers it, tens of records at HiFi depth -- loads nine k-mers, the eight records' and the one in front, all
+//   in flight together before the first comparison.  A strip of heads (singletons, most of the error k-mers) does nothing.
+// The check is a chain of dependent gathers and its rate is (bytes in flight) / (HBM latency); what it needs from the gather half arrives through
+// LDS instead of through three per-record arrays in HBM (locator, s-mer, head index: 40 B written and 60 B read per record) and one max-scan.
+// A k-mer that differs sets flags[0] and bad_head at the head of its group, found by walking back over newclus (forced-collision tests only: the
+// host then takes the pessimistic order below, which decides flags[1] again on its final clusters); an s-mer that differs sets flags[1].
+#ifndef OATK_VG_STRIP
+#define OATK_VG_STRIP 8
+#endif
+#ifndef OATK_VFY_WAVES
+#define OATK_VFY_WAVES 1
+#endif
+#define OATK_OP_TILE 256
+static_assert(64 % OATK_VG_STRIP == 0 && OATK_VG_STRIP <= 31 && OATK_OP_TILE % 64 == 0, "a wave's 64 head flags hold whole strips");
+__global__ __launch_bounds__(OATK_OP_TILE, OATK_VFY_WAVES) void gather_verify_kernel(GroupArgs g, FinishArgs a, const uint32_t *clus_id1, uint32_t n_scm, uint32_t *bad_head)
 {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n_rec) return;
-    const uint32_t p = g.perm[i], id = clus_id1[i] - 1u;
-    const uint4 r0 = g.slot_rec[2 * (size_t) p], r1 = g.slot_rec[2 * (size_t) p + 1];
-    const uint64_t loc = (uint64_t) r1.y << 32 | r1.x, smer = (uint64_t) r0.w << 32 | r0.z;
-    g.loc[i] = loc;
-    g.occ_sorted[i] = (uint64_t) r0.y << 32 | r0.x, g.smer_sorted[i] = smer;
-    a.pos_kid[p] = (uint64_t) id << 1;
-    if (g.newclus[i]) {
-        a.scm_h[id] = a.sorted_key[i];
-        a.scm_s[id] = smer;
-        a.scm_occ_off[id] = i;
-        a.scm_loc[id] = loc;
+    __shared__ uint64_t s_loc[OATK_OP_TILE + 1], s_sm[OATK_OP_TILE + 1];      // [1 + t]: record t0 + t; [0]: the record in front of the tile
+    __shared__ uint64_t s_live[OATK_OP_TILE / 64];                            // bit t: record t0 + t is in range and no head
+    const uint32_t t = threadIdx.x, t0 = blockIdx.x * (uint32_t) OATK_OP_TILE, i = t0 + t;
+    uint64_t loc = 0, smer = 0;
+    bool live = false;
+    if (i < a.n_rec) {
+        const uint32_t p = g.perm[i], id = clus_id1[i] - 1u, nc = g.newclus[i];
+        const uint32_t pp = t == 0 && i > 0? g.perm[i - 1] : 0u;
+        const uint4 r0 = g.slot_rec[2 * (size_t) p], r1 = g.slot_rec[2 * (size_t) p + 1];
+        live = !nc && i > 0;
+        if (t == 0 && live) {                  // (both gathers of this lane are in flight together)
+            const uint4 q0 = g.slot_rec[2 * (size_t) pp], q1 = g.slot_rec[2 * (size_t) pp + 1];
+            s_loc[0] = (uint64_t) q1.y << 32 | q1.x, s_sm[0] = (uint64_t) q0.w << 32 | q0.z;
+        }
+        loc = (uint64_t) r1.y << 32 | r1.x, smer = (uint64_t) r0.w << 32 | r0.z;
+        g.occ_sorted[i] = (uint64_t) r0.y << 32 | r0.x;
+        a.pos_kid[p] = (uint64_t) id << 1;
+        if (nc) {
+            a.scm_h[id] = a.sorted_key[i];
+            a.scm_s[id] = smer;
+            a.scm_occ_off[id] = i;
+            a.scm_loc[id] = loc;
+        }
+        if (i == a.n_rec - 1) a.scm_occ_off[n_scm] = a.n_rec;
     }
-    if (i == a.n_rec - 1) a.scm_occ_off[n_scm] = a.n_rec;
+    s_loc[1 + t] = loc, s_sm[1 + t] = smer;
+    const uint64_t wave_live = __ballot(live);
+    if ((t & 63u) == 0) s_live[t >> 6] = wave_live;
+    __syncthreads();
+    // identical k-mers must carry the same s-mer (fatal in the reference, syncmer.c:1370-1376); only meaningful where the k-mers ARE identical
+    if (live && s_sm[t] != smer) g.flags[1] = 1u;
+
+    const uint32_t hl = t & 31u, half0 = t & 32u;                             // lane in the half wave; first lane of the half wave within the wave
+    const uint32_t *hs32 = (const uint32_t *) g.hoco_s;
+    const int nw = (g.K + 31) / 32;
+    constexpr uint32_t PER_HALF = OATK_OP_TILE / OATK_VG_STRIP / (OATK_OP_TILE / 32);       // strips per half wave: those of the records its wave gathered
+#pragma unroll 1
+    for (uint32_t u = 0; u < PER_HALF; ++u) {
+        const uint32_t s0 = ((t >> 5) * PER_HALF + u) * OATK_VG_STRIP;        // the strip's first record within the tile
+        const uint32_t live_mask = (uint32_t) (s_live[s0 >> 6] >> (s0 & 63u)) & ((1u << OATK_VG_STRIP) - 1u);
+        if (live_mask == 0) continue;
+        const uint32_t need = onepass_need_mask(live_mask);
+        uint32_t diff = 0;                                                    // bit r: this lane saw record s0 + r differ from the one in front of it
+        for (int w0 = 0; w0 < nw; w0 += 32) {
+            const int wd = w0 + (int) hl;
+            const bool in = wd < nw;
+            uint64_t w[OATK_VG_STRIP + 1];
+#pragma unroll
+            for (int j = 0; j <= OATK_VG_STRIP; ++j) {                        // every load of the strip is issued before the first comparison
+                const uint64_t lp = s_loc[s0 + j];
+                w[j] = in && ((need >> j) & 1u)? kmer_word_global(hs32 + (lp >> 32), (uint32_t) lp >> 1, (uint32_t) lp & 1u, g.K, wd) : 0;
+            }
+            diff |= onepass_diff_mask<OATK_VG_STRIP>(w, live_mask);
+        }
+        if (((__ballot(diff != 0) >> half0) & 0xFFFFFFFFULL) == 0) continue;
+#pragma unroll
+        for (int r = 0; r < OATK_VG_STRIP; ++r) {
+            const uint64_t bad = (__ballot((diff >> r) & 1u) >> half0) & 0xFFFFFFFFULL;
+            if (bad && hl == (uint32_t) r) g.flags[0] = 1u, bad_head[onepass_head_of(g.newclus, t0 + s0 + r)] = 1u;
+        }
+    }
 }
 
-// identical k-mers must carry the same s-mer (fatal in the reference, syncmer.c:1370-1376)
+// identical k-mers must carry the same s-mer (fatal in the reference, syncmer.c:1370-1376): on the final clusters of the pessimistic order
 __global__ void check_smer_kernel(FinishArgs a)
 {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
